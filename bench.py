@@ -3,8 +3,14 @@
 of the full OsuFusion UNet (dim_h=256, 343.5 M parameters) at per-GPU batch 32, L=4096, bf16 compute -- BASELINE.json
 configs[1] (N=1) / configs[2] (N>1, weak scaling: global batch 32*N, one process per GPU, RCCL over xGMI).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the result line.  --full adds everything else the benchmark measures: the
+HIP-event roofline of the timed steps' attention kernels, and on one GPU the CPU baseline and, at the full size, the fp32 compute modes,
+the config-4 sampler and the DoRA config-5 shard (each can still be left out with its --no-* switch).  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (see dump_outputs).  Every step starts from the same seeded parameters (restored between
+steps, outside the timed spans), so that with the same arguments a run's outputs are the same, to rounding, in every run.
 
 Shape-mapping note printed with every result: the reference UNet takes audio as (B, 96, L) with the
 same L as the map sequence (models/diffusion.py:86); BASELINE's "C=256" is dim_h=256 and "audio-ctx=1024x128" has no literal
@@ -96,6 +102,41 @@ def build_model(device, dim_h: int):
     with torch.no_grad():                                  # the reference zero-inits final_conv (unet.py:354): every other
         model.unet.final_conv.weight.normal_(0.0, 0.02)    # gradient would be exactly zero -- use a live head instead
     return model.to(device)
+
+
+DUMP_SAMPLE = 1 << 22                   # elements per sampled array of --dump-outputs: 16 MiB of float32 each
+
+
+def dump_outputs(out_dir, model, loss, grad_norm) -> list:
+    """--dump-outputs: what a caller of the timed train step holds after its last step, as float32 .npy files in out_dir -- the loss and the
+    clipped step's gradient norm, and the trainable parameters as AdamW left them and their gradients, at a fixed seeded sample of
+    DUMP_SAMPLE positions of the named_parameters() order (every position when there are fewer).  Indexed by parameter name, not by the
+    flat buffer, whose layout follows the first backward's completion order."""
+    import numpy as np
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    sizes = torch.tensor([p.numel() for _, p in named], dtype=torch.int64)
+    ends = sizes.cumsum(0)
+    total = int(ends[-1])
+    if total <= DUMP_SAMPLE:
+        idx = torch.arange(total)
+    else:
+        idx = torch.randint(0, total, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(4096)).sort().values
+    cut = torch.searchsorted(idx, ends).tolist()       # idx[cut[i-1]:cut[i]] lie in parameter i
+    params, grads, lo = [], [], 0
+    for (name, p), hi, end in zip(named, cut, ends.tolist()):
+        if hi > lo:
+            assert p.grad is not None, f"{name} has no gradient after the timed step"
+            local = (idx[lo:hi] - (end - p.numel())).to(p.device)
+            params.append(p.detach().reshape(-1)[local].float())
+            grads.append(p.grad.detach().reshape(-1)[local].float())
+        lo = hi
+    arrays = {"loss": loss.detach().float().reshape(1), "grad_norm": grad_norm.detach().float().reshape(1),
+              "params": torch.cat(params), "grads": torch.cat(grads)}
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(out_dir / f"{name}.npy", v.cpu().numpy().astype(np.float32))
+    return sorted(arrays)
 
 
 def cpu_baseline(model, length: int, thread_counts):
@@ -292,7 +333,15 @@ def main() -> None:
     ap.add_argument("--grad-comm", choices=["fp32", "bf16"], default="fp32",
                     help="N > 1: element type of the gradient all-reduce (bf16 halves the xGMI bytes at one bf16 rounding per rank contribution; default fp32)")
     ap.add_argument("--no-fuse-rowdot", action="store_true", help="A/B: sum(dO*O) by the stand-alone pass instead of the to_out dgrad epilogue")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the attention kernels' HIP-event roofline of the timed steps "
+                         "and, on one GPU, the fp32 modes, the config-4 sampler, the CPU baseline and config 5 (subject to the --no-* switches)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed (loss, grad norm, a seeded sample of the parameters and their "
+                         "gradients) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries the ONE JSON line and nothing else: RCCL prints a five-line version banner to fd 1 at communicator set-up (seen in the
     # one-rank rehearsal, profiles/r05_rccl_one_rank/), so fd 1 is pointed at stderr for the run and the line goes to the saved descriptor
@@ -353,19 +402,42 @@ def main() -> None:
             dist.barrier()
         torch.cuda.synchronize()
 
+    # Every step, warm-up and timed, starts from the same seeded parameters, restored between the steps and outside the timed spans.
+    # The float-atomic reductions of a step (dQ, weight and bias gradients, GroupNorm statistics) round differently from run to run, and
+    # along an evolving trajectory those differences compound step by step; from a fixed start a step's outputs are a function of its
+    # inputs, equal to rounding in every run.  The AdamW moments still accumulate over the steps, as in training.
+    from osufusion_amd import functional as Fn
+    start = [(p, p.detach().clone()) for p in trainer.flat.params]
+
+    def restore():
+        with torch.no_grad():
+            torch._foreach_copy_([p.data for p, _ in start], [v for _, v in start])
+        Fn.bump_weight_epoch()                             # written behind autograd's back, as the fused optimizer does; then the
+        for job in Fn._PACK_JOBS.values():                 # grouped re-pack of the step's end again (it only takes the packs used
+            job.used = True                                # since its last call), so the next step finds its GEMM operands current
+        Fn.refresh_packs()
+
     if rank == 0:
         print(f"[bench] model + data resident; {args.warmup} warmup + {args.steps} timed steps ...", file=sys.stderr, flush=True)
     for _ in range(args.warmup):
+        restore()
         trainer.step(x, a, c, noise, t)
     sync()
-    prof = ops.KernelTimer(list(ATTN_UNITS))
+    prof = ops.KernelTimer(list(ATTN_UNITS)) if args.full else None
     ops.set_kernel_timer(prof)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
+    spans = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    for t_start, t_end in spans:                           # timed by events on the stream: the restore in between is not counted,
+        restore()                                          # and the host runs ahead of the GPU as in back-to-back steps
+        t_start.record()
         loss, gnorm = trainer.step(x, a, c, noise, t)
+        t_end.record()
     sync()
-    elapsed = time.perf_counter() - t0
+    elapsed = sum(s.elapsed_time(e) for s, e in spans) / 1e3
     ops.set_kernel_timer(None)
+    start.clear()
+    if args.dump_outputs and rank == 0:                    # before anything below touches the parameters or gradients
+        names = dump_outputs(args.dump_outputs, model, loss, gnorm)
+        print(f"[bench] outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}", file=sys.stderr, flush=True)
     if dist_on:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -401,8 +473,8 @@ def main() -> None:
         ms = 1e3 * elapsed / args.steps
         full = (args.batch, args.length, args.dim_h) == (BATCH, LENGTH, DIM_H)
         value = world * args.steps / elapsed * (args.batch / BATCH)
-        # roofline of the dominant kernel: algorithmic FLOPs per launch / mean launch duration (HIP events, timed region)
-        stats = prof.summary()
+        # roofline of the dominant kernel: algorithmic FLOPs per launch / mean launch duration (HIP events, timed region; --full only)
+        stats = prof.summary() if prof is not None else {}
         dom = max(stats, key=lambda k: stats[k]["total_ms"]) if stats else None
         roof = None
         if dom is not None:
@@ -439,8 +511,9 @@ def main() -> None:
                                    f"audio (B,96,L) [BASELINE 'audio-ctx=1024x128' maps to the (B,1024,L/8) bottleneck code]",
                        "global_batch": args.batch * world, "seq_len": args.length, "parallelism": f"dp{world}"},
             "loss": round(loss.item(), 5), "grad_norm": round(gnorm.item(), 4),
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         if comm is not None:
             out["comm"] = comm
 
@@ -454,7 +527,8 @@ def main() -> None:
         if args.timed_mode != "bf16":
             out["metric"] += f" [PROFILING RUN in the {args.timed_mode} compute mode -- not the headline number]"
             out["dtype"] = args.timed_mode
-        if world == 1 and not args.no_fp32_mode and not args.lora and full and args.timed_mode == "bf16":
+        more = world == 1 and args.full                    # the single-GPU legs beyond the headline figure
+        if more and not args.no_fp32_mode and not args.lora and full and args.timed_mode == "bf16":
             # the compute mode in which north_star's 1e-3 bound holds (exact-f32 MFMA everywhere, bf16 only where the reference casts):
             # one warm-up + two timed steps (the faster is reported), after the timed region; bf16 (timed above) sits at the reference's own autocast distance
             def fp32_modes():
@@ -487,14 +561,14 @@ def main() -> None:
                                   "HIP / reference ratio max 1.16, median 0.82 (tests/test_hip_parity.py::test_unet_bf16_vs_reference_autocast); both fp32 modes are "
                                   "held to 1e-3 at full size by tests/test_full_size.py (forward of two samples and all 1,239 gradients of one sample, each with "
                                   "set_f32_matmul('exact') and ('x3')): fp32x3_mode = split-bf16 GEMMs, fp32_mode = f32 MFMA")
-        if world == 1 and not args.no_sampler and not args.lora and full:
+        if more and not args.no_sampler and not args.lora and full:
             print("[bench] secondary: DDIM sample at config 4's size ...", file=sys.stderr, flush=True)
             guarded("secondary", lambda: sampler_secondary(model, device))
-        if world == 1 and not args.no_cpu_baseline and not args.lora:
+        if more and not args.no_cpu_baseline and not args.lora:
             guarded("cpu_baseline", lambda: cpu_baseline(model, args.length, [args.cpu_threads] if args.cpu_threads else host_thread_counts()))
             if "value" in out["cpu_baseline"]:
                 out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
-        if world == 1 and not args.no_config5 and not args.lora and full:
+        if more and not args.no_config5 and not args.lora and full:
             print("[bench] config 5: DoRA r=16 steps at the per-GPU shard B=64 ...", file=sys.stderr, flush=True)
             del trainer
             guarded("config5", lambda: config5_secondary(model, rank, device))      # LAST: wraps the model's layers in place

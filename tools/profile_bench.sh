@@ -4,6 +4,7 @@
 # (cd /tmp + TMPDIR=/tmp as the pool's guide asks; the program after `--` is python itself, no wrapper in between.)
 set -e
 TAG=$1; shift
+set -- --full "$@"                 # the saved bench line carries the HIP-event roofline of the timed steps
 ROOT=$(pwd)
 mkdir -p "$ROOT/gpurun_out/prof_$TAG"
 cd /tmp && export TMPDIR=/tmp
