@@ -230,6 +230,43 @@ def test_config4_ddim_step_vs_oracle(full):
         model.sampling_timesteps = 35
 
 
+def test_config4_sampler_is_independent_of_uninitialised_memory(full):
+    """Round-4 incident (a) replayed in its order with every allocation poisoned: a config-4 fp32-mode call (it leaves the caches holding fp32
+    operands), then 3-step bf16 eager samples with every torch.empty / torch.empty_like of the package NaN-filled (0xFF) and ~3.4e38-filled (0x7F)
+    -- each on freshly allocated workspaces and operand packs, the first bf16 call's situation --, then a plain eager sample and a hipGraph replay.
+    A kernel that read a region before its producer wrote it would make the two poisoned samples differ (or not be finite); all four must be equal."""
+    import osufusion_amd as oa
+    from tests.memguard import guard
+    model = full[0]
+    Bc, Lc, S, cs = 16, 8192, 50, 2.0
+    g = torch.Generator().manual_seed(404)
+    a = (torch.randn(Bc, 96, Lc, generator=g) * 3 - 10).cuda()
+    c = (torch.rand(Bc, 5, generator=g) * 2 - 1).cuda()
+    x0 = torch.randn(Bc, 6, Lc, generator=g).cuda()
+    model.sampling_timesteps = S
+    try:
+        model.stop_after = 1
+        with oa.forced_compute_dtype(torch.float32):
+            model.sample(a, c, x0, cond_scale=cs)
+        model.stop_after = 3
+        outs = []
+        for byte in (0xFF, 0x7F):
+            with guard(byte, canaries=False) as gd, oa.forced_compute_dtype(torch.bfloat16):
+                outs.append(model.sample(a, c, x0, cond_scale=cs))
+            assert gd.allocations > 1000, gd.allocations                  # every pack, workspace and activation of the sample came through it
+        with oa.forced_compute_dtype(torch.bfloat16):
+            outs.append(model.sample(a, c, x0, cond_scale=cs))
+            model.use_hip_graph = True
+            outs.append(model.sample(a, c, x0, cond_scale=cs))
+        assert torch.isfinite(outs[0]).all()
+        for name, o in zip(("0x7F", "unguarded eager", "hipGraph replay"), outs[1:]):
+            assert torch.equal(outs[0], o), (name, ((o - outs[0]).norm() / outs[0].norm()).item())
+    finally:
+        model.stop_after = None
+        model.use_hip_graph = False
+        model.sampling_timesteps = 35
+
+
 def test_full_size_fresh_dora_adapters_leave_the_denoiser_unchanged(full):
     """Idempotence at full size (runs last: it wraps the shared model in place).  peft zero-inits lora_B and DoRA starts its
     magnitude at ||W||, so g = 1 and the adapted UNet must reproduce the base UNet up to the rounding of g; one adapted
