@@ -2041,6 +2041,36 @@ static int fill_bwd_args(AttnArgs& a, const void* q, long ldq, const void* k, lo
   return OSUF_OK;
 }
 
+// The backward of osuf_mqa_fwd_masked (Attend with attn_mask): one K/V head, gradients of the ROTATED q / k (x scale) and of v, every head dim
+// (64 included) on the generic kernel pair with the bias restarting S.  dbias (may be NULL): dense fp32 [B][H][N][N], dL/d(bias).
+extern "C" int osuf_mqa_bwd_masked(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
+                                   const float* lse2, const float* delta, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k,
+                                   void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H, int N, int head_dim, float scale,
+                                   int out_dtype, float* dbias, hipStream_t stream) {
+  AttnArgs a;
+  int rc = fill_bwd_args(a, q, ldq, k, ldk, v, ldv, dout, lddo, lse2, delta, B, H, N, head_dim, scale);
+  if (rc) return rc;
+  if (!mask || !lse2 || !delta || scale == 0.f || lddq % 8 || lddk % 8 || !al16(dq) || !al16(dk) || !al16(dv) ||
+      (out_dtype != OSUF_DT_F32 && out_dtype != OSUF_DT_BF16) || (dbias && !al16(dbias)))
+    return OSUF_EINVAL;
+  a.mask = (const bf16_t*)mask; a.mask_b = mask_b; a.mask_h = mask_h; a.mask_q = mask_q; a.mask_k = mask_k;
+  a.dq = dq; a.lddq = lddq; a.dk = dk; a.dv = dv; a.lddk = lddk; a.g_bf16 = out_dtype == OSUF_DT_BF16;
+  const int nvb = ((N + 31) / 32) * H;
+  const dim3 grid((nvb + 3) / 4, B), ggrid(((N + 127) / 128) * B);
+  const int dp = head_dim == D ? 64 : gen_dp(head_dim);
+  if (dp == 32) {
+    hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<32, true>), grid, dim3(256), 2 * 64 * 64, stream, a, head_dim);
+    hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<32, true>), ggrid, dim3(256), 2 * 32 * 64 + 256, stream, a, head_dim, dbias);
+  } else if (dp == 64) {
+    hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<64, true>), grid, dim3(256), 2 * 64 * 128, stream, a, head_dim);
+    hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<64, true>), ggrid, dim3(256), 2 * 32 * 128 + 256, stream, a, head_dim, dbias);
+  } else {
+    hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<128, true>), grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
+    hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<128, true>), ggrid, dim3(256), 2 * 32 * 256 + 256, stream, a, head_dim, dbias);
+  }
+  return osuf_launch_status();
+}
+
 // delta[b][h][n] = sum_d dO * O   (o: bf16 or f32 storage of the forward output)
 extern "C" int osuf_attn_delta(const void* dout, long lddo, const void* o, long ldo, int o_dtype, float* delta, int B, int H, int N,
                                int head_dim, hipStream_t stream) {
@@ -2124,8 +2154,8 @@ extern "C" int osuf_mqa_bwd_dkv(const void* q, long ldq, const void* k, long ldk
   if (head_dim != D) {                                            // generic head dims: gradients of the rotated k and of v, unsplit
     if (rope_cos) return OSUF_EUNSUPPORTED;
     const dim3 ggrid(((N + 127) / 128) * B);
-    if (gen_dp(head_dim) == 32) hipLaunchKernelGGL(mqa_gen_bwd_dkv_kernel<32>, ggrid, dim3(256), 2 * 32 * 64 + 256, stream, a, head_dim);
-    else hipLaunchKernelGGL(mqa_gen_bwd_dkv_kernel<128>, ggrid, dim3(256), 2 * 32 * 256 + 256, stream, a, head_dim);
+    if (gen_dp(head_dim) == 32) hipLaunchKernelGGL(mqa_gen_bwd_dkv_kernel<32>, ggrid, dim3(256), 2 * 32 * 64 + 256, stream, a, head_dim, (float*)nullptr);
+    else hipLaunchKernelGGL(mqa_gen_bwd_dkv_kernel<128>, ggrid, dim3(256), 2 * 32 * 256 + 256, stream, a, head_dim, (float*)nullptr);
     return osuf_launch_status();
   }
   const int b8 = (B + 7) / 8 * 8;

@@ -174,7 +174,8 @@ __global__ __launch_bounds__(256) void mqa_gen_fwd_kernel(AttnArgs a, int hd) {
 }
 
 // ---- backward, dQ (query-stationary): dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q]; gradient of the ROTATED q (x scale), no RoPE transpose
-template <int DP>
+// MASKED: the forward's additive bias starts S again (same units, same clamped indices), so P is recomputed exactly as lse2 was formed
+template <int DP, bool MASKED = false>
 __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd) {
   using T = GenTile<DP>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -205,10 +206,26 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
     T::fill(smem + TILE, a.v + (long)b * a.N * a.ldv, a.ldv, 64, j * 64, a.N, hd, tid, 256);
     __syncthreads();
     f32x16 s[2], dp[2];
+    if constexpr (MASKED) {                                            // as in the forward: bias / scale, rows / keys past N clamped
+      const bf16_t* mrow = a.mask + (long)b * a.mask_b + (long)h * a.mask_h + (long)(qok ? qrow : 0) * a.mask_q;
+      const float inv_scale = 1.f / a.scale;
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          s[kt][r] = bf16_to_f32(mrow[(long)(key < a.N ? key : a.N - 1) * a.mask_k]) * inv_scale;
+        }
+    } else {
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
+    }
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { s[kt][r] = 0.f; dp[kt][r] = 0.f; }
+      for (int r = 0; r < 16; ++r) dp[kt][r] = 0.f;
 #pragma unroll
       for (int ks = 0; ks < T::KS; ++ks) {
         s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T::row_frag(smem, lane, ks, kt), qf[ks], s[kt], 0, 0, 0);
@@ -219,7 +236,11 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float p = fast_exp2(fmaf(s[kt][r], c, -L2));            // keys past N: zero K rows -> their dS meets zero K rows below
+        float p = fast_exp2(fmaf(s[kt][r], c, -L2));                  // keys past N: zero K rows -> their dS meets zero K rows below
+        if constexpr (MASKED) {                                        // (a clamped bias could make p large there: drop it outright)
+          const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          p = key < a.N ? p : 0.f;
+        }
         s[kt][r] = p * (dp[kt][r] - dl);
       }
 #pragma unroll
@@ -234,8 +255,11 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
 }
 
 // ---- backward, dK / dV (key-stationary): 4 waves = 128 keys sweep every (head, 32-query block) pair; gradients of the ROTATED k (x scale) and v
-template <int DP>
-__global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd) {
+// MASKED: the bias starts S as in the forward; here the accumulator rows are queries and the lanes keys, so the 32 lanes of a row read 32
+// consecutive keys of mask[b][h][q][*].  dbias != null (MASKED only): dS = P (dP - delta) -- dL/dbias, the bias being added to the scaled
+// scores -- is stored to the dense fp32 [B][H][N][N] dbias for every valid (query, key); padded rows and keys are not written.
+template <int DP, bool MASKED = false>
+__global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd, float* dbias) {
   using T = GenTile<DP>;
   extern __shared__ __attribute__((aligned(16))) char smem[];        // Q image 32 x RB | dO image 32 x RB | lse 128 | delta 128
   constexpr int TILE = 32 * T::RB;
@@ -267,8 +291,20 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd
       }
       __syncthreads();
       f32x16 s, dp;
+      if constexpr (MASKED) {
+        const bf16_t* mcol = a.mask + (long)b * a.mask_b + (long)h * a.mask_h + (long)(kok ? key : a.N - 1) * a.mask_k;
+        const float inv_scale = 1.f / a.scale;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+        for (int r = 0; r < 16; ++r) {
+          const int qr = pb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          s[r] = bf16_to_f32(mcol[(long)(qr < a.N ? qr : a.N - 1) * a.mask_q]) * inv_scale;
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dp[r] = 0.f;
 #pragma unroll
       for (int ks = 0; ks < T::KS; ++ks) {
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T::row_frag(smem, lane, ks, 0), kf[ks], s, 0, 0, 0);
@@ -281,6 +317,16 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd
         const float p = fast_exp2(fmaf(s[r], c, -ls[qi]));
         s[r] = p;
         ds[r] = p * (dp[r] - ls[32 + qi]);
+      }
+      if constexpr (MASKED) {
+        if (dbias && kok) {                                            // lanes = 32 consecutive keys of one query row: 128-byte rows
+          float* drow = dbias + (((long)b * a.H + h) * a.N + pb * 32) * a.N + key;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int qi = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (pb * 32 + qi < a.N) drow[(long)qi * a.N] = ds[r];
+          }
+        }
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
