@@ -8,8 +8,10 @@
  * Conventions
  *   - plain device pointers + sizes + hipStream_t; no allocation, no host sync, graph-capturable.  Nothing is kept between
  *     calls except the one-time hipFuncSetAttribute registration of kernels that need > 64 KiB of LDS.  Kernel variants are
- *     chosen per call (`variant` arguments); the GEMM launchers additionally honour the documented A/B environment switches
- *     OSUF_GEMM_* / OSUF_TN_* (read on every call, never cached) -- measurement aids, not configuration;
+ *     chosen per call (`variant` arguments).  A few environment switches force one path so that tests can compare it bit for
+ *     bit with another and A/B runs can time it: OSUF_GEMM_BIG_MIN_TILES, OSUF_GEMM_NO8P, OSUF_GEMM_NOHALO and
+ *     OSUF_WGRAD_F32_PARTIALS in the GEMM launchers, OSUF_ATTN_FWD_NOWHOLE and OSUF_ATTN_FWD_NOQSK in the attention forward.
+ *     They are test and A/B aids, not configuration, and are read on every call (never cached);
  *   - return 0 on success, <0 for an argument error (-1 invalid, -2 unsupported), >0 = hipError_t of the launch;
  *   - activations are channels-last rows [B*L][C] ("rows"), C contiguous, row stride `ld*` in ELEMENTS;
  *   - dtype: 0 = fp32 storage (exact-f32 MFMA), 1 = bf16 storage (bf16 MFMA, fp32 accumulate);

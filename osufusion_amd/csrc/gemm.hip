@@ -7,9 +7,10 @@
 // A rows are shifted by the tap; both MFMA operands are K-contiguous (weights are pre-packed [tap][N][K]).
 // bf16 storage -> v_mfma_f32_32x32x16_bf16; f32 storage -> v_mfma_f32_32x32x2_f32 (exact f32 fmaf chain).
 // Block tile 128x128, 4 waves (2x2), wave tile 64x64 = 2x2 MFMA tiles; K-step = 128 bytes of K per row.
-// Global -> registers -> LDS double buffering (one barrier per K-step), XOR-swizzled 16-B chunks so the
+// Global -> LDS double buffering (one barrier per K-step), XOR-swizzled 16-B chunks so the
 // ds_read_b128 fragment reads are conflict-free; epilogue goes through LDS so HBM stores are full rows.
 #include "common.hpp"
+#include <optional>
 #include <stdlib.h>
 
 struct RowMap {
@@ -192,123 +193,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[2
   else gemm_epilogue_impl<T, true>(g, acc, smem, m0, n0, tid, lane, wr, wc);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int BK = Mma<T>::BK;
-  constexpr int EPC = ElemTraits<T>::kPer16B;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int tiles_n = (g.N + kTile - 1) / kTile;
-  const int m0 = (blockIdx.x / tiles_n) * kTile, n0 = (blockIdx.x % tiles_n) * kTile;
-  const T* A = reinterpret_cast<const T*>(g.A);
-  const T* W = reinterpret_cast<const T*>(g.W);
-
-  // staging assignment: chunk column c (16 B of K), rows r0 + 32*i
-  const int c = tid & 7, r0 = tid >> 3;
-  int a_base[4], a_pos[4];
-  bool b_ok[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int m = m0 + r0 + 32 * i;
-    if (m < g.M) { int b = m / g.rm.Lout; a_base[i] = b * g.rm.Lin; a_pos[i] = m - b * g.rm.Lout; }
-    else { a_base[i] = 0; a_pos[i] = -1; }
-    b_ok[i] = (n0 + r0 + 32 * i) < g.N;
-  }
-  const int ksteps = (g.K + BK - 1) / BK;
-  const int nsteps = g.taps * ksteps;
-
-  // Two statically named register sets: the tile of step s+2 is issued at the top of step s and written to LDS at the
-  // bottom of step s+1, so every global load has ~2 K-steps (>= 1000 MFMA cycles at 2 waves/SIMD) to land.
-  u32x4 ra0[4], rb0[4], ra1[4], rb1[4];
-  auto load_regs = [&](int step, u32x4 (&ra)[4], u32x4 (&rb)[4]) {
-    const int t = step / ksteps, kb = step - t * ksteps;
-    const int k = kb * BK + c * EPC;
-    const bool kok = k < g.K;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      u32x4 z = {0u, 0u, 0u, 0u};
-      ra[i] = z; rb[i] = z;
-      if (kok && a_pos[i] >= 0) {
-        int s = map_row(g.rm, a_pos[i], t);
-        if (s >= 0) ra[i] = *reinterpret_cast<const u32x4*>(A + (long)(a_base[i] + s) * g.lda + k);
-      }
-      if (kok && b_ok[i])
-        rb[i] = *reinterpret_cast<const u32x4*>(W + (long)t * g.tapstride + (long)(n0 + r0 + 32 * i) * g.ldw + k);
-    }
-  };
-  auto store_lds = [&](int buf, const u32x4 (&ra)[4], const u32x4 (&rb)[4]) {
-    char* sa = smem + buf * kStageBytes;
-    char* sb = sa + kTile * 128;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int off = swz_off(r0 + 32 * i, c);
-      *reinterpret_cast<u32x4*>(sa + off) = ra[i];
-      *reinterpret_cast<u32x4*>(sb + off) = rb[i];
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int lr = lane & 31, lh = lane >> 5;
-  auto compute = [&](int buf) {
-    const char* sa = smem + buf * kStageBytes;
-    const char* sb = sa + kTile * 128;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 fa[2], fb[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        fa[i] = *reinterpret_cast<const u32x4*>(sa + swz_off(wr * 64 + i * 32 + lr, 2 * ks + lh));
-        fb[i] = *reinterpret_cast<const u32x4*>(sb + swz_off(wc * 64 + i * 32 + lr, 2 * ks + lh));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if constexpr (sizeof(T) == 2) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i]),
-                                                                 __builtin_bit_cast(bf16x8, fb[j]), acc[i][j], 0, 0, 0);
-          } else {
-            f32x4 va = __builtin_bit_cast(f32x4, fa[i]), vb = __builtin_bit_cast(f32x4, fb[j]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[e], vb[e], acc[i][j], 0, 0, 0);
-          }
-        }
-    }
-  };
-
-  // prologue: step 0 -> LDS[0]; step 1 in flight in set 1
-  load_regs(0, ra0, rb0);
-  if (nsteps > 1) load_regs(1, ra1, rb1);
-  store_lds(0, ra0, rb0);
-  __syncthreads();
-  for (int step = 0; step < nsteps; step += 2) {
-    // even step: compute LDS[0]; set 1 (step+1) -> LDS[1]; issue step+2 into set 0
-    if (step + 2 < nsteps) load_regs(step + 2, ra0, rb0);
-    compute(0);
-    if (step + 1 < nsteps) store_lds(1, ra1, rb1);
-    __syncthreads();
-    if (step + 1 >= nsteps) break;
-    // odd step: compute LDS[1]; set 0 (step+2) -> LDS[0]; issue step+3 into set 1
-    if (step + 3 < nsteps) load_regs(step + 3, ra1, rb1);
-    compute(1);
-    if (step + 2 < nsteps) store_lds(0, ra0, rb0);
-    __syncthreads();
-  }
-
-  gemm_epilogue<T>(g, acc, smem, m0, n0, tid, lane, wr, wc);
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// LDS-DMA variant of gemm_nt: tiles go HBM/L2 -> LDS by global_load_lds_dwordx4 (no VGPR staging, no ds_write: the
-// ds_write_b128 path moves only ~79 B/clk/CU and was the bottleneck of the register-staged loop).  One wave-instruction
+// The 128 x 128 gemm_nt: tiles go HBM/L2 -> LDS by global_load_lds_dwordx4 (no VGPR staging, no ds_write: the
+// ds_write_b128 path moves only ~79 B/clk/CU and was the bottleneck of the removed register-staged loop).  One wave-instruction
 // fills 1 KiB = 8 tile rows; the LDS image is lane-linear, so the XOR swizzle is applied to the per-lane SOURCE chunk
 // (cdna_hip_programming.md rule 21) and undone by swz_off() on the read side.  Rows outside the tensor (conv padding,
 // M / N / K tails) read from a 64-byte device zero page.
@@ -622,11 +509,9 @@ __device__ __forceinline__ void gemm_big_epilogue(const GemmArgs& g, f32x16 (&ac
   else gemm_big_epilogue_impl<T, 3>(g, acc, smem, m0, n0, tid, lane, wave, wr, wc);
 }
 
-// DBG (bottleneck triage builds, selected by OSUF_GEMM_DBG; results are garbage unless 0): 1 = no MFMA, 2 = no LDS fragment
-// reads, 3 = no global->LDS DMA, 4 = DMA only, 5 = DMA only from one hot 1-KiB region (memory-side vs LDS-side cost).
 // SPLIT (T = float, OSUF_DT_F32X3): fp32 stages (32 k per row), every fragment split in registers into bf16 hi + lo, three bf16
 // MFMAs per product (mfma_x3) -- two 16-deep k-steps per stage, 48 MFMAs per wave and stage against 32 of the bf16 kernel.
-template <typename T, int DBG = 0, bool SPLIT = false>
+template <typename T, bool SPLIT = false>
 __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BK = Mma<T>::BK;
@@ -691,7 +576,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(GemmArgs g) {
     const char* qa = pa[i];
     const char* qb = pb[i];
     if (ktail && ikb == ksteps - 1 && ikb * BK + koff[i] >= g.K) { qa = zero; qb = zero; }
-    if (DBG == 5) { qa = reinterpret_cast<const char*>(A) + lane * 16; qb = reinterpret_cast<const char*>(W) + lane * 16; }
     __builtin_amdgcn_global_load_lds((gas_ptr)qa, (las_ptr)(sa + i * 1024), 16, 0, 0);
     __builtin_amdgcn_global_load_lds((gas_ptr)qb, (las_ptr)(sb + i * 1024), 16, 0, 0);
     pa[i] += ia[i];
@@ -718,16 +602,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(GemmArgs g) {
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   const int lr = lane & 31, lh = lane >> 5;
-  if (DBG != 3) issue(0);
+  issue(0);
   __syncthreads();
-  u32x4 dfa[4], dfb[2];
-  if (DBG == 2) {
-    for (int i = 0; i < 4; ++i) dfa[i] = u32x4{(uint32_t)lane, 1u, 2u, 3u};
-    for (int j = 0; j < 2; ++j) dfb[j] = u32x4{(uint32_t)lane, 5u, 6u, 7u};
-  }
   for (int step = 0; step < nsteps; ++step) {
     const int buf = step & 1;
-    const bool more = DBG != 3 && step + 1 < nsteps;
+    const bool more = step + 1 < nsteps;
     const char* sa = smem + buf * kBigStage;
     const char* sb = sa + kBig * 128;
     if constexpr (SPLIT) {
@@ -755,25 +634,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(GemmArgs g) {
     for (int ks = 0; ks < 4; ++ks) {
       u32x4 fa[4], fb[2];
       if (more) issue_part(buf ^ 1, ks);
-      if (DBG >= 4) continue;
-      if (DBG == 2) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { asm volatile("" : "+v"(dfa[i])); fa[i] = dfa[i]; }
+      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const u32x4*>(sa + swz_off(wr * 128 + i * 32 + lr, 2 * ks + lh));
 #pragma unroll
-        for (int j = 0; j < 2; ++j) { asm volatile("" : "+v"(dfb[j])); fb[j] = dfb[j]; }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const u32x4*>(sa + swz_off(wr * 128 + i * 32 + lr, 2 * ks + lh));
-#pragma unroll
-        for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const u32x4*>(sb + swz_off(wc * 64 + j * 32 + lr, 2 * ks + lh));
-      }
-      if (DBG == 1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(fa[i]));
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(fb[j]));
-        continue;
-      }
+      for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const u32x4*>(sb + swz_off(wc * 64 + j * 32 + lr, 2 * ks + lh));
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -820,13 +684,10 @@ template <int OFF> __device__ __forceinline__ void lds_read_b128(u32x4& d, uint3
 }
 template <int V> struct IntC { static constexpr int value = V; };
 
-// DBG (timing-only triage builds, OSUF_GEMM_DBG with OSUF_GEMM_8P; results are garbage unless 0): 1 = no MFMA, 2 = no fragment reads,
-// 3 = no DMA, 4 = DMA only, 5 = DMA only with B from one hot KiB (A's feed alone), 6 = DMA only with A from one hot KiB (B's feed alone)
 __device__ uint4 g_zero_row[1024];                           // 16 KiB of zeros: the source "row" of padded / out-of-range A rows (K <= 8192 bf16)
 static constexpr int kP8Tbl = 2 * kBigStage + 2112;          // LDS: per-tap source rows of the tile's 256 A rows, [taps][256] ints, behind the stat slots
 static constexpr int kP8MaxTaps = 16;
 
-template <int DBG = 0>
 __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef bf16_t T;
@@ -901,15 +762,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
   auto stage = [&](auto hc, auto bufc) {
     constexpr int H = decltype(hc)::value, BUF = decltype(bufc)::value, S = H >> 1;
     constexpr bool IS_A = (H & 1) != 0;
-    if (DBG != 3) {
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const char* q = IS_A ? pa[S][j] : pb[S][j];
-        if ((DBG == 5 && !IS_A) || (DBG == 6 && IS_A)) q = (IS_A ? A : reinterpret_cast<const char*>(W)) + lane * 16;   // that operand from one hot KiB
-        char* dst = smem + BUF * 32768 + (IS_A ? aw + S * 8192 : bw + S * 4096) + j * 1024;
-        __builtin_amdgcn_global_load_lds((gas_ptr)q, (las_ptr)dst, 16, 0, 0);
-        if (IS_A) pa[S][j] += 128; else pb[S][j] += 128;
-      }
+    for (int j = 0; j < 2; ++j) {
+      const char* q = IS_A ? pa[S][j] : pb[S][j];
+      char* dst = smem + BUF * 32768 + (IS_A ? aw + S * 8192 : bw + S * 4096) + j * 1024;
+      __builtin_amdgcn_global_load_lds((gas_ptr)q, (las_ptr)dst, 16, 0, 0);
+      if (IS_A) pa[S][j] += 128; else pb[S][j] += 128;
     }
   };
   // behind the last half-tile (A1) of a K-tile: on to the next K-tile, and at the end of a tap's K range to the next tap
@@ -944,66 +802,53 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
     kb[ks] = lds0 + 65536u + (uint32_t)((wc * 64 + lr) * 128) + ch;
   }
   u32x4 fa[2][4], fb0[4], fb1[4];
-  if (DBG == 2) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      fa[0][ks] = u32x4{(uint32_t)lane, 1u, 2u, 3u}; fa[1][ks] = fa[0][ks]; fb0[ks] = u32x4{(uint32_t)lane, 5u, 6u, 7u}; fb1[ks] = fb0[ks];
-    }
-  }
 #define P8_WAIT_A(cnt)                                                                                                        \
   asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fa[0][3]), "+v"(fa[1][0]), \
                "+v"(fa[1][1]), "+v"(fa[1][2]), "+v"(fa[1][3]));
 #define P8_WAIT_B(cnt, fb) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
 #define P8_MFMA(i0, j, fbv)                                                                                                   \
-  if (DBG != 1 && DBG < 4) {                                                                                                  \
+  {                                                                                                                           \
     __builtin_amdgcn_s_setprio(1);                                                                                            \
     _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                                        \
       acc[i0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[0][ks]), __builtin_bit_cast(bf16x8, fbv[ks]), acc[i0][j], 0, 0, 0); \
       acc[i0 + 1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[1][ks]), __builtin_bit_cast(bf16x8, fbv[ks]), acc[i0 + 1][j], 0, 0, 0); \
     }                                                                                                                         \
     __builtin_amdgcn_s_setprio(0);                                                                                            \
-  } else {                                                                                                                    \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) { asm volatile("" ::"v"(fa[0][ks]), "v"(fa[1][ks]), "v"(fbv[ks])); }         \
   }
-  constexpr bool RD = DBG != 2 && DBG < 4;
   // one K-tile (four phases) out of buffer BUF; t = its index
   auto tile = [&](auto bufc, int t) {
     constexpr int BUF = decltype(bufc)::value, O = BUF * 32768;
     // ---- P1: B0, A0 -> acc[0..1][0]; stage A1(t + 1)
-    if (RD) {
-      lds_read_b128<O>(fb0[0], kb[0]); lds_read_b128<O>(fb0[1], kb[1]); lds_read_b128<O>(fb0[2], kb[2]); lds_read_b128<O>(fb0[3], kb[3]);
-      __builtin_amdgcn_sched_barrier(0);
-      lds_read_b128<O>(fa[0][0], ka[0]); lds_read_b128<O>(fa[0][1], ka[1]); lds_read_b128<O>(fa[0][2], ka[2]); lds_read_b128<O>(fa[0][3], ka[3]);
-      lds_read_b128<O + 4096>(fa[1][0], ka[0]); lds_read_b128<O + 4096>(fa[1][1], ka[1]); lds_read_b128<O + 4096>(fa[1][2], ka[2]);
-      lds_read_b128<O + 4096>(fa[1][3], ka[3]);
-    }
+    lds_read_b128<O>(fb0[0], kb[0]); lds_read_b128<O>(fb0[1], kb[1]); lds_read_b128<O>(fb0[2], kb[2]); lds_read_b128<O>(fb0[3], kb[3]);
+    __builtin_amdgcn_sched_barrier(0);
+    lds_read_b128<O>(fa[0][0], ka[0]); lds_read_b128<O>(fa[0][1], ka[1]); lds_read_b128<O>(fa[0][2], ka[2]); lds_read_b128<O>(fa[0][3], ka[3]);
+    lds_read_b128<O + 4096>(fa[1][0], ka[0]); lds_read_b128<O + 4096>(fa[1][1], ka[1]); lds_read_b128<O + 4096>(fa[1][2], ka[2]);
+    lds_read_b128<O + 4096>(fa[1][3], ka[3]);
     if (t + 1 < n) { stage(IntC<3>{}, IntC<BUF ^ 1>{}); next_ktile(); }
-    if (RD) { P8_WAIT_B(8, fb0) }                               // B0's reads are done before anyone passes the barrier: P2 re-stages B0's slot
+    P8_WAIT_B(8, fb0)                                           // B0's reads are done before anyone passes the barrier: P2 re-stages B0's slot
     __builtin_amdgcn_s_barrier();
-    if (RD) { P8_WAIT_A(0) }
+    P8_WAIT_A(0)
     __builtin_amdgcn_sched_barrier(0);
     P8_MFMA(0, 0, fb0)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     // ---- P2: B1 -> acc[0..1][1]; stage B0(t + 2)
-    if (RD) { lds_read_b128<O + 4096>(fb1[0], kb[0]); lds_read_b128<O + 4096>(fb1[1], kb[1]); lds_read_b128<O + 4096>(fb1[2], kb[2]); lds_read_b128<O + 4096>(fb1[3], kb[3]); }
+    lds_read_b128<O + 4096>(fb1[0], kb[0]); lds_read_b128<O + 4096>(fb1[1], kb[1]); lds_read_b128<O + 4096>(fb1[2], kb[2]); lds_read_b128<O + 4096>(fb1[3], kb[3]);
     if (t + 2 < n) stage(IntC<0>{}, IntC<BUF>{});
     __builtin_amdgcn_s_barrier();
-    if (RD) { P8_WAIT_B(0, fb1) }
+    P8_WAIT_B(0, fb1)
     __builtin_amdgcn_sched_barrier(0);
     P8_MFMA(0, 1, fb1)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     // ---- P3: A1 -> acc[2..3][1]; stage A0(t + 2)
-    if (RD) {
-      lds_read_b128<O + 8192>(fa[0][0], ka[0]); lds_read_b128<O + 8192>(fa[0][1], ka[1]); lds_read_b128<O + 8192>(fa[0][2], ka[2]);
-      lds_read_b128<O + 8192>(fa[0][3], ka[3]);
-      lds_read_b128<O + 12288>(fa[1][0], ka[0]); lds_read_b128<O + 12288>(fa[1][1], ka[1]); lds_read_b128<O + 12288>(fa[1][2], ka[2]);
-      lds_read_b128<O + 12288>(fa[1][3], ka[3]);
-    }
+    lds_read_b128<O + 8192>(fa[0][0], ka[0]); lds_read_b128<O + 8192>(fa[0][1], ka[1]); lds_read_b128<O + 8192>(fa[0][2], ka[2]);
+    lds_read_b128<O + 8192>(fa[0][3], ka[3]);
+    lds_read_b128<O + 12288>(fa[1][0], ka[0]); lds_read_b128<O + 12288>(fa[1][1], ka[1]); lds_read_b128<O + 12288>(fa[1][2], ka[2]);
+    lds_read_b128<O + 12288>(fa[1][3], ka[3]);
     if (t + 2 < n) stage(IntC<1>{}, IntC<BUF>{});
     __builtin_amdgcn_s_barrier();
-    if (RD) { P8_WAIT_A(0) }
+    P8_WAIT_A(0)
     __builtin_amdgcn_sched_barrier(0);
     P8_MFMA(2, 1, fb1)
     __builtin_amdgcn_sched_barrier(0);
@@ -1206,7 +1051,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_halo3_kernel(GemmArgs g) {
 // ---------------------------------------------------------------------------------------------------------
 static constexpr int kH8B = 2 * kPanelBytes;                 // 67,584: B ring behind the two panels
 
-template <int DBG = 0>
 __global__ __launch_bounds__(512, 2) void gemm_nt_big8_halo3_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef bf16_t T;
@@ -1254,11 +1098,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_halo3_kernel(GemmArgs g) 
   int st_tap = 0;                                            // tap of the B tile being staged
   auto stage_b = [&](auto sc, auto bufc) {                    // half-tile S of the B tile being staged, into buffer BUF; behind B1: on to the next B tile
     constexpr int S = decltype(sc)::value, BUF = decltype(bufc)::value;
-    if (DBG != 3) {
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
-        __builtin_amdgcn_global_load_lds((gas_ptr)pb[S][j], (las_ptr)(smem + bw + BUF * 32768 + S * 4096 + j * 1024), 16, 0, 0);
-    }
+    for (int j = 0; j < 2; ++j)
+      __builtin_amdgcn_global_load_lds((gas_ptr)pb[S][j], (las_ptr)(smem + bw + BUF * 32768 + S * 4096 + j * 1024), 16, 0, 0);
     if (S == 1) {
       const long d = st_tap < 2 ? tapb : next_k;
       st_tap = st_tap < 2 ? st_tap + 1 : 0;
@@ -1271,7 +1113,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_halo3_kernel(GemmArgs g) 
   auto stage_a = [&](auto ic, auto panelc) {                  // piece I of this wave into panel PANEL; advances to the next K-step
     constexpr int I = decltype(ic)::value, PANEL = decltype(panelc)::value;
     const int gi = I < 4 ? wave * 4 + I : 32;
-    if (DBG != 3) __builtin_amdgcn_global_load_lds((gas_ptr)pa[I], (las_ptr)(smem + PANEL * kPanelBytes + gi * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gas_ptr)pa[I], (las_ptr)(smem + PANEL * kPanelBytes + gi * 1024), 16, 0, 0);
     pa[I] += 128;
   };
 
@@ -1293,15 +1135,13 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_halo3_kernel(GemmArgs g) 
                "+v"(fa[1][1]), "+v"(fa[1][2]), "+v"(fa[1][3]));
 #define H8_WAIT_B(cnt, fb) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
 #define H8_MFMA(i0, j, fbv)                                                                                                   \
-  if (DBG != 1) {                                                                                                             \
+  {                                                                                                                           \
     __builtin_amdgcn_s_setprio(1);                                                                                            \
     _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                                        \
       acc[i0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[0][ks]), __builtin_bit_cast(bf16x8, fbv[ks]), acc[i0][j], 0, 0, 0); \
       acc[i0 + 1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[1][ks]), __builtin_bit_cast(bf16x8, fbv[ks]), acc[i0 + 1][j], 0, 0, 0); \
     }                                                                                                                         \
     __builtin_amdgcn_s_setprio(0);                                                                                            \
-  } else {                                                                                                                    \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) { asm volatile("" ::"v"(fa[0][ks]), "v"(fa[1][ks]), "v"(fbv[ks])); }         \
   }
   // one K-tile = (K-step in panel PANEL, tap TAP), B tile in buffer BUF; t = its index, more_k: another K-step follows this one
   auto tile = [&](auto panelc, auto bufc, auto tapc, int t, bool more_k) {
@@ -1529,7 +1369,6 @@ struct WgradArgs {
   RowMap rm;
   int rows_per_split;
   float* dbias;                    // optional: column sums of dY (the bias gradient) += , from the dY fragments the kernel already holds
-  int xcd_chunks;                  // 256x256 wgrad kernels: unit list dealt to the XCDs in eighths (1) or round-robin (0: A/B switch OSUF_TN_RR)
 };
 
 // bf16 tile: [64 rows][128 cols] (256 B/row), byte-in-row ^= (row&3)<<6 -> ds_read_b64_tr_b16 conflict-free
@@ -1793,13 +1632,13 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_kernel(WgradArgs g) {
   const int tiles_n2 = (g.N2 + kBig - 1) / kBig;
   const int tiles_n1 = (g.N1 + kBig - 1) / kBig;
   // XCD-aware order (speed only): the taps of one (split, tile) unit re-read identical dY / X bytes; give them ids 8 apart
-  // so they share one XCD's L2 and run back to back, and deal the units themselves round-robin over the 8 XCDs.
+  // so they share one XCD's L2 and run back to back, and deal the units themselves to the 8 XCDs in eighths.
   const int ntile = tiles_n1 * tiles_n2;
   const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;
   // (units are (split, tile) pairs, split-major: XCD x takes the x-th eighth of the list, so the tiles of one m-split -- which re-read the
   //  same dY / X rows -- and their taps run back to back on one XCD.  The first form, unit = (qid / taps) * 8 + xcd, dealt a split's tiles
   //  to eight different L2s: PMC FETCH_SIZE of these launches summed to 4.5 TB/s HBM-side, twice the algorithmic bytes.)
-  const int unit = g.xcd_chunks ? xcd * (((int)gridDim.x >> 3) / g.taps) + qid / g.taps : (qid / g.taps) * 8 + xcd;
+  const int unit = xcd * (((int)gridDim.x >> 3) / g.taps) + qid / g.taps;
   const int t = qid % g.taps;
   const int split = unit / ntile, tile = unit % ntile;
   const int n1_0 = (tile / tiles_n2) * kBig, n2_0 = (tile % tiles_n2) * kBig;
@@ -1956,7 +1795,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_x3_kernel(WgradArgs g) {
   const int tiles_n1 = (g.N1 + kBig - 1) / kBig;
   const int ntile = tiles_n1 * tiles_n2;                        // block -> (split, tile, tap) as in gemm_tn_big_kernel
   const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;
-  const int unit = g.xcd_chunks ? xcd * (((int)gridDim.x >> 3) / g.taps) + qid / g.taps : (qid / g.taps) * 8 + xcd;
+  const int unit = xcd * (((int)gridDim.x >> 3) / g.taps) + qid / g.taps;
   const int t = qid % g.taps;
   const int split = unit / ntile, tile = unit % ntile;
   const int n1_0 = (tile / tiles_n2) * kBig, n2_0 = (tile % tiles_n2) * kBig;
@@ -2690,6 +2529,14 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* Y, long ldy, int M
 // ---------------------------------------------------------------------------------------------------------
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// OSUF_GEMM_BIG_MIN_TILES overrides when the 256^2 kernels are picked (tests: 1 forces them, 0 / "off" rules them out).  Read on
+// every call: tests flip it between calls.
+static std::optional<long> big_min_tiles_override() {
+  const char* s = getenv("OSUF_GEMM_BIG_MIN_TILES");
+  if (!s) return std::nullopt;
+  return atol(s);
+}
+
 static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, long ldw, long tapstride,
                           void* C, long ldc, void* C2, long ldc2, const void* R, long ldr, const void* U, long ldu,
                           const float* bias, const float* rscale, double* stats,
@@ -2739,15 +2586,12 @@ static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, lon
   const int lds = 2 * kStageBytes + 512;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute((const void*)gemm_nt_glds_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute((const void*)gemm_nt_glds_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute((const void*)(gemm_nt_glds_kernel<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_done = true;
   }
-  const bool noskinny = getenv("OSUF_GEMM_NOSKINNY") != nullptr;
-  if (!noskinny && dtype == OSUF_DT_BF16 && N <= 32 && N % 8 == 0 && ldc % 8 == 0 && M >= 4096 && !C2 && !R && !U && !bias && !rscale && !stats &&
+  if (dtype == OSUF_DT_BF16 && N <= 32 && N % 8 == 0 && ldc % 8 == 0 && M >= 4096 && !C2 && !R && !U && !bias && !rscale && !stats &&
       act == 0) {
     const int lds_sk = 2 * kSkStage;
     static bool sk_attr = ((void)hipFuncSetAttribute((const void*)gemm_nt_skinny_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_sk), true);
@@ -2755,12 +2599,11 @@ static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, lon
     hipLaunchKernelGGL(gemm_nt_skinny_kernel, dim3((M + kBig - 1) / kBig), dim3(512), lds_sk, stream, g);
     return osuf_launch_status();
   }
-  const bool regstage = getenv("OSUF_GEMM_REGSTAGE") != nullptr;      // A/B switches for profiling only
-  // 256^2 tiles once they fill most of the 256 CUs; OSUF_GEMM_BIG_MIN_TILES overrides the threshold (tests force 1, "off" = never)
-  const char* bigenv = getenv("OSUF_GEMM_BIG_MIN_TILES");
-  const long min_tiles = bigenv ? atol(bigenv) : 192;
+  // 256^2 tiles once they fill most of the 256 CUs
+  const std::optional<long> bigenv = big_min_tiles_override();
+  const long min_tiles = bigenv.value_or(192);
   const long big_tiles = (long)((M + kBig - 1) / kBig) * ((N + kBig - 1) / kBig);
-  const bool use_big = !regstage && (dtype == OSUF_DT_BF16 || dtype == OSUF_DT_F32X3) && min_tiles > 0 && big_tiles >= min_tiles && (N >= 192 || bigenv) && N % 8 == 0 &&
+  const bool use_big = (dtype == OSUF_DT_BF16 || dtype == OSUF_DT_F32X3) && min_tiles > 0 && big_tiles >= min_tiles && (N >= 192 || bigenv) && N % 8 == 0 &&
                        ldc % 8 == 0 && (!C2 || ldc2 % 8 == 0) && (!R || ldr % 8 == 0) && (!U || ldu % 8 == 0) &&
                        (!bias || (reinterpret_cast<uintptr_t>(bias) & 31) == 0) && (!rscale || (reinterpret_cast<uintptr_t>(rscale) & 31) == 0);
   if (use_big) {
@@ -2769,47 +2612,32 @@ static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, lon
     static bool big_attr = false;
     if (!big_attr) {
       (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-      (void)hipFuncSetAttribute((const void*)(gemm_nt_big_kernel<float, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<bf16_t, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<bf16_t, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<bf16_t, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<bf16_t, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<bf16_t, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
+      (void)hipFuncSetAttribute((const void*)(gemm_nt_big_kernel<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
       big_attr = true;
     }
     const long tm = (M + kBig - 1) / kBig, tn = (N + kBig - 1) / kBig;
-    const int dbg = getenv("OSUF_GEMM_DBG") ? atoi(getenv("OSUF_GEMM_DBG")) : 0;
     const dim3 grid_big((int)(((tm + 7) / 8) * 8 * tn));
     const bool halo3 = taps == 3 && mode == 0 && stride == 1 && pad == 1 && Lin == Lout && Lout % kBig == 0 && K % (dtype == OSUF_DT_BF16 ? 64 : 32) == 0 &&
-                       dbg == 0 && getenv("OSUF_GEMM_NOHALO") == nullptr;
+                       getenv("OSUF_GEMM_NOHALO") == nullptr;
     if (halo3) {
       static bool halo_attr = ((void)hipFuncSetAttribute((const void*)gemm_nt_big_halo3_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big),
                                (void)hipFuncSetAttribute((const void*)gemm_nt_big_halo3_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big), true);
       (void)halo_attr;
       if (dtype == OSUF_DT_BF16 && getenv("OSUF_GEMM_NO8P") == nullptr && K <= 8192) {
         const int lds_h8 = kH8B + 65536 + 2112;
-        static bool h8_attr = ((void)hipFuncSetAttribute((const void*)gemm_nt_big8_halo3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_h8), true);
+        static bool h8_attr = ((void)hipFuncSetAttribute((const void*)gemm_nt_big8_halo3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_h8), true);
         (void)h8_attr;
-        hipLaunchKernelGGL(gemm_nt_big8_halo3_kernel<0>, grid_big, dim3(512), lds_h8, stream, g);
+        hipLaunchKernelGGL(gemm_nt_big8_halo3_kernel, grid_big, dim3(512), lds_h8, stream, g);
       } else if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL(gemm_nt_big_halo3_kernel<bf16_t>, grid_big, dim3(512), lds_big, stream, g);
       else hipLaunchKernelGGL(gemm_nt_big_halo3_kernel<float>, grid_big, dim3(512), lds_big, stream, g);
     } else if (dtype == OSUF_DT_BF16 && getenv("OSUF_GEMM_NO8P") == nullptr && taps <= kP8MaxTaps && K <= 8192 && K % 64 == 0) {
       // (the 8-phase loop; OSUF_GEMM_NO8P=1 = the one-barrier-per-K-step loop above, for A/B runs and for K % 64 != 0 / more than 16 taps)
       const int lds_p8_max = kP8Tbl + kP8MaxTaps * kBig * 4;
-#define P8_CASE(D) case D: { static bool a_ = ((void)hipFuncSetAttribute((const void*)gemm_nt_big8_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_p8_max), true); (void)a_; \
-                             hipLaunchKernelGGL(gemm_nt_big8_kernel<D>, grid_big, dim3(512), lds_p8, stream, g); } break;
-      switch (dbg) { P8_CASE(1) P8_CASE(2) P8_CASE(3) P8_CASE(4) P8_CASE(5) P8_CASE(6) default: P8_CASE(0) }
-#undef P8_CASE
-    } else if (dtype == OSUF_DT_F32X3) hipLaunchKernelGGL((gemm_nt_big_kernel<float, 0, true>), grid_big, dim3(512), lds_big, stream, g);
-    else if (dbg == 1) hipLaunchKernelGGL((gemm_nt_big_kernel<bf16_t, 1>), grid_big, dim3(512), lds_big, stream, g);
-    else if (dbg == 2) hipLaunchKernelGGL((gemm_nt_big_kernel<bf16_t, 2>), grid_big, dim3(512), lds_big, stream, g);
-    else if (dbg == 3) hipLaunchKernelGGL((gemm_nt_big_kernel<bf16_t, 3>), grid_big, dim3(512), lds_big, stream, g);
-    else if (dbg == 4) hipLaunchKernelGGL((gemm_nt_big_kernel<bf16_t, 4>), grid_big, dim3(512), lds_big, stream, g);
-    else if (dbg == 5) hipLaunchKernelGGL((gemm_nt_big_kernel<bf16_t, 5>), grid_big, dim3(512), lds_big, stream, g);
+      static bool p8_attr = ((void)hipFuncSetAttribute((const void*)gemm_nt_big8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_p8_max), true);
+      (void)p8_attr;
+      hipLaunchKernelGGL(gemm_nt_big8_kernel, grid_big, dim3(512), lds_p8, stream, g);
+    } else if (dtype == OSUF_DT_F32X3) hipLaunchKernelGGL((gemm_nt_big_kernel<float, true>), grid_big, dim3(512), lds_big, stream, g);
     else hipLaunchKernelGGL(gemm_nt_big_kernel<bf16_t>, grid_big, dim3(512), lds_big, stream, g);
-  } else if (regstage) {
-    if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL(gemm_nt_kernel<bf16_t>, dim3(grid), dim3(256), lds, stream, g);
-    else hipLaunchKernelGGL(gemm_nt_kernel<float>, dim3(grid), dim3(256), lds, stream, g);
   } else {
     if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL(gemm_nt_glds_kernel<bf16_t>, dim3(grid), dim3(256), lds, stream, g);
     else if (dtype == OSUF_DT_F32X3) hipLaunchKernelGGL((gemm_nt_glds_kernel<float, true>), dim3(grid), dim3(256), lds, stream, g);
@@ -2820,10 +2648,9 @@ static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, lon
 
 // split plan of the 256x256 wgrad kernel: rows of m per split and number of splits (one workgroup per CU, ~1.25 rounds)
 static bool tn_big_plan(int dtype, int M, int N1, int N2, int taps, int* rows_out, int* splits_out) {
-  const char* bigenv = getenv("OSUF_GEMM_BIG_MIN_TILES");
-  const bool forced = bigenv && atol(bigenv) == 1, off = bigenv && atol(bigenv) <= 0;
-  const int lo = getenv("OSUF_TN_BIG_MIN_N") ? atoi(getenv("OSUF_TN_BIG_MIN_N")) : 64;
-  if ((dtype != OSUF_DT_BF16 && dtype != OSUF_DT_F32X3) || off || !(forced || (N1 >= lo && N2 >= lo && (N1 >= 192 || N2 >= 192)))) return false;
+  const std::optional<long> bigenv = big_min_tiles_override();
+  const bool forced = bigenv == 1, off = bigenv && *bigenv <= 0;
+  if ((dtype != OSUF_DT_BF16 && dtype != OSUF_DT_F32X3) || off || !(forced || (N1 >= 64 && N2 >= 64 && (N1 >= 192 || N2 >= 192)))) return false;
   const int btiles = ((N1 + kBig - 1) / kBig) * ((N2 + kBig - 1) / kBig);
   int sp = (256 + btiles * taps / 2) / (btiles * taps);        // one workgroup per CU: about one round of the 256 CUs
   if (sp < 1) sp = 1;
@@ -2870,8 +2697,7 @@ static int gemm_tn_launch(int dtype, const void* dY, long ldy, const void* X, lo
     return dbias ? osuf_colsum(dtype == OSUF_DT_BF16 ? OSUF_DT_BF16 : OSUF_DT_F32, dY, ldy, M, N1, dbias, stream) : OSUF_OK;
   };
   const int bkm = dtype == OSUF_DT_BF16 ? 64 : 32;
-  const bool noskinny = getenv("OSUF_GEMM_NOSKINNY") != nullptr;
-  if (!noskinny && splits <= 0 && dtype == OSUF_DT_BF16 && N2 <= 32 && M >= 4096) {
+  if (splits <= 0 && dtype == OSUF_DT_BF16 && N2 <= 32 && M >= 4096) {
     WgradArgs gs{};
     gs.dY = dY; gs.X = X; gs.dW = dW; gs.ws = nullptr; gs.es = es; gs.ldy = ldy; gs.ldx = ldx; gs.ldw = ldw; gs.tapstride = tapstride;
     gs.M = M; gs.N1 = N1; gs.N2 = N2; gs.taps = taps; gs.rm = RowMap{Lin, Lout, stride, pad, mode};
@@ -2932,7 +2758,6 @@ static int gemm_tn_launch(int dtype, const void* dY, long ldy, const void* X, lo
       gb.dY = dY; gb.X = X; gb.dW = dW; gb.ldy = ldy; gb.ldx = ldx; gb.ldw = ldw; gb.tapstride = tapstride;
       gb.M = M; gb.N1 = N1; gb.N2 = N2; gb.taps = taps; gb.rm = RowMap{Lin, Lout, stride, pad, mode};
       gb.rows_per_split = rows;
-      gb.xcd_chunks = getenv("OSUF_TN_RR") == nullptr;
       const long n = (long)taps * N1 * N2;
       const bool dense = (out_layout == 1 && ((long)N1 * N2) % 4 == 0) || (out_layout == 0 && ldw == N2 && (taps == 1 || tapstride == (long)N1 * N2) && n % 4 == 0 && aligned16(dW));
       gb.ws = (workspace && dense && aligned16(workspace) && workspace_bytes >= (long)sp * n * (long)sizeof(float)) ? workspace : nullptr;

@@ -979,17 +979,15 @@ extern "C" int osuf_ln_bwd(int dtype, const void* dy, long lddy, const void* x, 
   if (bad_c(C) || M <= 0 || ldx % 8 || lddy % 8 || lddx % 8) return OSUF_EINVAL;
   const int G = pick_group(C / 8);
   const int nch = (C / 8 + G - 1) / G;                // chunks per lane: 1 (C <= 512), 2 (<= 1024), 3 or 4 (<= 2048)
-  // one chunk per lane: 1,024 threads; two: 512 (the LDS reduction holds NT / 64 x 2 C floats <= 64 KiB); OSUF_LN_BWD_SMALLBLOCKS=1 = 256 everywhere (A/B)
-  const int nt = getenv("OSUF_LN_BWD_SMALLBLOCKS") != nullptr ? 256 : nch == 1 ? 1024 : nch == 2 ? 512 : 256;
+  // one chunk per lane: 1,024 threads; two: 512 (the LDS reduction holds NT / 64 x 2 C floats <= 64 KiB)
+  const int nt = nch == 1 ? 1024 : nch == 2 ? 512 : 256;
   long blocks = (M + (nt / 64) * (64 / G) - 1) / ((nt / 64) * (64 / G));
-  const char* cap_env = getenv("OSUF_LN_BWD_BLOCKS");
-  const long cap = cap_env ? atol(cap_env) : (nt == 256 || (nt == 512 && M >= 32768)) ? 512 : 256;   // bounds the dgamma / dbeta atomics (one per channel and block)
+  const long cap = (nt == 256 || (nt == 512 && M >= 32768)) ? 512 : 256;   // bounds the dgamma / dbeta atomics (one per channel and block)
   if (blocks > cap) blocks = cap;
   const size_t lds = (size_t)(nt / 64) * 2 * C * sizeof(float);
 #define LN_BWD_LAUNCH(NCH_, NT_) hipLaunchKernelGGL((ln_bwd_kernel<T, NCH_, NT_>), dim3((int)blocks), dim3(NT_), lds, stream, (const T*)dy, lddy, \
                                                     (const T*)x, ldx, (T*)dx, lddx, mr, gamma, dgamma, dbeta, M, C, G)
-  DISPATCH_T(dtype, if (nt == 1024) LN_BWD_LAUNCH(1, 1024); else if (nt == 512) LN_BWD_LAUNCH(2, 512); else if (nch == 1) LN_BWD_LAUNCH(1, 256);
-                    else if (nch == 2) LN_BWD_LAUNCH(2, 256); else LN_BWD_LAUNCH(4, 256));
+  DISPATCH_T(dtype, if (nch == 1) LN_BWD_LAUNCH(1, 1024); else if (nch == 2) LN_BWD_LAUNCH(2, 512); else LN_BWD_LAUNCH(4, 256));
 #undef LN_BWD_LAUNCH
   return osuf_launch_status();
 }
@@ -1004,10 +1002,8 @@ extern "C" int osuf_rowdot(int dtype, const void* h, long ldh, const float* w, l
 }
 
 // rows per workgroup: ~1,024 workgroups over the batch, 32 ... 128 rows each (tools/bench_gca.py, B = 32: L = 4096 / 8192 best at 128, 2048 at 64, <= 1024 at 32;
-// more rows amortise the end-of-block reduction, fewer keep the chip full); OSUF_GCA_RPB overrides (A/B)
+// more rows amortise the end-of-block reduction, fewer keep the chip full)
 static int gca_pool_rows_per_block(int M) {
-  const char* e = getenv("OSUF_GCA_RPB");
-  if (e) return atoi(e) > 0 ? atoi(e) : 64;
   int r = 32;
   while (r < 128 && (long)M / (2 * r) >= 1024) r <<= 1;
   return r;
@@ -1023,7 +1019,7 @@ extern "C" int osuf_gca_pool(int dtype, const void* h, long ldh, const float* wk
                              int M, int C, int L, hipStream_t stream) {
   if (bad_c(C) || M <= 0 || L <= 0 || M % L || ldh % 8 || !part || !p || !pooled || !wk) return OSUF_EINVAL;
   const int B = M / L, G = pick_group(C / 8), nch = (C / 8 + G - 1) / G;
-  const int rpb = std::max(32, gca_pool_rows_per_block(M)), nblk = (L + rpb - 1) / rpb;
+  const int rpb = gca_pool_rows_per_block(M), nblk = (L + rpb - 1) / rpb;
   const size_t lds = (size_t)4 * (C + 2) * sizeof(float);
   if ((size_t)nblk * sizeof(float) > 60000) return OSUF_EUNSUPPORTED;
 #define GCA_POOL_LAUNCH(NCH_) hipLaunchKernelGGL((gca_pool_kernel<T, NCH_>), dim3(nblk, B), dim3(256), lds, stream, (const T*)h, ldh, wk, bk, part, p, C, L, G, rpb)

@@ -8,8 +8,6 @@ from __future__ import annotations
 import weakref
 from typing import Dict, Optional, Tuple
 
-import os
-
 import torch
 
 from . import ops
@@ -279,13 +277,10 @@ def conv_dgrad(dy, w, cache: PackCache, kind: str, Lin: int, residual=None, vp=N
     return ops.gemm_nt(dy, wp, None, lin=Lout, lout=Lin, residual=residual, out_shape=(B, Lin, Cin), **geom)
 
 
-FUSE_BIAS_GRAD = os.environ.get("OSUF_NO_FUSED_BIAS") is None      # weight + bias gradient of a layer from one pass over dy (osuf_gemm_tn_bias); off: osuf_gemm_tn + osuf_colsum
-
-
 def conv_wgrad_bias(dy, x, w, kind: str, bias, need_w: bool, need_b: bool, n: Optional[int] = None):
     """(dw, db) of one Conv1d / Linear.  When both are wanted and the bias has a direct .grad target, its column sums ride the weight
     gradient's pass over dy; otherwise the two separate calls."""
-    if need_w and need_b and bias is not None and FUSE_BIAS_GRAD:
+    if need_w and need_b and bias is not None:
         tgt = grad_target(bias)
         if tgt is not None and tgt.numel() == w.shape[0]:
             dw = conv_wgrad(dy, x, w, kind, bias_out=tgt)
@@ -707,14 +702,8 @@ class GCAPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, wk, bk, link=None):
-        B, L, C = h.shape
         wkv = wk.reshape(-1).contiguous()
-        if ops.gca_pool_fused_ok():                        # one pass over h: logits, running softmax, weighted column sums (round 5)
-            pooled, p = ops.gca_pool(h, wkv, bk.reshape(-1), L)
-        else:
-            p = ops.rowdot(h, wkv, bk.reshape(-1), L)
-            ops.softmax_rows_(p, B, L)
-            pooled = ops.wcolsum(h, None, p, B, L)
+        pooled, p = ops.gca_pool(h, wkv, bk.reshape(-1), h.shape[1])   # one pass over h: logits, running softmax, weighted column sums
         ctx.save_for_backward(h, wkv, p, pooled)
         ctx.wshape, ctx.link = wk.shape, link
         ctx.wk_ref, ctx.bk_ref = wk, bk                   # the Parameters themselves (direct .grad accumulation)
@@ -922,9 +911,8 @@ class AttentionFn(torch.autograd.Function):
             o, lse = ops.mqa_fwd(qkv_r, B, N, H, D, dt, scale, kv_heads=G, qs=qs, zero_dq=dq_ws)
         # DoRA adapters on to_q / to_kv: their magnitude gradient needs sum_m dy * y over the PRE-RoPE projections.  Kept from here (604 MB per N = 4096
         # layer at B = 64: 23 GB over the UNet, affordable on 288 GB) instead of running the q|kv GEMM a second time in the backward (39 GEMMs of
-        # ~260 us per DoRA step); OSUF_ATTN_RECOMPUTE_QKV=1 restores the recompute
-        keep_raw = will_bwd and ((aq is not None and aq.m is not None) or (akv is not None and akv.m is not None)) and \
-            os.environ.get("OSUF_ATTN_RECOMPUTE_QKV") != "1"
+        # ~260 us per DoRA step)
+        keep_raw = will_bwd and ((aq is not None and aq.m is not None) or (akv is not None and akv.m is not None))
         ctx.qkv_raw = qkv if keep_raw else None
         del qkv
         ctx.dq_ws = dq_ws
@@ -985,7 +973,7 @@ class AttentionFn(torch.autograd.Function):
         gq = gkv = (None, None, None)
         if (aq is not None and any(need[13:16])) or (akv is not None and any(need[16:19])):
             qkv = ctx.qkv_raw                                                     # pre-RoPE projections (for d magnitude): kept by the forward, or again
-            if qkv is None:
+            if qkv is None:                                                       # (LoRA-only adapters; a second backward through a retained graph)
                 qkv = ops.gemm_nt(xn, packs[0], None, out_shape=(B, N, (H + 2 * G) * D))
             ctx.qkv_raw = None
             if aq is not None:

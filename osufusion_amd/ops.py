@@ -384,10 +384,6 @@ def rowdot(h: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], L: in
     return out
 
 
-def gca_pool_fused_ok() -> bool:
-    return os.environ.get("OSUF_GCA_NO_FUSED_POOL") != "1"
-
-
 def gca_pool(h: torch.Tensor, wk: torch.Tensor, bk: Optional[torch.Tensor], L: int):
     """GlobalContext pooling in one pass over h: returns (pooled (B, C) fp32, p (B*L,) fp32 = softmax over each sample's L logits h . wk + bk).
     A running softmax per workgroup, the workgroups' partials added in order by a second kernel: no atomics (bit-reproducible)."""
@@ -449,9 +445,8 @@ LOG2E = 1.4426950408889634
 
 def q_prescale_ok(head_dim: int, variant: int) -> bool:
     """May AttentionFn fold the softmax scale into the queries' bf16 rounding (osuf_rope_cast_qs -> osuf_mqa_fwd_qs -> osuf_mqa_bwd_fused_qs)?
-    Only the 64-wide kernels and the fused backward sweeps have the pre-scaled form; OSUF_ATTN_NO_QS=1 switches it off (A/B runs)."""
-    import os
-    return head_dim == 64 and variant in _FUSED_DQ_MODE and not os.environ.get("OSUF_ATTN_NO_QS")
+    Only the 64-wide kernels and the fused backward sweeps have the pre-scaled form."""
+    return head_dim == 64 and variant in _FUSED_DQ_MODE
 
 
 def rope_cast(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, N: int, n_rot: int, n_heads: int, head_dim: int,

@@ -1,6 +1,6 @@
-"""GlobalContext pooling: the one-pass kernel pair (osuf_gca_pool) against rowdot + softmax_rows + wcolsum at the UNet's level shapes (B = 32), for a few
-rows-per-workgroup settings (OSUF_GCA_RPB).   python tools/bench_gca.py"""
-import os, sys
+"""GlobalContext pooling: the one-pass kernel pair (osuf_gca_pool) against rowdot + softmax_rows + wcolsum at the UNet's level shapes (B = 32).
+python tools/bench_gca.py"""
+import sys
 sys.path.insert(0, "/root/repo")
 import torch
 from osufusion_amd import ops
@@ -20,9 +20,5 @@ for L, C in ((4096, 256), (2048, 512), (1024, 768), (512, 1024), (8192, 256)):
     def old_repro():
         with ops.reproducible_mode(True):
             return old()
-    line = f"B*L={B * L:6d} C={C:4d}: three kernels {timeit(old):6.1f} us (reproducible form {timeit(old_repro):6.1f})  one pass:"
-    for rpb in (32, 64, 128, 256, 512):
-        os.environ["OSUF_GCA_RPB"] = str(rpb)
-        line += f"  [{rpb}] {timeit(lambda: ops.gca_pool(h, wk, bk, L)):6.1f}"
-    os.environ.pop("OSUF_GCA_RPB", None)
-    print(line, flush=True)
+    print(f"B*L={B * L:6d} C={C:4d}: three kernels {timeit(old):6.1f} us (reproducible form {timeit(old_repro):6.1f})  one pass "
+          f"{timeit(lambda: ops.gca_pool(h, wk, bk, L)):6.1f} us", flush=True)
