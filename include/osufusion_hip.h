@@ -365,6 +365,33 @@ int osuf_vqt_logmag(const float* spec, long ld, float* out, long ldo, const floa
 int osuf_fir_decimate2(const float* in, long n_in, const float* taps, int ntaps, float* out, long n_out, hipStream_t stream);
 int osuf_frame_rows(const float* in, long n_in, int hop, int K, float* out, long frames, hipStream_t stream);
 
+/* ---- DiT row kernels (dit.hip)    replaces: osu_fusion/modules/dit.py:14-15 modulate(LayerNorm(x)), 63-70 MultiHeadRMSNorm, 275-277 the
+ *      audio statistics pooling.  Rows [M][C], M = B * L, sample of row m = m / L; C % 8 == 0, C <= 2048; row strides multiples of 8
+ *      elements, 16-B aligned pointers.  No atomics: every cross-row sum goes through per-workgroup partials added in a fixed order.
+ * osuf_adaln_fwd: out = LN(x) * (1 + scale[b]) + shift[b] (no affine, eps given); shift / scale fp32 read at [b * ldm + c] (e.g. column
+ *      blocks of the (B, 6C) modulation output, ldm = 6C); mr[2m] = mean, mr[2m+1] = rstd (fp32).
+ * osuf_adaln_bwd: dx = dres + LN-backward(dy * (1 + scale[b])) (dres may be NULL); stores dshift[b][c] = sum_n dy at dmod[b * ldd + c]
+ *      and dscale[b][c] = sum_n dy * xhat at dmod[b * ldd + off2 + c] (e.g. column blocks of the (B, 6C) modulation gradient, ldd = 6C);
+ *      B = M / L <= 65535; workspace: osuf_adaln_bwd_workspace_bytes(M, C, L) bytes.
+ * osuf_qknorm_fwd: raw q|k|v projection rows [M][3 H D] (dtype) -> bf16 rows: q and k heads x / max(||x||, 1e-12) * gamma[h] * sqrt(D),
+ *      v copied; inv[m][2H] = 1 / max(||x||, 1e-12) of the q then k heads.  D in {16, 32, 64, 128}, 3 H D <= 4096.
+ * osuf_qknorm_bwd: fp32 dq|dk|dv rows -> gradient of the raw projections (dtype); dgamma [2][H][D] (q then k) stored;
+ *      workspace: osuf_qknorm_bwd_workspace_bytes(M, H, D) bytes.
+ * osuf_stat_pool: a fp32 (B, C, L) contiguous -> out (B, 2C) = [mean_l | unbiased std_l]. ---- */
+int osuf_adaln_fwd(int dtype, const void* x, long ldx, void* out, long ldo, float* mr, const float* shift, const float* scale, long ldm,
+                   int M, int C, int L, float eps, hipStream_t stream);
+long osuf_adaln_bwd_workspace_bytes(int M, int C, int L);
+int osuf_adaln_bwd(int dtype, const void* dy, long lddy, const void* x, long ldx, const void* dres, long ldr, void* dx, long lddx,
+                   const float* mr, const float* scale, long ldm, float* dmod, long ldd, long off2, float* workspace, long workspace_bytes,
+                   int M, int C, int L, hipStream_t stream);
+int osuf_qknorm_fwd(int dtype, const void* x, long ldx, void* y, long ldy, float* inv, const float* gamma_q, const float* gamma_k,
+                    int M, int H, int D, hipStream_t stream);
+long osuf_qknorm_bwd_workspace_bytes(int M, int H, int D);
+int osuf_qknorm_bwd(int dtype, const float* g, long ldg, const void* x, long ldx, const float* inv, const float* gamma_q,
+                    const float* gamma_k, void* dx, long lddx, float* dgamma, float* workspace, long workspace_bytes,
+                    int M, int H, int D, hipStream_t stream);
+int osuf_stat_pool(const float* a, float* out, int B, int C, int L, hipStream_t stream);
+
 /* Measurement aid (no reference counterpart): sustained shader clock under an MFMA (mode 1) or VALU (mode 0) load.
  * out[2*block] = shader cycles, out[2*block+1] = 100 MHz wall ticks. */
 int osuf_clock_probe(int blocks, int iters, int mode, long* out, hipStream_t stream);
