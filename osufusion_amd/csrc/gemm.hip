@@ -58,6 +58,15 @@ static constexpr int kStageBytes = 2 * kTile * 128;   // A tile + B tile, 128 B 
 
 __device__ __forceinline__ int swz_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
+template <int NI, int NJ> __device__ __forceinline__ void zero_acc(f32x16 (&acc)[NI][NJ]) {
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
 // LOADS = false: instantiation for launches without residual / dact operand -- no vector-memory load inside the store loop, hence no
 // `s_waitcnt vmcnt(0)` (which also waits for the previous pass's stores) in front of every pass; see gemm_big_epilogue_impl.
 template <typename T, bool LOADS>
@@ -186,6 +195,13 @@ __device__ __forceinline__ void mfma_x3(f32x16& acc, const bf16x8& ah, const bf1
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
 }
+// split fragment of the 256^2 kernels out of a swizzled fp32 stage (32 k per row): k = 16 ks + 8 lh + 0..7 of this lane's row
+__device__ __forceinline__ void frag_x3(const char* base, int row, int ks, int lh, bf16x8& hi, bf16x8& lo) {
+  const f32x4 x0 = *reinterpret_cast<const f32x4*>(base + swz_off(row, 4 * ks + 2 * lh));
+  const f32x4 x1 = *reinterpret_cast<const f32x4*>(base + swz_off(row, 4 * ks + 2 * lh + 1));
+  const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+  split_bf16x8(x, hi, lo);
+}
 
 template <typename T>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[2][2], char* smem, int m0, int n0, int tid, int lane, int wr, int wc) {
@@ -253,12 +269,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_glds_kernel(GemmArgs g) {
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int lr = lane & 31, lh = lane >> 5;
   issue(0, 0);
@@ -509,6 +520,18 @@ __device__ __forceinline__ void gemm_big_epilogue(const GemmArgs& g, f32x16 (&ac
   else gemm_big_epilogue_impl<T, 3>(g, acc, smem, m0, n0, tid, lane, wave, wr, wc);
 }
 
+// (m0, n0) of this workgroup's 256 x 256 tile; false: the grid's padding beyond the last M-tile.
+// XCD-aware tile order (speed only): block ids are dealt round-robin to the 8 XCDs, so the N-tiles that share one
+// M-tile's A rows get ids 8 apart -> same XCD (same L2), dispatched back to back.
+__device__ __forceinline__ bool nt_big_tile(const GemmArgs& g, int& m0, int& n0) {
+  const int tiles_n = (g.N + kBig - 1) / kBig;
+  const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;
+  const int mt = (qid / tiles_n) * 8 + xcd;
+  m0 = mt * kBig;
+  n0 = (qid % tiles_n) * kBig;
+  return m0 < g.M;
+}
+
 // SPLIT (T = float, OSUF_DT_F32X3): fp32 stages (32 k per row), every fragment split in registers into bf16 hi + lo, three bf16
 // MFMAs per product (mfma_x3) -- two 16-deep k-steps per stage, 48 MFMAs per wave and stage against 32 of the bf16 kernel.
 template <typename T, bool SPLIT = false>
@@ -518,13 +541,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(GemmArgs g) {
   constexpr int EPC = ElemTraits<T>::kPer16B;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
-  const int tiles_n = (g.N + kBig - 1) / kBig;
-  // XCD-aware tile order (speed only): block ids are dealt round-robin to the 8 XCDs, so the N-tiles that share one
-  // M-tile's A rows get ids 8 apart -> same XCD (same L2), dispatched back to back.
-  const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;
-  const int mt = (qid / tiles_n) * 8 + xcd;
-  const int m0 = mt * kBig, n0 = (qid % tiles_n) * kBig;
-  if (m0 >= g.M) return;
+  int m0, n0;
+  if (!nt_big_tile(g, m0, n0)) return;
   const T* A = reinterpret_cast<const T*>(g.A);
   const T* W = reinterpret_cast<const T*>(g.W);
   const char* zero = reinterpret_cast<const char*>(g_zero_page);
@@ -594,12 +612,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(GemmArgs g) {
   };
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int lr = lane & 31, lh = lane >> 5;
   issue(0);
@@ -614,16 +627,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(GemmArgs g) {
       for (int ks = 0; ks < 2; ++ks) {
         if (more) { issue_part(buf ^ 1, 2 * ks); issue_part(buf ^ 1, 2 * ks + 1); }
         bf16x8 ah[4], al[4], bh[2], bl[2];
-        auto frag = [&](const char* base, int row, bf16x8& hi, bf16x8& lo) {      // k = 16 ks + 8 lh + 0..7 of this lane's row
-          const f32x4 x0 = *reinterpret_cast<const f32x4*>(base + swz_off(row, 4 * ks + 2 * lh));
-          const f32x4 x1 = *reinterpret_cast<const f32x4*>(base + swz_off(row, 4 * ks + 2 * lh + 1));
-          const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-          split_bf16x8(x, hi, lo);
-        };
 #pragma unroll
-        for (int i = 0; i < 4; ++i) frag(sa, wr * 128 + i * 32 + lr, ah[i], al[i]);
+        for (int i = 0; i < 4; ++i) frag_x3(sa, wr * 128 + i * 32 + lr, ks, lh, ah[i], al[i]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) frag(sb, wc * 64 + j * 32 + lr, bh[j], bl[j]);
+        for (int j = 0; j < 2; ++j) frag_x3(sb, wc * 64 + j * 32 + lr, ks, lh, bh[j], bl[j]);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -684,6 +691,79 @@ template <int OFF> __device__ __forceinline__ void lds_read_b128(u32x4& d, uint3
 }
 template <int V> struct IntC { static constexpr int value = V; };
 
+// the fragment waits name the registers they retire, so no MFMA that uses them can be scheduled in front of the wait
+template <int CNT> __device__ __forceinline__ void p8_wait_a(u32x4 (&fa)[2][4]) {
+  asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fa[0][3]), "+v"(fa[1][0]),
+               "+v"(fa[1][1]), "+v"(fa[1][2]), "+v"(fa[1][3]) : "n"(CNT));
+}
+template <int CNT> __device__ __forceinline__ void p8_wait_b(u32x4 (&fb)[4]) {
+  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]) : "n"(CNT));
+}
+// one phase's 8-MFMA cluster: the 64 x 32 quadrant acc[I0..I0+1][J] over the four k16 sub-steps
+template <int I0, int J> __device__ __forceinline__ void p8_mfma(f32x16 (&acc)[4][2], const u32x4 (&fa)[2][4], const u32x4 (&fb)[4]) {
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    acc[I0][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[0][ks]), __builtin_bit_cast(bf16x8, fb[ks]), acc[I0][J], 0, 0, 0);
+    acc[I0 + 1][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[1][ks]), __builtin_bit_cast(bf16x8, fb[ks]), acc[I0 + 1][J], 0, 0, 0);
+  }
+  __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// One K-tile = the four phases.  ka / kb: this lane's fragment addresses (k16 sub-step ks) in the wave's first A / B MFMA tile of a buffer at
+// offset 0; OA / OB: byte offsets of the A / B buffer the K-tile is read from (immediates, with the MFMA tile's 4 KiB and the half-tile).
+// stage1 .. stage4 issue what the kernel stages in P1 .. P4; stage4 ends with the K-tile's one vector-memory wait (its count depends on what
+// the kernel has in flight), behind which everything the NEXT K-tile reads has landed.
+template <int OA, int OB, typename S1, typename S2, typename S3, typename S4>
+__device__ __forceinline__ void p8_ktile(f32x16 (&acc)[4][2], const uint32_t (&ka)[4], const uint32_t (&kb)[4], S1 stage1, S2 stage2, S3 stage3,
+                                         S4 stage4) {
+  u32x4 fa[2][4], fb0[4], fb1[4];
+  // ---- P1: B0, A0 -> acc[0..1][0]
+  lds_read_b128<OB>(fb0[0], kb[0]); lds_read_b128<OB>(fb0[1], kb[1]); lds_read_b128<OB>(fb0[2], kb[2]); lds_read_b128<OB>(fb0[3], kb[3]);
+  __builtin_amdgcn_sched_barrier(0);
+  lds_read_b128<OA>(fa[0][0], ka[0]); lds_read_b128<OA>(fa[0][1], ka[1]); lds_read_b128<OA>(fa[0][2], ka[2]); lds_read_b128<OA>(fa[0][3], ka[3]);
+  lds_read_b128<OA + 4096>(fa[1][0], ka[0]); lds_read_b128<OA + 4096>(fa[1][1], ka[1]); lds_read_b128<OA + 4096>(fa[1][2], ka[2]);
+  lds_read_b128<OA + 4096>(fa[1][3], ka[3]);
+  stage1();
+  p8_wait_b<8>(fb0);                                          // B0's reads are done before anyone passes the barrier: P2 re-stages B0's slot
+  __builtin_amdgcn_s_barrier();
+  p8_wait_a<0>(fa);
+  p8_mfma<0, 0>(acc, fa, fb0);
+  __builtin_amdgcn_s_barrier();
+  // ---- P2: B1 -> acc[0..1][1]
+  lds_read_b128<OB + 4096>(fb1[0], kb[0]); lds_read_b128<OB + 4096>(fb1[1], kb[1]); lds_read_b128<OB + 4096>(fb1[2], kb[2]); lds_read_b128<OB + 4096>(fb1[3], kb[3]);
+  stage2();
+  __builtin_amdgcn_s_barrier();
+  p8_wait_b<0>(fb1);
+  p8_mfma<0, 1>(acc, fa, fb1);
+  __builtin_amdgcn_s_barrier();
+  // ---- P3: A1 -> acc[2..3][1]
+  lds_read_b128<OA + 8192>(fa[0][0], ka[0]); lds_read_b128<OA + 8192>(fa[0][1], ka[1]); lds_read_b128<OA + 8192>(fa[0][2], ka[2]);
+  lds_read_b128<OA + 8192>(fa[0][3], ka[3]);
+  lds_read_b128<OA + 12288>(fa[1][0], ka[0]); lds_read_b128<OA + 12288>(fa[1][1], ka[1]); lds_read_b128<OA + 12288>(fa[1][2], ka[2]);
+  lds_read_b128<OA + 12288>(fa[1][3], ka[3]);
+  stage3();
+  __builtin_amdgcn_s_barrier();
+  p8_wait_a<0>(fa);
+  p8_mfma<2, 1>(acc, fa, fb1);
+  __builtin_amdgcn_s_barrier();
+  // ---- P4: (B0 still in registers) -> acc[2..3][0]
+  stage4();
+  __builtin_amdgcn_s_barrier();
+  p8_mfma<2, 0>(acc, fa, fb0);
+  __builtin_amdgcn_s_barrier();
+}
+
+// B-side DMA sources of the 8-phase kernels at tap 0, K-step 0.  Half-tile s of B = tile rows wc' * 64 + s * 32 + 0..31 (wc' = 0..3); a wave
+// moves two 8-row pieces j of each: rows (wave >> 1) * 64 + s * 32 + (wave & 1) * 16 + 8 j + lane / 8.  W rows beyond N are clamped to N - 1
+// (their output columns are never stored), so every later step on the B side is one uniform pointer delta.
+__device__ __forceinline__ const char* p8_b_source(const GemmArgs& g, int n0, int wave, int lane, int s, int j) {
+  const int rb = (wave >> 1) * 64 + s * 32 + (wave & 1) * 16 + j * 8 + (lane >> 3);
+  return reinterpret_cast<const char*>(reinterpret_cast<const bf16_t*>(g.W) + (long)min(n0 + rb, g.N - 1) * g.ldw + ((lane & 7) ^ ((rb >> 1) & 7)) * 8);
+}
+
 __device__ uint4 g_zero_row[1024];                           // 16 KiB of zeros: the source "row" of padded / out-of-range A rows (K <= 8192 bf16)
 static constexpr int kP8Tbl = 2 * kBigStage + 2112;          // LDS: per-tap source rows of the tile's 256 A rows, [taps][256] ints, behind the stat slots
 static constexpr int kP8MaxTaps = 16;
@@ -695,13 +775,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int tiles_n = (g.N + kBig - 1) / kBig;
-  const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;       // tile order as in gemm_nt_big_kernel
-  const int mt = (qid / tiles_n) * 8 + xcd;
-  const int m0 = mt * kBig, n0 = (qid % tiles_n) * kBig;
-  if (m0 >= g.M) return;
+  int m0, n0;
+  if (!nt_big_tile(g, m0, n0)) return;
   const char* A = reinterpret_cast<const char*>(g.A);
-  const T* W = reinterpret_cast<const T*>(g.W);
   const char* zero = reinterpret_cast<const char*>(g_zero_row);
   const int ksteps = (g.K + BK - 1) / BK;
   const int n = g.taps * ksteps;                             // K-tiles (K % 64 == 0: launcher)
@@ -722,14 +798,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
     __syncthreads();
   }
 
-  // DMA roles.  Half-tile s of A = tile rows wr' * 128 + s * 64 + 0..63 (wr' = 0, 1); of B = tile rows wc' * 64 + s * 32 + 0..31
-  // (wc' = 0..3).  A wave moves two 8-row pieces (j) of every half-tile: A rows (wave >> 2) * 128 + s * 64 + (wave & 3) * 16 + 8 j + lane / 8,
-  // B rows (wave >> 1) * 64 + s * 32 + (wave & 1) * 16 + 8 j + lane / 8.  Every K-step is `pointer += 128 B` (zero rows walk the zero row);
-  // W rows beyond N are clamped to N - 1 (their output columns are never stored), so a tap switch on the B side is one uniform delta.
+  // DMA roles.  Half-tile s of A = tile rows wr' * 128 + s * 64 + 0..63 (wr' = 0, 1); a wave moves two 8-row pieces (j) of every half-tile:
+  // A rows (wave >> 2) * 128 + s * 64 + (wave & 3) * 16 + 8 j + lane / 8 (B: p8_b_sources).  Every K-step is `pointer += 128 B` (zero rows
+  // walk the zero row); a tap switch on the B side is one uniform delta.
   const char* pa[2][2];
   const char* pb[2][2];
   auto a_row = [&](int s, int j) { return (wave >> 2) * 128 + s * 64 + (wave & 3) * 16 + j * 8 + (lane >> 3); };
-  auto b_row = [&](int s, int j) { return (wave >> 1) * 64 + s * 32 + (wave & 1) * 16 + j * 8 + (lane >> 3); };
   const long lda_b = g.lda * (long)sizeof(T);
   auto set_tap_a = [&](int t) {
     int src[2][2];
@@ -747,13 +821,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
         pa[s][j] = (src[s][j] >= 0 ? A + (long)src[s][j] * lda_b : zero) + chunk;
       }
   };
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int rb = b_row(s, j);
-      pb[s][j] = reinterpret_cast<const char*>(W + (long)min(n0 + rb, g.N - 1) * g.ldw + ((lane & 7) ^ ((rb >> 1) & 7)) * 8);
-    }
+  _Pragma("unroll") for (int s = 0; s < 2; ++s) _Pragma("unroll") for (int j = 0; j < 2; ++j) pb[s][j] = p8_b_source(g, n0, wave, lane, s, j);
   const long tap_delta_b = (g.tapstride - (long)ksteps * BK) * (long)sizeof(T);      // from the end of tap t's K range to the start of tap t + 1's
   const int aw = ((wave >> 2) * 128 + (wave & 3) * 16) * 128;  // LDS byte offsets of this wave's first piece in a half-tile 0
   const int bw = 65536 + ((wave >> 1) * 64 + (wave & 1) * 16) * 128;
@@ -785,12 +853,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
   };
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   // fragment addresses: row lr of the wave's first A / B MFMA tile, chunk (2 ks + lh) ^ swizzle; tile i / j, buffer: immediates
   const int lr = lane & 31, lh = lane >> 5;
@@ -801,70 +864,20 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
     ka[ks] = lds0 + (uint32_t)((wr * 128 + lr) * 128) + ch;
     kb[ks] = lds0 + 65536u + (uint32_t)((wc * 64 + lr) * 128) + ch;
   }
-  u32x4 fa[2][4], fb0[4], fb1[4];
-#define P8_WAIT_A(cnt)                                                                                                        \
-  asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fa[0][3]), "+v"(fa[1][0]), \
-               "+v"(fa[1][1]), "+v"(fa[1][2]), "+v"(fa[1][3]));
-#define P8_WAIT_B(cnt, fb) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
-#define P8_MFMA(i0, j, fbv)                                                                                                   \
-  {                                                                                                                           \
-    __builtin_amdgcn_s_setprio(1);                                                                                            \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                                        \
-      acc[i0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[0][ks]), __builtin_bit_cast(bf16x8, fbv[ks]), acc[i0][j], 0, 0, 0); \
-      acc[i0 + 1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[1][ks]), __builtin_bit_cast(bf16x8, fbv[ks]), acc[i0 + 1][j], 0, 0, 0); \
-    }                                                                                                                         \
-    __builtin_amdgcn_s_setprio(0);                                                                                            \
-  }
-  // one K-tile (four phases) out of buffer BUF; t = its index
+  // one K-tile out of buffer BUF; t = its index.  P1 stages A1(t + 1), P2 B0(t + 2), P3 A0(t + 2), P4 B1(t + 2)
   auto tile = [&](auto bufc, int t) {
     constexpr int BUF = decltype(bufc)::value, O = BUF * 32768;
-    // ---- P1: B0, A0 -> acc[0..1][0]; stage A1(t + 1)
-    lds_read_b128<O>(fb0[0], kb[0]); lds_read_b128<O>(fb0[1], kb[1]); lds_read_b128<O>(fb0[2], kb[2]); lds_read_b128<O>(fb0[3], kb[3]);
-    __builtin_amdgcn_sched_barrier(0);
-    lds_read_b128<O>(fa[0][0], ka[0]); lds_read_b128<O>(fa[0][1], ka[1]); lds_read_b128<O>(fa[0][2], ka[2]); lds_read_b128<O>(fa[0][3], ka[3]);
-    lds_read_b128<O + 4096>(fa[1][0], ka[0]); lds_read_b128<O + 4096>(fa[1][1], ka[1]); lds_read_b128<O + 4096>(fa[1][2], ka[2]);
-    lds_read_b128<O + 4096>(fa[1][3], ka[3]);
-    if (t + 1 < n) { stage(IntC<3>{}, IntC<BUF ^ 1>{}); next_ktile(); }
-    P8_WAIT_B(8, fb0)                                           // B0's reads are done before anyone passes the barrier: P2 re-stages B0's slot
-    __builtin_amdgcn_s_barrier();
-    P8_WAIT_A(0)
-    __builtin_amdgcn_sched_barrier(0);
-    P8_MFMA(0, 0, fb0)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- P2: B1 -> acc[0..1][1]; stage B0(t + 2)
-    lds_read_b128<O + 4096>(fb1[0], kb[0]); lds_read_b128<O + 4096>(fb1[1], kb[1]); lds_read_b128<O + 4096>(fb1[2], kb[2]); lds_read_b128<O + 4096>(fb1[3], kb[3]);
-    if (t + 2 < n) stage(IntC<0>{}, IntC<BUF>{});
-    __builtin_amdgcn_s_barrier();
-    P8_WAIT_B(0, fb1)
-    __builtin_amdgcn_sched_barrier(0);
-    P8_MFMA(0, 1, fb1)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- P3: A1 -> acc[2..3][1]; stage A0(t + 2)
-    lds_read_b128<O + 8192>(fa[0][0], ka[0]); lds_read_b128<O + 8192>(fa[0][1], ka[1]); lds_read_b128<O + 8192>(fa[0][2], ka[2]);
-    lds_read_b128<O + 8192>(fa[0][3], ka[3]);
-    lds_read_b128<O + 12288>(fa[1][0], ka[0]); lds_read_b128<O + 12288>(fa[1][1], ka[1]); lds_read_b128<O + 12288>(fa[1][2], ka[2]);
-    lds_read_b128<O + 12288>(fa[1][3], ka[3]);
-    if (t + 2 < n) stage(IntC<1>{}, IntC<BUF>{});
-    __builtin_amdgcn_s_barrier();
-    P8_WAIT_A(0)
-    __builtin_amdgcn_sched_barrier(0);
-    P8_MFMA(2, 1, fb1)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- P4: (B0 still in registers) -> acc[2..3][0]; stage B1(t + 2); K-tile t + 1 has landed behind the counted wait
-    if (t + 2 < n) {
-      stage(IntC<2>{}, IntC<BUF>{});
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    P8_MFMA(2, 0, fb0)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
+    p8_ktile<O, O>(
+        acc, ka, kb, [&] { if (t + 1 < n) { stage(IntC<3>{}, IntC<BUF ^ 1>{}); next_ktile(); } },
+        [&] { if (t + 2 < n) stage(IntC<0>{}, IntC<BUF>{}); }, [&] { if (t + 2 < n) stage(IntC<1>{}, IntC<BUF>{}); },
+        [&] {                                                  // K-tile t + 1 has landed behind the counted wait
+          if (t + 2 < n) {
+            stage(IntC<2>{}, IntC<BUF>{});
+            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+          } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          }
+        });
   };
 
   // prologue: K-tile 0 and three half-tiles of K-tile 1
@@ -886,9 +899,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
   }
   if (t < n) tile(IntC<0>{}, t);
   if (wr == 0) __builtin_amdgcn_s_barrier();
-#undef P8_WAIT_A
-#undef P8_WAIT_B
-#undef P8_MFMA
   gemm_big_epilogue<T>(g, acc, smem, m0, n0, tid, lane, wave, wr, wc);
 }
 
@@ -904,6 +914,16 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_kernel(GemmArgs g) {
 static constexpr int kPanelRows = 264;                       // 33 DMA groups of 8 rows
 static constexpr int kPanelBytes = kPanelRows * 128;
 
+// DMA piece i of a wave's share of the panel: group gi (8 rows) of wave w is 4 w + i, i < 4; wave 0 also loads group 32 (rows 256 .. 263, of
+// which 256 and 257 are read).  ok: the lane's panel row lies inside the tile's sample (a tile never straddles samples) -- the others are zeros.
+struct HaloPiece { bool ok; long row; int chunk; };          // activation row, and the lane's logical 16-B chunk of it (swizzled)
+__device__ __forceinline__ HaloPiece halo_piece(const GemmArgs& g, int m0, int wave, int lane, int i) {
+  const int L = g.rm.Lout;
+  const int r = ((i < 4 ? wave * 4 + i : 32) * 8) + (lane >> 3);         // panel row; activation row m0 - 1 + r
+  const int pos = m0 % L - 1 + r;                            // position inside the sample
+  return {r < 258 && pos >= 0 && pos < L, (long)(m0 - 1 + r), (lane & 7) ^ ((r >> 1) & 7)};
+}
+
 // (T = float: the fp32 mode's split-bf16 form -- fp32 panels and B tiles of 32 k per row, fragments split in registers, mfma_x3)
 template <typename T>
 __global__ __launch_bounds__(512, 2) void gemm_nt_big_halo3_kernel(GemmArgs g) {
@@ -913,29 +933,21 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_halo3_kernel(GemmArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int tiles_n = (g.N + kBig - 1) / kBig;
-  const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;       // tile order as in gemm_nt_big_kernel
-  const int mt = (qid / tiles_n) * 8 + xcd;
-  const int m0 = mt * kBig, n0 = (qid % tiles_n) * kBig;
-  if (m0 >= g.M) return;
+  int m0, n0;
+  if (!nt_big_tile(g, m0, n0)) return;
   const T* A = reinterpret_cast<const T*>(g.A);
   const T* W = reinterpret_cast<const T*>(g.W);
   const char* zero = reinterpret_cast<const char*>(g_zero_page);
-  const int L = g.rm.Lout;
-  const int pos0 = m0 % L;                                   // position of the tile's first row inside its sample
   const int ksteps = g.K / (8 * EPC);
 
-  // A panel: group gi (8 rows) of wave w is 4 w + i, i < 4; wave 0 also loads group 32 (rows 256 .. 263, of which 256 and 257 are read)
+  // A panel (rows outside the sample stay on the zero page)
   const char* pa[5];
   int ia[5];
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
-    const int r = ((i < 4 ? wave * 4 + i : 32) * 8) + (lane >> 3);       // panel row; activation row m0 - 1 + r
-    const int pos = pos0 - 1 + r;
-    const bool ok = r < 258 && pos >= 0 && pos < L;
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    pa[i] = ok ? reinterpret_cast<const char*>(A + (long)(m0 - 1 + r) * g.lda + c * EPC) : zero;
-    ia[i] = ok ? 128 : 0;
+    const HaloPiece p = halo_piece(g, m0, wave, lane, i);
+    pa[i] = p.ok ? reinterpret_cast<const char*>(A + p.row * g.lda + p.chunk * EPC) : zero;
+    ia[i] = p.ok ? 128 : 0;
   }
   // B tiles: this lane's row of W for DMA instruction i, tap 0, K-step 0
   const char* pb[4];
@@ -961,12 +973,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_halo3_kernel(GemmArgs g) {
   };
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int lr = lane & 31, lh = lane >> 5;
 #pragma unroll
@@ -996,16 +1003,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_halo3_kernel(GemmArgs g) {
             if (t == 2 && ks == 1 && wave == 0) issue_a((kb + 1) & 1, 4);
           }
           bf16x8 ah[4], al[4], bh[2], bl[2];
-          auto frag = [&](const char* base, int row, bf16x8& hi, bf16x8& lo) {      // k = 16 ks + 8 lh + 0..7 of this lane's row
-            const f32x4 x0 = *reinterpret_cast<const f32x4*>(base + swz_off(row, 4 * ks + 2 * lh));
-            const f32x4 x1 = *reinterpret_cast<const f32x4*>(base + swz_off(row, 4 * ks + 2 * lh + 1));
-            const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-            split_bf16x8(x, hi, lo);
-          };
 #pragma unroll
-          for (int i = 0; i < 4; ++i) frag(pan, wr * 128 + i * 32 + lr + t, ah[i], al[i]);
+          for (int i = 0; i < 4; ++i) frag_x3(pan, wr * 128 + i * 32 + lr + t, ks, lh, ah[i], al[i]);
 #pragma unroll
-          for (int j = 0; j < 2; ++j) frag(sb, wc * 64 + j * 32 + lr, bh[j], bl[j]);
+          for (int j = 0; j < 2; ++j) frag_x3(sb, wc * 64 + j * 32 + lr, ks, lh, bh[j], bl[j]);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1057,41 +1058,24 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_halo3_kernel(GemmArgs g) 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int tiles_n = (g.N + kBig - 1) / kBig;
-  const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;       // tile order as in gemm_nt_big_kernel
-  const int mt = (qid / tiles_n) * 8 + xcd;
-  const int m0 = mt * kBig, n0 = (qid % tiles_n) * kBig;
-  if (m0 >= g.M) return;
+  int m0, n0;
+  if (!nt_big_tile(g, m0, n0)) return;
   const T* A = reinterpret_cast<const T*>(g.A);
-  const T* W = reinterpret_cast<const T*>(g.W);
   const char* zero = reinterpret_cast<const char*>(g_zero_row);
-  const int L = g.rm.Lout;
-  const int pos0 = m0 % L;                                   // position of the tile's first row inside its sample (a tile never straddles samples)
   const int ksteps = g.K / 64;
   const int n = 3 * ksteps;                                  // K-tiles
   const uint32_t lds0 = (uint32_t)(uintptr_t)(LDS_PTR(char))smem;
 
-  // A panel: group gi (8 rows) of wave w is 4 w + i, i < 4; wave 0 also loads group 32 (rows 256 .. 263, of which 256 and 257 are read).
-  // Rows outside the sample walk the zero row.
+  // A panel; rows outside the sample walk the zero row
   const char* pa[5];
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
-    const int r = ((i < 4 ? wave * 4 + i : 32) * 8) + (lane >> 3);       // panel row; activation row m0 - 1 + r
-    const int pos = pos0 - 1 + r;
-    const bool ok = r < 258 && pos >= 0 && pos < L;
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    pa[i] = (ok ? reinterpret_cast<const char*>(A + (long)(m0 - 1 + r) * g.lda) : zero) + c * 16;
+    const HaloPiece p = halo_piece(g, m0, wave, lane, i);
+    pa[i] = (p.ok ? reinterpret_cast<const char*>(A + p.row * g.lda) : zero) + p.chunk * 16;
   }
-  // B: half-tile s = tile rows wc' * 64 + s * 32 + 0..31; this wave's two pieces j: rows (wave >> 1) * 64 + s * 32 + (wave & 1) * 16 + 8 j + lane / 8.
-  // Running pointers through (K-step, tap) order; W rows beyond N are clamped (their columns are never stored).
+  // B: running pointers through (K-step, tap) order
   const char* pb[2][2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int rb = (wave >> 1) * 64 + s * 32 + (wave & 1) * 16 + j * 8 + (lane >> 3);
-      pb[s][j] = reinterpret_cast<const char*>(W + (long)min(n0 + rb, g.N - 1) * g.ldw + ((lane & 7) ^ ((rb >> 1) & 7)) * 8);
-    }
+  _Pragma("unroll") for (int s = 0; s < 2; ++s) _Pragma("unroll") for (int j = 0; j < 2; ++j) pb[s][j] = p8_b_source(g, n0, wave, lane, s, j);
   const long tapb = g.tapstride * (long)sizeof(T);
   const long next_k = 128 - 2 * tapb;                        // from tap 2 of a K-step to tap 0 of the next
   const int bw = kH8B + ((wave >> 1) * 64 + (wave & 1) * 16) * 128;
@@ -1118,96 +1102,47 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_halo3_kernel(GemmArgs g) 
   };
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int lr = lane & 31, lh = lane >> 5;
   uint32_t kb_[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) kb_[ks] = lds0 + (uint32_t)kH8B + (uint32_t)((wc * 64 + lr) * 128) + (uint32_t)(((2 * ks + lh) ^ ((lr >> 1) & 7)) << 4);
-  u32x4 fa[2][4], fb0[4], fb1[4];
-#define H8_WAIT_A(cnt)                                                                                                        \
-  asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fa[0][3]), "+v"(fa[1][0]), \
-               "+v"(fa[1][1]), "+v"(fa[1][2]), "+v"(fa[1][3]));
-#define H8_WAIT_B(cnt, fb) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
-#define H8_MFMA(i0, j, fbv)                                                                                                   \
-  {                                                                                                                           \
-    __builtin_amdgcn_s_setprio(1);                                                                                            \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                                        \
-      acc[i0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[0][ks]), __builtin_bit_cast(bf16x8, fbv[ks]), acc[i0][j], 0, 0, 0); \
-      acc[i0 + 1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[1][ks]), __builtin_bit_cast(bf16x8, fbv[ks]), acc[i0 + 1][j], 0, 0, 0); \
-    }                                                                                                                         \
-    __builtin_amdgcn_s_setprio(0);                                                                                            \
-  }
-  // one K-tile = (K-step in panel PANEL, tap TAP), B tile in buffer BUF; t = its index, more_k: another K-step follows this one
+  // one K-tile = (K-step in panel PANEL, tap TAP), B tile in buffer BUF; t = its index, more_k: another K-step follows this one.
+  // P1 / P3 stage pieces of the next panel, P2 B0(t + 2), P4 B1(t + 2)
   auto tile = [&](auto panelc, auto bufc, auto tapc, int t, bool more_k) {
     constexpr int PANEL = decltype(panelc)::value, BUF = decltype(bufc)::value, TAP = decltype(tapc)::value;
-    constexpr int OA = PANEL * kPanelBytes, OB = BUF * 32768;
     // fragment rows of this tap: panel row wr * 128 + i * 32 + lr + TAP (the swizzle follows the shifted row)
     uint32_t ka[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
       ka[ks] = lds0 + (uint32_t)((wr * 128 + lr + TAP) * 128) + (uint32_t)(((2 * ks + lh) ^ (((lr + TAP) >> 1) & 7)) << 4);
-    // ---- P1: B0, A rows 0..63 -> acc[0..1][0]; a piece of the next panel
-    lds_read_b128<OB>(fb0[0], kb_[0]); lds_read_b128<OB>(fb0[1], kb_[1]); lds_read_b128<OB>(fb0[2], kb_[2]); lds_read_b128<OB>(fb0[3], kb_[3]);
-    __builtin_amdgcn_sched_barrier(0);
-    lds_read_b128<OA>(fa[0][0], ka[0]); lds_read_b128<OA>(fa[0][1], ka[1]); lds_read_b128<OA>(fa[0][2], ka[2]); lds_read_b128<OA>(fa[0][3], ka[3]);
-    lds_read_b128<OA + 4096>(fa[1][0], ka[0]); lds_read_b128<OA + 4096>(fa[1][1], ka[1]); lds_read_b128<OA + 4096>(fa[1][2], ka[2]);
-    lds_read_b128<OA + 4096>(fa[1][3], ka[3]);
-    if (more_k) {
-      if (TAP == 0) stage_a(IntC<0>{}, IntC<PANEL ^ 1>{});
-      if (TAP == 1) stage_a(IntC<2>{}, IntC<PANEL ^ 1>{});
-      if (TAP == 2 && wave == 0) stage_a(IntC<4>{}, IntC<PANEL ^ 1>{});
-    }
-    H8_WAIT_B(8, fb0)                                           // B0's reads are done before anyone passes the barrier: P2 re-stages B0's slot
-    __builtin_amdgcn_s_barrier();
-    H8_WAIT_A(0)
-    __builtin_amdgcn_sched_barrier(0);
-    H8_MFMA(0, 0, fb0)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- P2: B1 -> acc[0..1][1]; stage B0(t + 2)
-    lds_read_b128<OB + 4096>(fb1[0], kb_[0]); lds_read_b128<OB + 4096>(fb1[1], kb_[1]); lds_read_b128<OB + 4096>(fb1[2], kb_[2]); lds_read_b128<OB + 4096>(fb1[3], kb_[3]);
-    if (t + 2 < n) stage_b(IntC<0>{}, IntC<BUF>{});
-    __builtin_amdgcn_s_barrier();
-    H8_WAIT_B(0, fb1)
-    __builtin_amdgcn_sched_barrier(0);
-    H8_MFMA(0, 1, fb1)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- P3: A rows 64..127 -> acc[2..3][1]; a piece of the next panel
-    lds_read_b128<OA + 8192>(fa[0][0], ka[0]); lds_read_b128<OA + 8192>(fa[0][1], ka[1]); lds_read_b128<OA + 8192>(fa[0][2], ka[2]);
-    lds_read_b128<OA + 8192>(fa[0][3], ka[3]);
-    lds_read_b128<OA + 12288>(fa[1][0], ka[0]); lds_read_b128<OA + 12288>(fa[1][1], ka[1]); lds_read_b128<OA + 12288>(fa[1][2], ka[2]);
-    lds_read_b128<OA + 12288>(fa[1][3], ka[3]);
-    if (more_k) {
-      if (TAP == 0) stage_a(IntC<1>{}, IntC<PANEL ^ 1>{});
-      if (TAP == 1) stage_a(IntC<3>{}, IntC<PANEL ^ 1>{});
-    }
-    __builtin_amdgcn_s_barrier();
-    H8_WAIT_A(0)
-    __builtin_amdgcn_sched_barrier(0);
-    H8_MFMA(2, 1, fb1)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- P4: (B0 still in registers) -> acc[2..3][0]; stage B1(t + 2); B(t + 1) -- at tap 2 also the next panel -- has landed behind the wait
-    if (t + 2 < n) {
-      stage_b(IntC<1>{}, IntC<BUF>{});
-      // younger than B1(t + 1): this tile's panel pieces (taps 0, 1: two) and B0 / B1(t + 2) (two each); tap 2's piece must land too
-      if (TAP < 2 && more_k) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    H8_MFMA(2, 0, fb0)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
+    p8_ktile<PANEL * kPanelBytes, BUF * 32768>(
+        acc, ka, kb_,
+        [&] {
+          if (more_k) {
+            if (TAP == 0) stage_a(IntC<0>{}, IntC<PANEL ^ 1>{});
+            if (TAP == 1) stage_a(IntC<2>{}, IntC<PANEL ^ 1>{});
+            if (TAP == 2 && wave == 0) stage_a(IntC<4>{}, IntC<PANEL ^ 1>{});
+          }
+        },
+        [&] { if (t + 2 < n) stage_b(IntC<0>{}, IntC<BUF>{}); },
+        [&] {
+          if (more_k) {
+            if (TAP == 0) stage_a(IntC<1>{}, IntC<PANEL ^ 1>{});
+            if (TAP == 1) stage_a(IntC<3>{}, IntC<PANEL ^ 1>{});
+          }
+        },
+        [&] {                                                  // B(t + 1) -- at tap 2 also the next panel -- has landed behind the wait
+          if (t + 2 < n) {
+            stage_b(IntC<1>{}, IntC<BUF>{});
+            // younger than B1(t + 1): this tile's panel pieces (taps 0, 1: two) and B0 / B1(t + 2) (two each); tap 2's piece must land too
+            if (TAP < 2 && more_k) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+          } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          }
+        });
   };
 
   // prologue: panel 0, B tiles 0 and 1
@@ -1234,9 +1169,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big8_halo3_kernel(GemmArgs g) 
     tile(IntC<0>{}, IntC<0>{}, IntC<2>{}, 3 * kb + 2, false);
   }
   if (wr == 0) __builtin_amdgcn_s_barrier();
-#undef H8_WAIT_A
-#undef H8_WAIT_B
-#undef H8_MFMA
   gemm_big_epilogue<T>(g, acc, smem, m0, n0, tid, lane, wave, wr, wc);
 }
 
@@ -1427,12 +1359,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(WgradArgs g) {
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int lr = lane & 31, lh = lane >> 5;
   // transposed-read lane roles (ds_read_b64_tr_b16 works per 16-lane group; see cdna_hip_programming.md T10)
@@ -1621,6 +1548,23 @@ __device__ __forceinline__ float bf16x8_sum(u32x2 lo, u32x2 hi, float acc) {
   return bf16x2_sum(w3, bf16x2_sum(w2, bf16x2_sum(w1, bf16x2_sum(w0, acc))));
 }
 
+// What a workgroup of the 512-thread wgrad kernels computes: m-split `split` (rows m_begin .. m_end) of the TILE x TILE output tile at (n1_0, n2_0),
+// for tap t.  `taps` = the taps that have workgroups of their own (g.taps; 1 for the kernels that hold all three taps: t = 0).
+// XCD-aware order (speed only): units are (split, tile) pairs, split-major, and block ids are dealt round-robin to the 8 XCDs: XCD x takes the
+// x-th eighth of the unit list, so the tiles of one m-split -- which re-read the same dY / X rows -- and their taps (ids 8 apart) run back to
+// back on one XCD and meet in its L2.  (The first form, unit = (qid / taps) * 8 + xcd, dealt a split's tiles to eight different L2s: PMC
+// FETCH_SIZE of these launches summed to 4.5 TB/s HBM-side, twice the algorithmic bytes.)
+struct WgradUnit { int split, t, n1_0, n2_0, m_begin, m_end; };
+template <int TILE> __device__ __forceinline__ WgradUnit wgrad_unit(const WgradArgs& g, int taps) {
+  const int tiles_n2 = (g.N2 + TILE - 1) / TILE, tiles_n1 = (g.N1 + TILE - 1) / TILE;
+  const int ntile = tiles_n1 * tiles_n2;
+  const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;
+  const int unit = xcd * (((int)gridDim.x >> 3) / taps) + qid / taps;
+  const int split = unit / ntile, tile = unit % ntile;
+  const int m_begin = split * g.rows_per_split;
+  return {split, qid % taps, (tile / tiles_n2) * TILE, (tile % tiles_n2) * TILE, m_begin, min(g.M, m_begin + g.rows_per_split)};
+}
+
 #define OSUF_TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 
 __global__ __launch_bounds__(512, 2) void gemm_tn_big_kernel(WgradArgs g) {
@@ -1629,21 +1573,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_kernel(WgradArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int tiles_n2 = (g.N2 + kBig - 1) / kBig;
-  const int tiles_n1 = (g.N1 + kBig - 1) / kBig;
-  // XCD-aware order (speed only): the taps of one (split, tile) unit re-read identical dY / X bytes; give them ids 8 apart
-  // so they share one XCD's L2 and run back to back, and deal the units themselves to the 8 XCDs in eighths.
-  const int ntile = tiles_n1 * tiles_n2;
-  const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;
-  // (units are (split, tile) pairs, split-major: XCD x takes the x-th eighth of the list, so the tiles of one m-split -- which re-read the
-  //  same dY / X rows -- and their taps run back to back on one XCD.  The first form, unit = (qid / taps) * 8 + xcd, dealt a split's tiles
-  //  to eight different L2s: PMC FETCH_SIZE of these launches summed to 4.5 TB/s HBM-side, twice the algorithmic bytes.)
-  const int unit = xcd * (((int)gridDim.x >> 3) / g.taps) + qid / g.taps;
-  const int t = qid % g.taps;
-  const int split = unit / ntile, tile = unit % ntile;
-  const int n1_0 = (tile / tiles_n2) * kBig, n2_0 = (tile % tiles_n2) * kBig;
-  const int m_begin = split * g.rows_per_split;
-  const int m_end = min(g.M, m_begin + g.rows_per_split);
+  const WgradUnit u = wgrad_unit<kBig>(g, g.taps);
+  const int split = u.split, t = u.t, n1_0 = u.n1_0, n2_0 = u.n2_0, m_begin = u.m_begin, m_end = u.m_end;
   if (m_begin >= m_end) return;
   const bf16_t* dY = reinterpret_cast<const bf16_t*>(g.dY);
   const bf16_t* X = reinterpret_cast<const bf16_t*>(g.X);
@@ -1692,12 +1623,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_kernel(WgradArgs g) {
   };
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int lr = lane & 31, lh = lane >> 5;
   const int ip = lane & 15, cb = ((lane >> 4) & 1) * 16, tq = ip >> 2, tp = ip & 3;
@@ -1791,16 +1717,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_x3_kernel(WgradArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int tiles_n2 = (g.N2 + kBig - 1) / kBig;
-  const int tiles_n1 = (g.N1 + kBig - 1) / kBig;
-  const int ntile = tiles_n1 * tiles_n2;                        // block -> (split, tile, tap) as in gemm_tn_big_kernel
-  const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;
-  const int unit = xcd * (((int)gridDim.x >> 3) / g.taps) + qid / g.taps;
-  const int t = qid % g.taps;
-  const int split = unit / ntile, tile = unit % ntile;
-  const int n1_0 = (tile / tiles_n2) * kBig, n2_0 = (tile % tiles_n2) * kBig;
-  const int m_begin = split * g.rows_per_split;
-  const int m_end = min(g.M, m_begin + g.rows_per_split);
+  const WgradUnit u = wgrad_unit<kBig>(g, g.taps);
+  const int split = u.split, t = u.t, n1_0 = u.n1_0, n2_0 = u.n2_0, m_begin = u.m_begin, m_end = u.m_end;
   if (m_begin >= m_end) return;
   const float* dY = reinterpret_cast<const float*>(g.dY);
   const float* X = reinterpret_cast<const float*>(g.X);
@@ -1840,12 +1758,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_x3_kernel(WgradArgs g) {
   };
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int lr = lane & 31, lh = lane >> 5;
   issue(m_begin, 0);
@@ -1905,16 +1818,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_taps3_kernel(WgradArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int tiles_n2 = (g.N2 + 127) / 128, tiles_n1 = (g.N1 + 127) / 128;
-  const int ntile = tiles_n1 * tiles_n2;
-  // XCD-aware order (speed only): the tiles of one m-split re-read the same dY / X rows.  Block ids are dealt round-robin to the 8 XCDs, so
-  // XCD x takes the x-th eighth of the (split-major) unit list: a split's tiles run back to back on one XCD and meet in its L2
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int unit = xcd * ((int)gridDim.x >> 3) + local;
-  const int split = unit / ntile, tile = unit % ntile;
-  const int n1_0 = (tile / tiles_n2) * 128, n2_0 = (tile % tiles_n2) * 128;
-  const int m_begin = split * g.rows_per_split;
-  const int m_end = min(g.M, m_begin + g.rows_per_split);
+  const WgradUnit u = wgrad_unit<128>(g, 1);
+  const int split = u.split, n1_0 = u.n1_0, n2_0 = u.n2_0, m_begin = u.m_begin, m_end = u.m_end;
   if (m_begin >= m_end) return;
   const bf16_t* dY = reinterpret_cast<const bf16_t*>(g.dY);
   const bf16_t* X = reinterpret_cast<const bf16_t*>(g.X);
@@ -1955,12 +1860,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_taps3_kernel(WgradArgs g) {
   };
 
   f32x16 acc[2][3];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][t][r] = 0.f;
+  zero_acc(acc);
 
   const int lr = lane & 31, lh = lane >> 5;
   const int ip = lane & 15, cb = ((lane >> 4) & 1) * 16, tq = ip >> 2, tp = ip & 3;
@@ -2077,16 +1977,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_taps3_x3_kernel(WgradArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int tiles_n2 = (g.N2 + 127) / 128, tiles_n1 = (g.N1 + 127) / 128;
-  const int ntile = tiles_n1 * tiles_n2;
-  // XCD-aware order (speed only): the tiles of one m-split re-read the same dY / X rows.  Block ids are dealt round-robin to the 8 XCDs, so
-  // XCD x takes the x-th eighth of the (split-major) unit list: a split's tiles run back to back on one XCD and meet in its L2
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int unit = xcd * ((int)gridDim.x >> 3) + local;
-  const int split = unit / ntile, tile = unit % ntile;
-  const int n1_0 = (tile / tiles_n2) * 128, n2_0 = (tile % tiles_n2) * 128;
-  const int m_begin = split * g.rows_per_split;
-  const int m_end = min(g.M, m_begin + g.rows_per_split);
+  const WgradUnit u = wgrad_unit<128>(g, 1);
+  const int split = u.split, n1_0 = u.n1_0, n2_0 = u.n2_0, m_begin = u.m_begin, m_end = u.m_end;
   if (m_begin >= m_end) return;
   const float* dY = reinterpret_cast<const float*>(g.dY);
   const float* X = reinterpret_cast<const float*>(g.X);
@@ -2121,12 +2013,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_taps3_x3_kernel(WgradArgs g) {
   };
 
   f32x16 acc[2][3];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][t][r] = 0.f;
+  zero_acc(acc);
 
   const int lr = lane & 31, lh = lane >> 5;
   issue(m_begin, 0);
@@ -2189,9 +2076,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_taps3_x3_kernel(WgradArgs g) {
   }
 }
 
-// deterministic second stage of the split wgrad: dW (+)= sum_s ws[s][t][i], i = n1*N2 + n2.
-// LAYOUT 0: dW[t][i] (the kernel's own order)   LAYOUT 1: dW[i][t] = torch's (Cout, Cin, k) conv weight layout -- the permute
-// is free here: a thread owns one i and writes its `taps` values contiguously.
 // ---------------------------------------------------------------------------------------------------------
 // Skinny wgrad (N2 <= 32: the rank-r LoRA gradients dB = dy^T u and, with the operands' roles swapped, dA^T = x^T du): a 256 (n1) x
 // 32 (n2) output tile per workgroup, 8 waves x one 32x32 MFMA tile, split over m with fp32 atomics into the small result
@@ -2315,6 +2199,9 @@ __device__ __forceinline__ f32x4 sum_partials(const float* p, long stride, int s
   return (a0 + a1) + (a2 + a3);
 }
 
+// deterministic second stage of the split wgrad: dW (+)= sum_s ws[s][t][i], i = n1*N2 + n2.
+// LAYOUT 0: dW[t][i] (the kernel's own order)   LAYOUT 1: dW[i][t] = torch's (Cout, Cin, k) conv weight layout -- the permute
+// is free here: a thread owns one i and writes its `taps` values contiguously.
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, float* dW, long n12, int taps, int splits, int accumulate) {
   if constexpr (LAYOUT == 0) {
@@ -2529,37 +2416,18 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* Y, long ldy, int M
 // ---------------------------------------------------------------------------------------------------------
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// lets KERNEL be launched with `bytes` of dynamic LDS (more than the 64 KiB default); takes effect once per kernel
+template <auto KERNEL> static void allow_lds(int bytes) {
+  static const bool once = ((void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), true);
+  (void)once;
+}
+
 // OSUF_GEMM_BIG_MIN_TILES overrides when the 256^2 kernels are picked (tests: 1 forces them, 0 / "off" rules them out).  Read on
 // every call: tests flip it between calls.
 static std::optional<long> big_min_tiles_override() {
   const char* s = getenv("OSUF_GEMM_BIG_MIN_TILES");
   if (!s) return std::nullopt;
   return atol(s);
-}
-
-static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, long ldw, long tapstride,
-                          void* C, long ldc, void* C2, long ldc2, const void* R, long ldr, const void* U, long ldu,
-                          const float* bias, const float* rscale, double* stats,
-                          int M, int N, int K, int taps, int Lin, int Lout, int stride, int pad, int mode, int act,
-                          float* delta, int heads, hipStream_t stream);
-
-extern "C" int osuf_gemm_nt(int dtype, const void* A, long lda, const void* W, long ldw, long tapstride,
-                            void* C, long ldc, void* C2, long ldc2, const void* R, long ldr, const void* U, long ldu,
-                            const float* bias, const float* rscale, double* stats,
-                            int M, int N, int K, int taps, int Lin, int Lout, int stride, int pad, int mode, int act,
-                            hipStream_t stream) {
-  return gemm_nt_launch(dtype, A, lda, W, ldw, tapstride, C, ldc, C2, ldc2, R, ldr, U, ldu, bias, rscale, stats, M, N, K, taps, Lin, Lout,
-                        stride, pad, mode, act, nullptr, 0, stream);
-}
-
-// C = A W^T (one tap, no bias) and, from the same epilogue, delta[b][h][l] = sum_{d < 64} bf16(C[b*L + l][h*64 + d]) * O[b*L + l][h*64 + d]:
-// the to_out input-gradient GEMM of the attention block hands the flash backward its row constants (sum_d dO * O) without a
-// second pass over dO and O.  N = heads * 64; M % L == 0.
-extern "C" int osuf_gemm_nt_rowdot(int dtype, const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* O, long ldo,
-                                   float* delta, int M, int N, int K, int L, int heads, hipStream_t stream) {
-  if (!O || !delta || heads <= 0 || N != heads * 64 || L <= 0 || !aligned16(O) || ldo % 8) return OSUF_EINVAL;
-  return gemm_nt_launch(dtype, A, lda, W, ldw, 0, C, ldc, nullptr, 0, O, ldo, nullptr, 0, nullptr, nullptr, nullptr, M, N, K, 1, L, L, 1, 0, 0, 0,
-                        delta, heads, stream);
 }
 
 static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, long ldw, long tapstride,
@@ -2584,18 +2452,13 @@ static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, lon
   g.act = act;
   const int grid = ((M + kTile - 1) / kTile) * ((N + kTile - 1) / kTile);
   const int lds = 2 * kStageBytes + 512;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_glds_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_glds_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)(gemm_nt_glds_kernel<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  allow_lds<gemm_nt_glds_kernel<bf16_t>>(lds);
+  allow_lds<gemm_nt_glds_kernel<float>>(lds);
+  allow_lds<gemm_nt_glds_kernel<float, true>>(lds);
   if (dtype == OSUF_DT_BF16 && N <= 32 && N % 8 == 0 && ldc % 8 == 0 && M >= 4096 && !C2 && !R && !U && !bias && !rscale && !stats &&
       act == 0) {
     const int lds_sk = 2 * kSkStage;
-    static bool sk_attr = ((void)hipFuncSetAttribute((const void*)gemm_nt_skinny_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_sk), true);
-    (void)sk_attr;
+    allow_lds<gemm_nt_skinny_kernel>(lds_sk);
     hipLaunchKernelGGL(gemm_nt_skinny_kernel, dim3((M + kBig - 1) / kBig), dim3(512), lds_sk, stream, g);
     return osuf_launch_status();
   }
@@ -2609,32 +2472,24 @@ static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, lon
   if (use_big) {
     const int lds_big = 2 * kBigStage + 2112;          // ring + per-tile GroupNorm stat slots (2 x 258 floats)
     const int lds_p8 = kP8Tbl + taps * kBig * 4;
-    static bool big_attr = false;
-    if (!big_attr) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_big_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-      (void)hipFuncSetAttribute((const void*)(gemm_nt_big_kernel<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-      big_attr = true;
-    }
+    allow_lds<gemm_nt_big_kernel<bf16_t>>(lds_big);
+    allow_lds<gemm_nt_big_kernel<float, true>>(lds_big);
     const long tm = (M + kBig - 1) / kBig, tn = (N + kBig - 1) / kBig;
     const dim3 grid_big((int)(((tm + 7) / 8) * 8 * tn));
     const bool halo3 = taps == 3 && mode == 0 && stride == 1 && pad == 1 && Lin == Lout && Lout % kBig == 0 && K % (dtype == OSUF_DT_BF16 ? 64 : 32) == 0 &&
                        getenv("OSUF_GEMM_NOHALO") == nullptr;
     if (halo3) {
-      static bool halo_attr = ((void)hipFuncSetAttribute((const void*)gemm_nt_big_halo3_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big),
-                               (void)hipFuncSetAttribute((const void*)gemm_nt_big_halo3_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big), true);
-      (void)halo_attr;
+      allow_lds<gemm_nt_big_halo3_kernel<bf16_t>>(lds_big);
+      allow_lds<gemm_nt_big_halo3_kernel<float>>(lds_big);
       if (dtype == OSUF_DT_BF16 && getenv("OSUF_GEMM_NO8P") == nullptr && K <= 8192) {
         const int lds_h8 = kH8B + 65536 + 2112;
-        static bool h8_attr = ((void)hipFuncSetAttribute((const void*)gemm_nt_big8_halo3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_h8), true);
-        (void)h8_attr;
+        allow_lds<gemm_nt_big8_halo3_kernel>(lds_h8);
         hipLaunchKernelGGL(gemm_nt_big8_halo3_kernel, grid_big, dim3(512), lds_h8, stream, g);
       } else if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL(gemm_nt_big_halo3_kernel<bf16_t>, grid_big, dim3(512), lds_big, stream, g);
       else hipLaunchKernelGGL(gemm_nt_big_halo3_kernel<float>, grid_big, dim3(512), lds_big, stream, g);
     } else if (dtype == OSUF_DT_BF16 && getenv("OSUF_GEMM_NO8P") == nullptr && taps <= kP8MaxTaps && K <= 8192 && K % 64 == 0) {
       // (the 8-phase loop; OSUF_GEMM_NO8P=1 = the one-barrier-per-K-step loop above, for A/B runs and for K % 64 != 0 / more than 16 taps)
-      const int lds_p8_max = kP8Tbl + kP8MaxTaps * kBig * 4;
-      static bool p8_attr = ((void)hipFuncSetAttribute((const void*)gemm_nt_big8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_p8_max), true);
-      (void)p8_attr;
+      allow_lds<gemm_nt_big8_kernel>(kP8Tbl + kP8MaxTaps * kBig * 4);       // once, so for the most taps a launch can have
       hipLaunchKernelGGL(gemm_nt_big8_kernel, grid_big, dim3(512), lds_p8, stream, g);
     } else if (dtype == OSUF_DT_F32X3) hipLaunchKernelGGL((gemm_nt_big_kernel<float, true>), grid_big, dim3(512), lds_big, stream, g);
     else hipLaunchKernelGGL(gemm_nt_big_kernel<bf16_t>, grid_big, dim3(512), lds_big, stream, g);
@@ -2644,6 +2499,25 @@ static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, lon
     else hipLaunchKernelGGL(gemm_nt_glds_kernel<float>, dim3(grid), dim3(256), lds, stream, g);
   }
   return osuf_launch_status();
+}
+
+extern "C" int osuf_gemm_nt(int dtype, const void* A, long lda, const void* W, long ldw, long tapstride,
+                            void* C, long ldc, void* C2, long ldc2, const void* R, long ldr, const void* U, long ldu,
+                            const float* bias, const float* rscale, double* stats,
+                            int M, int N, int K, int taps, int Lin, int Lout, int stride, int pad, int mode, int act,
+                            hipStream_t stream) {
+  return gemm_nt_launch(dtype, A, lda, W, ldw, tapstride, C, ldc, C2, ldc2, R, ldr, U, ldu, bias, rscale, stats, M, N, K, taps, Lin, Lout,
+                        stride, pad, mode, act, nullptr, 0, stream);
+}
+
+// C = A W^T (one tap, no bias) and, from the same epilogue, delta[b][h][l] = sum_{d < 64} bf16(C[b*L + l][h*64 + d]) * O[b*L + l][h*64 + d]:
+// the to_out input-gradient GEMM of the attention block hands the flash backward its row constants (sum_d dO * O) without a
+// second pass over dO and O.  N = heads * 64; M % L == 0.
+extern "C" int osuf_gemm_nt_rowdot(int dtype, const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* O, long ldo,
+                                   float* delta, int M, int N, int K, int L, int heads, hipStream_t stream) {
+  if (!O || !delta || heads <= 0 || N != heads * 64 || L <= 0 || !aligned16(O) || ldo % 8) return OSUF_EINVAL;
+  return gemm_nt_launch(dtype, A, lda, W, ldw, 0, C, ldc, nullptr, 0, O, ldo, nullptr, 0, nullptr, nullptr, nullptr, M, N, K, 1, L, L, 1, 0, 0, 0,
+                        delta, heads, stream);
 }
 
 // split plan of the 256x256 wgrad kernel: rows of m per split and number of splits (one workgroup per CU, ~1.25 rounds)
@@ -2677,7 +2551,19 @@ static bool wgrad_pk(int dtype, int N1, int N2) {
   return dtype == OSUF_DT_BF16 && (N1 % 2) == 0 && (N2 % 4) == 0 && getenv("OSUF_WGRAD_F32_PARTIALS") == nullptr;
 }
 
-extern "C" int osuf_colsum(int dtype, const void* Y, long ldy, int M, int N, float* out, hipStream_t stream);
+extern "C" int osuf_colsum(int dtype, const void* Y, long ldy, int M, int N, float* out, hipStream_t stream) {
+  if (M <= 0 || N <= 0 || N % 8 || ldy % 8 || !aligned16(Y)) return OSUF_EINVAL;
+  const int rows_per_block = 256;
+  dim3 grid((N + 255) / 256, (M + rows_per_block - 1) / rows_per_block);
+  if (dtype == OSUF_DT_BF16) {
+    hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)Y, ldy, M, N, out, rows_per_block);
+  } else if (dtype == OSUF_DT_F32) {
+    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, stream, (const float*)Y, ldy, M, N, out, rows_per_block);
+  } else {
+    return OSUF_EUNSUPPORTED;
+  }
+  return osuf_launch_status();
+}
 
 // dbias (optional): += the column sums of dY (the bias gradient of the layer).  The bf16 256x256 and merged-taps kernels take them from the
 // dY fragments they hold anyway; every other path runs osuf_colsum on dY.
@@ -2696,11 +2582,29 @@ static int gemm_tn_launch(int dtype, const void* dY, long ldy, const void* X, lo
   auto bias_by_colsum = [&]() -> int {                       // paths whose kernel does not produce the sums
     return dbias ? osuf_colsum(dtype == OSUF_DT_BF16 ? OSUF_DT_BF16 : OSUF_DT_F32, dY, ldy, M, N1, dbias, stream) : OSUF_OK;
   };
+  auto wgrad_args = [&](int rows_per_split) {               // for the atomic path; plan_partials fills in ws / ws_pk / dbias
+    WgradArgs a{};
+    a.dY = dY; a.X = X; a.dW = dW; a.es = es; a.ldy = ldy; a.ldx = ldx; a.ldw = ldw; a.tapstride = tapstride;
+    a.M = M; a.N1 = N1; a.N2 = N2; a.taps = taps; a.rm = RowMap{Lin, Lout, stride, pad, mode};
+    a.rows_per_split = rows_per_split;
+    return a;
+  };
+  // The 512-thread kernels, sp splits: may this launch leave partial tiles in the caller's workspace (a dense dW the reduce kernels can write
+  // with 16-byte stores, and room for sp fp32 copies of it)?  Otherwise it adds into dW with atomics, which needs zeros.  Only the bf16 kernels
+  // produce the bias gradient themselves.
+  auto plan_partials = [&](WgradArgs& gb, int sp) -> int {
+    const long n = (long)taps * N1 * N2;
+    const bool dense = (out_layout == 1 && ((long)N1 * N2) % 4 == 0) ||
+                       (out_layout == 0 && ldw == N2 && (taps == 1 || tapstride == (long)N1 * N2) && n % 4 == 0 && aligned16(dW));
+    gb.ws = (workspace && dense && aligned16(workspace) && workspace_bytes >= (long)sp * n * (long)sizeof(float)) ? workspace : nullptr;
+    gb.ws_pk = gb.ws && wgrad_pk(dtype, N1, N2);
+    gb.dbias = dtype == OSUF_DT_BF16 ? dbias : nullptr;
+    if (dtype != OSUF_DT_BF16) { if (int rc = bias_by_colsum()) return rc; }
+    if (!gb.ws && !accumulate) (void)hipMemsetAsync(dW, 0, (size_t)n * sizeof(float), stream);
+    return OSUF_OK;
+  };
   const int bkm = dtype == OSUF_DT_BF16 ? 64 : 32;
   if (splits <= 0 && dtype == OSUF_DT_BF16 && N2 <= 32 && M >= 4096) {
-    WgradArgs gs{};
-    gs.dY = dY; gs.X = X; gs.dW = dW; gs.ws = nullptr; gs.es = es; gs.ldy = ldy; gs.ldx = ldx; gs.ldw = ldw; gs.tapstride = tapstride;
-    gs.M = M; gs.N1 = N1; gs.N2 = N2; gs.taps = taps; gs.rm = RowMap{Lin, Lout, stride, pad, mode};
     const int tiles_n1 = (N1 + kBig - 1) / kBig;
     int sp = 512 / (tiles_n1 * taps);                                  // 2 workgroups per CU, and not one workgroup more than that
     if (sp < 1) sp = 1;                                                // (rounding up gave 171 x 3 = 513: a second round for one block)
@@ -2708,14 +2612,13 @@ static int gemm_tn_launch(int dtype, const void* dY, long ldy, const void* X, lo
     rows = ((rows + 63) / 64) * 64;
     if (rows < 256) rows = 256;
     sp = (M + rows - 1) / rows;
-    gs.rows_per_split = rows;
+    WgradArgs gs = wgrad_args(rows);
     if (!accumulate) {
       if (out_layout == 0 && !(ldw == N2 && (taps == 1 || tapstride == (long)N1 * N2))) return OSUF_EINVAL;
       (void)hipMemsetAsync(dW, 0, (size_t)taps * N1 * N2 * sizeof(float), stream);
     }
     const int lds_sk = 2 * (64 * 512 + 64 * 64);
-    static bool sk_attr = ((void)hipFuncSetAttribute((const void*)gemm_tn_skinny_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_sk), true);
-    (void)sk_attr;
+    allow_lds<gemm_tn_skinny_kernel>(lds_sk);
     hipLaunchKernelGGL(gemm_tn_skinny_kernel, dim3(tiles_n1 * taps * sp), dim3(512), lds_sk, stream, gs);
     if (int rc = bias_by_colsum()) return rc;
     return osuf_launch_status();
@@ -2729,22 +2632,11 @@ static int gemm_tn_launch(int dtype, const void* dY, long ldy, const void* X, lo
     int rows = (M + sp - 1) / sp;
     rows = ((rows + 127) / 128) * 128;
     sp = (M + rows - 1) / rows;
-    WgradArgs gb{};
-    gb.dY = dY; gb.X = X; gb.dW = dW; gb.ldy = ldy; gb.ldx = ldx; gb.ldw = ldw; gb.tapstride = tapstride;
-    gb.M = M; gb.N1 = N1; gb.N2 = N2; gb.taps = taps; gb.rm = RowMap{Lin, Lout, stride, pad, mode};
-    gb.rows_per_split = rows;
-    const long n = (long)taps * N1 * N2;
-    const bool dense = (out_layout == 1 && ((long)N1 * N2) % 4 == 0) || (out_layout == 0 && ldw == N2 && tapstride == (long)N1 * N2 && n % 4 == 0 && aligned16(dW));
-    gb.ws = (workspace && dense && aligned16(workspace) && workspace_bytes >= (long)sp * n * (long)sizeof(float)) ? workspace : nullptr;
-    gb.es = es;
-    gb.ws_pk = gb.ws && wgrad_pk(dtype, N1, N2);
-    gb.dbias = dtype == OSUF_DT_BF16 ? dbias : nullptr;
-    if (dtype != OSUF_DT_BF16) { if (int rc = bias_by_colsum()) return rc; }
-    if (!gb.ws && !accumulate) (void)hipMemsetAsync(dW, 0, (size_t)n * sizeof(float), stream);    // atomic path needs zeros
+    WgradArgs gb = wgrad_args(rows);
+    if (int rc = plan_partials(gb, sp)) return rc;
     const int lds_t3 = 2 * (128 * 256 + 132 * 256);
-    static bool t3_attr = ((void)hipFuncSetAttribute((const void*)gemm_tn_taps3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_t3),
-                           (void)hipFuncSetAttribute((const void*)gemm_tn_taps3_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_t3), true);
-    (void)t3_attr;
+    allow_lds<gemm_tn_taps3_kernel>(lds_t3);
+    allow_lds<gemm_tn_taps3_x3_kernel>(lds_t3);
     const dim3 grid_t3(((sp * btiles + 7) / 8) * 8);
     if (dtype == OSUF_DT_F32X3) hipLaunchKernelGGL(gemm_tn_taps3_x3_kernel, grid_t3, dim3(512), lds_t3, stream, gb);
     else hipLaunchKernelGGL(gemm_tn_taps3_kernel, grid_t3, dim3(512), lds_t3, stream, gb);
@@ -2754,26 +2646,12 @@ static int gemm_tn_launch(int dtype, const void* dY, long ldy, const void* X, lo
   {
     int rows, sp;
     if (splits <= 0 && tn_big_plan(dtype, M, N1, N2, taps, &rows, &sp)) {
-      WgradArgs gb{};
-      gb.dY = dY; gb.X = X; gb.dW = dW; gb.ldy = ldy; gb.ldx = ldx; gb.ldw = ldw; gb.tapstride = tapstride;
-      gb.M = M; gb.N1 = N1; gb.N2 = N2; gb.taps = taps; gb.rm = RowMap{Lin, Lout, stride, pad, mode};
-      gb.rows_per_split = rows;
-      const long n = (long)taps * N1 * N2;
-      const bool dense = (out_layout == 1 && ((long)N1 * N2) % 4 == 0) || (out_layout == 0 && ldw == N2 && (taps == 1 || tapstride == (long)N1 * N2) && n % 4 == 0 && aligned16(dW));
-      gb.ws = (workspace && dense && aligned16(workspace) && workspace_bytes >= (long)sp * n * (long)sizeof(float)) ? workspace : nullptr;
-      gb.es = es;
-      gb.ws_pk = gb.ws && wgrad_pk(dtype, N1, N2);
-      gb.dbias = dtype == OSUF_DT_BF16 ? dbias : nullptr;
-      if (dtype != OSUF_DT_BF16) { if (int rc = bias_by_colsum()) return rc; }
-      if (!gb.ws && !accumulate) (void)hipMemsetAsync(dW, 0, (size_t)n * sizeof(float), stream);    // atomic path needs zeros
+      WgradArgs gb = wgrad_args(rows);
+      if (int rc = plan_partials(gb, sp)) return rc;
       const int btiles = ((N1 + kBig - 1) / kBig) * ((N2 + kBig - 1) / kBig);
       const int lds_big = 2 * 65536;
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void*)gemm_tn_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-        (void)hipFuncSetAttribute((const void*)gemm_tn_big_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-        attr = true;
-      }
+      allow_lds<gemm_tn_big_kernel>(lds_big);
+      allow_lds<gemm_tn_big_x3_kernel>(lds_big);
       if (dtype == OSUF_DT_F32X3) hipLaunchKernelGGL(gemm_tn_big_x3_kernel, dim3(((sp * btiles + 7) / 8) * 8 * taps), dim3(512), lds_big, stream, gb);
       else hipLaunchKernelGGL(gemm_tn_big_kernel, dim3(((sp * btiles + 7) / 8) * 8 * taps), dim3(512), lds_big, stream, gb);
       if (gb.ws) launch_wgrad_reduce(gb, dW, N1, N2, taps, sp, out_layout, accumulate, out_layout == 0 || taps == 3, stream);
@@ -2787,12 +2665,7 @@ static int gemm_tn_launch(int dtype, const void* dY, long ldy, const void* X, lo
   int rows = (M + splits - 1) / splits;
   rows = ((rows + bkm - 1) / bkm) * bkm;
   splits = (M + rows - 1) / rows;
-  WgradArgs g{};
-  g.dY = dY; g.X = X; g.dW = dW; g.ldy = ldy; g.ldx = ldx; g.ldw = ldw; g.tapstride = tapstride;
-  g.M = M; g.N1 = N1; g.N2 = N2; g.taps = taps; g.rm = RowMap{Lin, Lout, stride, pad, mode};
-  g.rows_per_split = rows;
-  g.ws = nullptr;
-  g.es = es;
+  const WgradArgs g = wgrad_args(rows);
   if (!accumulate) {
     if (out_layout == 0 && !(ldw == N2 && (taps == 1 || tapstride == (long)N1 * N2))) return OSUF_EINVAL;   // needs a dense dW to clear
     (void)hipMemsetAsync(dW, 0, (size_t)taps * N1 * N2 * sizeof(float), stream);
@@ -2825,18 +2698,4 @@ extern "C" int osuf_gemm_tn_bias(int dtype, const void* dY, long ldy, const void
   if (!dbias) return OSUF_EINVAL;
   return gemm_tn_launch(dtype, dY, ldy, X, ldx, dW, ldw, tapstride, M, N1, N2, taps, Lin, Lout, stride, pad, mode, splits, out_layout, accumulate,
                         workspace, workspace_bytes, dbias, stream);
-}
-
-extern "C" int osuf_colsum(int dtype, const void* Y, long ldy, int M, int N, float* out, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || N % 8 || ldy % 8 || !aligned16(Y)) return OSUF_EINVAL;
-  const int rows_per_block = 256;
-  dim3 grid((N + 255) / 256, (M + rows_per_block - 1) / rows_per_block);
-  if (dtype == OSUF_DT_BF16) {
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)Y, ldy, M, N, out, rows_per_block);
-  } else if (dtype == OSUF_DT_F32) {
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, stream, (const float*)Y, ldy, M, N, out, rows_per_block);
-  } else {
-    return OSUF_EUNSUPPORTED;
-  }
-  return osuf_launch_status();
 }
