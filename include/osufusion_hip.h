@@ -43,8 +43,7 @@ extern "C" {
                                      OSUF_DQ_ATOMIC_512; whole 512-key blocks and an even number of (head, query block) pairs per part */
 #define OSUF_DQ_PREZEROED 0x100   /* flag, OR-ed into an atomic dq_mode: the dQ accumulator at the head of `workspace` was zero-filled by
                                      osuf_mqa_fwd_zdq of the same layer (the entry point then issues no memset) */
-#define OSUF_DQ_TIMING_512 4      /* DEBUG: the 512-key sweep WITHOUT its atomics (prices the loop; dq comes back zero) -- refused with
-                                     OSUF_EUNSUPPORTED unless the process environment holds OSUF_ALLOW_TIMING_BUILDS=1 */
+                                  /* (4 was a timing-only build of the 512-key sweep, since removed: refused with OSUF_EINVAL) */
 
 int osuf_version(void);
 

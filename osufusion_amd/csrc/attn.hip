@@ -67,6 +67,12 @@ __device__ __forceinline__ bf16x8 acc_to_frag(const f32x16& a, int sub) {
   return __builtin_convertvector(v, bf16x8);
 }
 
+__device__ __forceinline__ void zero_acc(f32x16& a) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) a[r] = 0.f;
+}
+__device__ __forceinline__ void zero_acc(f32x16 (&a)[2]) { zero_acc(a[0]); zero_acc(a[1]); }
+
 // Epilogue of the backward kernels: one row's 64 gradient values (acc[0]: d < 32, acc[1]: d >= 32, this lane holding
 // d = 8g + 4*(lane>>5) + e of each half) times `mul`, optionally mapped through the transpose of the RoPE rotation
 // (apply_rotary_pos_emb, attention.py:52-58: y1 = x1 c - x2 s, y2 = x2 c + x1 s  =>  dx1 = dy1 c + dy2 s, dx2 = dy2 c - dy1 s),
@@ -101,11 +107,7 @@ __device__ __forceinline__ void store_grad(void* base, long ld, long m, int col0
   else store_grad_row(reinterpret_cast<float*>(base) + m * ld + col0, acc, mul, cs, sn, lh);
 }
 
-#ifdef OSUF_FWD_TRIAGE_NOEXP
-__device__ __forceinline__ float fast_exp2(float x) { return x * 0.001f; }     // timing-only triage builds (tools/build_fwd_triage.sh): never in the product
-#else
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-#endif
 
 struct AttnArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v;
@@ -290,9 +292,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void mqa_fwd_kernel(AttnA
     constexpr bool MASK = decltype(mask_tag)::value;
     const char* ks_ = smem + (j & 1) * 16384;
     const char* vs_ = ks_ + 8192;
-#ifndef OSUF_FWD_TRIAGE_NOLOAD
     if (j + 1 < ntiles) st.template load<WHOLE>(a, (j + 1) * 64);
-#endif
     // S^T = K Q^T  (two 32-key tiles)
     f32x16 s[2];
 #pragma unroll
@@ -389,12 +389,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void mqa_fwd_kernel(AttnA
       for (int dt = 0; dt < 2; ++dt)
         o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_tr_frag(vs_, lo, (s4 >> 1) * 32 + (s4 & 1) * 16, dt), pf, o[dt], 0, 0, 0);
     }
-#ifndef OSUF_FWD_TRIAGE_NOLOAD
     if (j + 1 < ntiles) st.store(smem + ((j + 1) & 1) * 16384, smem + ((j + 1) & 1) * 16384 + 8192, tid);
-#endif
-#ifndef OSUF_FWD_TRIAGE_NOBARRIER
     __syncthreads();
-#endif
   };
   const bool ragged = !WHOLE && (a.N & 63) != 0;
   const int nfull = ragged ? ntiles - 1 : ntiles;                   // one unmasked copy of the tile body: with a loop AND a peeled unmasked twin
@@ -440,24 +436,22 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void mqa_fwd_kernel(AttnA
 }
 
 // ------------------------------------------------------------------------------------------------------
-// backward, dQ: query-stationary.  dQ^T[d][q] = sum_key K^T[d][key] * dS^T[key][q]
+// pieces the backward kernels share
 // ------------------------------------------------------------------------------------------------------
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void mqa_bwd_dq_kernel(AttnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 31, lh = lane >> 5;
-  const int b = blockIdx.y;
-  const int nqb = (a.N + 31) >> 5;
-  const int vb = blockIdx.x * NW + wave;
-  const bool active = vb < nqb * a.H;
-  const int h = active ? vb % a.H : 0, pb = active ? vb / a.H : 0;
-  const int qrow = pb * 32 + lr;
-  const bool qok = active && qrow < a.N;
-  const float c = a.cexp;
-
+// Query-stationary waves (the dQ kernels): wave vb of the sample = (head h, 32-query block pb), a lane = one query row.  The row's Q / dO
+// fragments stay in registers for the whole key loop; a row beyond N has zero fragments and lse = +inf (P = dS = 0).
+struct QueryRow {
+  int h, qrow;
+  bool qok;
   bf16x8 qf[4], dof[4];
-  {
+  float L2, dl;                                   // lse2 and delta of the row
+  __device__ __forceinline__ QueryRow(const AttnArgs& a, int b, int vb, int lr, int lh) {
+    const int nqb = (a.N + 31) >> 5;
+    const bool active = vb < nqb * a.H;
+    h = active ? vb % a.H : 0;
+    const int pb = active ? vb / a.H : 0;
+    qrow = pb * 32 + lr;
+    qok = active && qrow < a.N;
     const bf16_t* qp = a.q + ((long)b * a.N + qrow) * a.ldq + h * D;
     const bf16_t* dp = a.dout + ((long)b * a.N + qrow) * a.lddo + h * D;
 #pragma unroll
@@ -467,15 +461,78 @@ __global__ __launch_bounds__(NW * 64) void mqa_bwd_dq_kernel(AttnArgs a) {
       qf[ks] = __builtin_bit_cast(bf16x8, z);
       dof[ks] = __builtin_bit_cast(bf16x8, z2);
     }
+    const long sidx = ((long)b * a.H + h) * a.N + qrow;
+    L2 = qok ? a.lse2[sidx] : INFINITY;
+    dl = qok ? a.delta[sidx] : 0.f;
   }
-  const long sidx = ((long)b * a.H + h) * a.N + qrow;
-  const float L2 = qok ? a.lse2[sidx] : INFINITY;
-  const float dl = qok ? a.delta[sidx] : 0.f;
+};
+
+// Key-stationary workgroups (the dK/dV and fused kernels): blockIdx.x -> (query part, sample b, key block kb of `keys` keys) and the part's
+// (head, 32-query block) pairs.  a.qsplit parts of gridDim.x / a.qsplit workgroups each (a multiple of 8); nqb = the 32-query blocks swept.
+// XCD-aware order inside a part (speed only): every key block of a sample sweeps the same Q / dO / lse / delta; block ids are dealt
+// round-robin over the 8 XCDs, so ids 8 apart share an L2.  PMC before this remap: 4.46 GB fetched per launch at
+// N=4096 against 0.54 GB of distinct Q + dO bytes.
+struct KeyBlock {
+  int b, kb, part, qb_begin, qb_end, niter;
+  bool empty;                                     // uniform per workgroup: return before any barrier
+  __device__ __forceinline__ KeyBlock(const AttnArgs& a, int keys, int nqb) {
+    const int nkb = (a.N + keys - 1) / keys;
+    const int per_split = (int)gridDim.x / a.qsplit;
+    part = (int)blockIdx.x / per_split;
+    const int bid = (int)blockIdx.x - part * per_split;
+    const int xcd = bid & 7, qid = bid >> 3;
+    b = (qid / nkb) * 8 + xcd;
+    kb = qid % nkb;
+    const int qb_per = (nqb + a.qsplit - 1) / a.qsplit;
+    qb_begin = part * qb_per; qb_end = min(nqb, qb_begin + qb_per);
+    niter = (qb_end - qb_begin) * a.H;
+    empty = b >= a.B || qb_begin >= qb_end;
+  }
+};
+
+// K / V rows of a wave's 32-key tile as MFMA fragments (this lane: row `key`, zero beyond N); with kimg the K row also goes to row img_row of
+// the workgroup's resident K image
+__device__ __forceinline__ void load_kv_frags(const AttnArgs& a, int b, int key, int lh, bf16x8 (&kf)[4], bf16x8 (&vf)[4], char* kimg = nullptr,
+                                              int img_row = 0) {
+  const long m = (long)b * a.N + key;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    u32x4 z = {0u, 0u, 0u, 0u}, z2 = {0u, 0u, 0u, 0u};
+    if (key < a.N) { z = *reinterpret_cast<const u32x4*>(a.k + m * a.ldk + 16 * ks + 8 * lh); z2 = *reinterpret_cast<const u32x4*>(a.v + m * a.ldv + 16 * ks + 8 * lh); }
+    kf[ks] = __builtin_bit_cast(bf16x8, z);
+    vf[ks] = __builtin_bit_cast(bf16x8, z2);
+    if (kimg != nullptr) *reinterpret_cast<u32x4*>(kimg + tile_off(img_row, (2 * ks + lh) * 16)) = z;
+  }
+}
+
+// dK^T / dV^T of key row `key`: with a query split this part's partial sums, plain 16-byte stores into the workspaces that dkv_finish_kernel adds
+// up (atomics measured as slow as the iterations the split saves: 38 G atomics/s); otherwise the final rows
+__device__ __forceinline__ void store_dkv(const AttnArgs& a, int part, int b, int key, int lh, const f32x16 (&dk)[2], const f32x16 (&dv)[2]) {
+  if (a.qsplit > 1) {
+    const long prow = ((long)part * a.B + b) * a.N + key;
+    store_grad_row(a.wsk + prow * D, dk, 1.f, nullptr, nullptr, lh);
+    store_grad_row(a.wsv + prow * D, dv, 1.f, nullptr, nullptr, lh);
+  } else {
+    store_grad(a.dk, a.lddk, (long)b * a.N + key, 0, a.g_bf16, dk, a.kmul, a.rcos, a.rsin, key, lh);
+    store_grad(a.dv, a.lddk, (long)b * a.N + key, 0, a.g_bf16, dv, 1.f, nullptr, nullptr, key, lh);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// backward, dQ: query-stationary.  dQ^T[d][q] = sum_key K^T[d][key] * dS^T[key][q]
+// ------------------------------------------------------------------------------------------------------
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void mqa_bwd_dq_kernel(AttnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lr = lane & 31, lh = lane >> 5;
+  const int b = blockIdx.y;
+  const float c = a.cexp;
+  const QueryRow w(a, b, blockIdx.x * NW + wave, lr, lh);
+  const bf16x8 (&qf)[4] = w.qf, (&dof)[4] = w.dof;
+  const float L2 = w.L2, dl = w.dl;
   f32x16 acc[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  zero_acc(acc);
 
   const LaneOffs lo(lane);
   const int ntiles = (a.N + 63) >> 6;
@@ -516,7 +573,7 @@ __global__ __launch_bounds__(NW * 64) void mqa_bwd_dq_kernel(AttnArgs a) {
     if (j + 1 < ntiles) st.store(smem + ((j + 1) & 1) * 16384, smem + ((j + 1) & 1) * 16384 + 8192, tid);
     __syncthreads();
   }
-  if (qok) store_grad(a.dq, a.lddq, (long)b * a.N + qrow, h * D, a.g_bf16, acc, a.scale, a.rcos, a.rsin, qrow, lh);
+  if (w.qok) store_grad(a.dq, a.lddq, (long)b * a.N + w.qrow, w.h * D, a.g_bf16, acc, a.scale, a.rcos, a.rsin, w.qrow, lh);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -532,34 +589,12 @@ __global__ __launch_bounds__(512) void mqa_bwd_dq_pipe_kernel(AttnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
   const int b = blockIdx.y;
-  const int nqb = (a.N + 31) >> 5;
-  const int vb = blockIdx.x * NW + wave;
-  const bool active = vb < nqb * a.H;
-  const int h = active ? vb % a.H : 0, pb = active ? vb / a.H : 0;
-  const int qrow = pb * 32 + lr;
-  const bool qok = active && qrow < a.N;
   const float c = a.cexp;
-
-  bf16x8 qf[4], dof[4];
-  {
-    const bf16_t* qp = a.q + ((long)b * a.N + qrow) * a.ldq + h * D;
-    const bf16_t* dp = a.dout + ((long)b * a.N + qrow) * a.lddo + h * D;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 z = {0u, 0u, 0u, 0u}, z2 = {0u, 0u, 0u, 0u};
-      if (qok) { z = *reinterpret_cast<const u32x4*>(qp + 16 * ks + 8 * lh); z2 = *reinterpret_cast<const u32x4*>(dp + 16 * ks + 8 * lh); }
-      qf[ks] = __builtin_bit_cast(bf16x8, z);
-      dof[ks] = __builtin_bit_cast(bf16x8, z2);
-    }
-  }
-  const long sidx = ((long)b * a.H + h) * a.N + qrow;
-  const float L2 = qok ? a.lse2[sidx] : INFINITY;
-  const float dl = qok ? a.delta[sidx] : 0.f;
+  const QueryRow w(a, b, blockIdx.x * NW + wave, lr, lh);
+  const bf16x8 (&qf)[4] = w.qf, (&dof)[4] = w.dof;
+  const float L2 = w.L2, dl = w.dl;
   f32x16 acc[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  zero_acc(acc);
 
   const LaneOffs lo(lane);
   const int ntiles = (a.N + 63) >> 6;
@@ -656,51 +691,30 @@ __global__ __launch_bounds__(512) void mqa_bwd_dq_pipe_kernel(AttnArgs a) {
     if (j + 1 < ntiles) iter(j + 1, j & 3, (j + 2) & 3, (j + 3) & 3, s1, dp1, s0, dp0, dfp);
   }
   dq_plain((ntiles - 1) & 3, dfp);
-  if (qok) store_grad(a.dq, a.lddq, (long)b * a.N + qrow, h * D, a.g_bf16, acc, a.scale, a.rcos, a.rsin, qrow, lh);
+  if (w.qok) store_grad(a.dq, a.lddq, (long)b * a.N + w.qrow, w.h * D, a.g_bf16, acc, a.scale, a.rcos, a.rsin, w.qrow, lh);
 }
 
 // ------------------------------------------------------------------------------------------------------
 // backward, dK/dV: key-stationary.  A wave owns 32 keys; the workgroup (8 waves = 256 keys) sweeps every
 // (head, 32-query block) pair, staging Q / dO / lse / delta of the pair in LDS for all waves.
 // ------------------------------------------------------------------------------------------------------
-// DBG (triage builds via OSUF_ATTN_DBG, results garbage unless 0): 1 = no stage loads/stores (stage 0 reused), 2 = 1 + no barrier,
-// 3 = no softmax VALU, 4 = no LDS fragment reads, 5 = no MFMA.
-template <int NW, int DBG = 0>
+template <int NW>
 __global__ __launch_bounds__(NW * 64) void mqa_bwd_dkv_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];        // [2][Q 4K | dO 4K | lse 128 | delta 128]
   constexpr int kStage = 4096 + 4096 + 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
-  // XCD-aware order (speed only): every key block of a sample sweeps the same Q / dO / lse / delta; block ids are dealt
-  // round-robin over the 8 XCDs, so ids 8 apart share an L2.  PMC before this remap: 4.46 GB fetched per launch at
-  // N=4096 against 0.54 GB of distinct Q + dO bytes.
-  const int nkb = (a.N + 32 * NW - 1) / (32 * NW);
-  const int xcd = blockIdx.x & 7, qid = blockIdx.x >> 3;
-  const int b = (qid / nkb) * 8 + xcd;
-  const int kb = qid % nkb;
-  if (b >= a.B) return;
-  const int key = kb * (32 * NW) + wave * 32 + lr;
+  const KeyBlock blk(a, 32 * NW, (a.N + 31) >> 5);                  // (this kernel is launched unsplit: a.qsplit = 1)
+  if (blk.empty) return;
+  const int b = blk.b, niter = blk.niter;
+  const int key = blk.kb * (32 * NW) + wave * 32 + lr;
   const bool kok = key < a.N;
   const float c = a.cexp;
-  const int nqb = (a.N + 31) >> 5;
-  const int niter = nqb * a.H;
 
   bf16x8 kf[4], vf[4];
-  {
-    const long m = (long)b * a.N + key;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 z = {0u, 0u, 0u, 0u}, z2 = {0u, 0u, 0u, 0u};
-      if (kok) { z = *reinterpret_cast<const u32x4*>(a.k + m * a.ldk + 16 * ks + 8 * lh); z2 = *reinterpret_cast<const u32x4*>(a.v + m * a.ldv + 16 * ks + 8 * lh); }
-      kf[ks] = __builtin_bit_cast(bf16x8, z);
-      vf[ks] = __builtin_bit_cast(bf16x8, z2);
-    }
-  }
+  load_kv_frags(a, b, key, lh, kf, vf);
   f32x16 dk[2], dv[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { dk[i][r] = 0.f; dv[i][r] = 0.f; }
+  zero_acc(dk); zero_acc(dv);
 
   // stage loader: 512 16-B chunks per (head, query block): chunks 0..255 = Q tile, 256..511 = dO tile; threads 0..31 lse,
   // 32..63 delta
@@ -741,41 +755,31 @@ __global__ __launch_bounds__(NW * 64) void mqa_bwd_dkv_kernel(AttnArgs a) {
   load_stage(0);
   store_stage(0);
   __syncthreads();
-  bf16x8 cfrag = __builtin_bit_cast(bf16x8, u32x4{(uint32_t)lane, 1u, 2u, 3u});
   for (int it = 0; it < niter; ++it) {
-    const char* qs = smem + ((DBG == 1 || DBG == 2) ? 0 : (it & 1)) * kStage;
+    const char* qs = smem + (it & 1) * kStage;
     const char* dos = qs + 4096;
     const float* ls = reinterpret_cast<const float*>(qs + 8192);
-    if (DBG != 1 && DBG != 2 && it + 1 < niter) load_stage(it + 1);
+    if (it + 1 < niter) load_stage(it + 1);
     // S[q][key] = Q K^T ; dP[q][key] = dO V^T    (q rows in registers, key on the lane)
     f32x16 s, dp;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-    if (DBG == 4) asm volatile("" : "+v"(cfrag));
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const bf16x8 fq = DBG == 4 ? cfrag : lds_row_frag(qs, lo, ks, 0);
-      const bf16x8 fo = DBG == 4 ? cfrag : lds_row_frag(dos, lo, ks, 0);
-      if (DBG == 5) { asm volatile("" ::"v"(fq), "v"(fo)); continue; }
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fq, kf[ks], s, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fo, vf[ks], dp, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_row_frag(qs, lo, ks, 0), kf[ks], s, 0, 0, 0);
+      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_row_frag(dos, lo, ks, 0), vf[ks], dp, 0, 0, 0);
     }
-    if (DBG == 5) asm volatile("" : "+v"(s), "+v"(dp));
     f32x16 ds;
-    if (DBG == 3) {
-      ds = dp;
-    } else {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 l4 = *reinterpret_cast<const f32x4*>(ls + 8 * g + 4 * lh);
-        const f32x4 d4 = *reinterpret_cast<const f32x4*>(ls + 32 + 8 * g + 4 * lh);
+    for (int g = 0; g < 4; ++g) {
+      const f32x4 l4 = *reinterpret_cast<const f32x4*>(ls + 8 * g + 4 * lh);
+      const f32x4 d4 = *reinterpret_cast<const f32x4*>(ls + 32 + 8 * g + 4 * lh);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          float p = fast_exp2(fmaf(s[r], c, -l4[e]));
-          s[r] = p;
-          ds[r] = p * (dp[r] - d4[e]);              // * scale folded into the final store
-        }
+      for (int e = 0; e < 4; ++e) {
+        const int r = 4 * g + e;
+        float p = fast_exp2(fmaf(s[r], c, -l4[e]));
+        s[r] = p;
+        ds[r] = p * (dp[r] - d4[e]);              // * scale folded into the final store
       }
     }
     // dV^T[d][key] += dO^T[d][q] P[q][key] ; dK^T[d][key] += Q^T[d][q] dS[q][key]
@@ -785,15 +789,12 @@ __global__ __launch_bounds__(NW * 64) void mqa_bwd_dkv_kernel(AttnArgs a) {
       const bf16x8 df = acc_to_frag(ds, s2);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        const bf16x8 fo = DBG == 4 ? cfrag : lds_tr_frag(dos, lo, s2 * 16, dt);
-        const bf16x8 fq = DBG == 4 ? cfrag : lds_tr_frag(qs, lo, s2 * 16, dt);
-        if (DBG == 5) { asm volatile("" ::"v"(fq), "v"(fo), "v"(pf), "v"(df)); continue; }
-        dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fo, pf, dv[dt], 0, 0, 0);
-        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fq, df, dk[dt], 0, 0, 0);
+        dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_tr_frag(dos, lo, s2 * 16, dt), pf, dv[dt], 0, 0, 0);
+        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_tr_frag(qs, lo, s2 * 16, dt), df, dk[dt], 0, 0, 0);
       }
     }
-    if (DBG != 1 && DBG != 2 && it + 1 < niter) store_stage((it + 1) & 1);
-    if (DBG != 2) __syncthreads();
+    if (it + 1 < niter) store_stage((it + 1) & 1);
+    __syncthreads();
   }
   if (kok) {
     store_grad(a.dk, a.lddk, (long)b * a.N + key, 0, a.g_bf16, dk, a.kmul, a.rcos, a.rsin, key, lh);
@@ -802,8 +803,8 @@ __global__ __launch_bounds__(NW * 64) void mqa_bwd_dkv_kernel(AttnArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// dK/dV, software-pipelined inside the wave (8 waves).  The triage builds of the plain kernel (OSUF_ATTN_DBG) showed its time
-// is the SUM of the MFMA time and of everything else (5.16 ms = 1.8 + 3.05 at N=4096): with 211 VGPRs there are two waves per
+// dK/dV, software-pipelined inside the wave (8 waves).  Triage builds of the plain kernel (stage loads, barrier, softmax VALU, LDS
+// fragment reads or MFMAs compiled out one at a time; since removed) showed its time is the SUM of the MFMA time and of everything else (5.16 ms = 1.8 + 3.05 at N=4096): with 211 VGPRs there are two waves per
 // SIMD, both of one workgroup and in barrier lock-step, and inside a wave the stage is a strict chain
 // MFMA(S, dP) -> exp/VALU -> MFMA(dV, dK), so the matrix pipe idles during the VALU phase and vice versa.  Here iteration `it`
 // issues the S / dP products of stage it+1 (independent of everything else in the iteration) next to the exp/VALU work of
@@ -815,38 +816,17 @@ __global__ __launch_bounds__(512) void mqa_bwd_dkv_pipe_kernel(AttnArgs a) {
   constexpr int NW = 8, kStage = 4096 + 4096 + 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
-  const int nkb = (a.N + 32 * NW - 1) / (32 * NW);
-  const int per_split = (int)gridDim.x / a.qsplit;                 // workgroups of one query part (a multiple of 8)
-  const int part = (int)blockIdx.x / per_split, bid = (int)blockIdx.x - part * per_split;
-  const int xcd = bid & 7, qid = bid >> 3;
-  const int b = (qid / nkb) * 8 + xcd;
-  const int kb = qid % nkb;
-  if (b >= a.B) return;
-  const int key = kb * (32 * NW) + wave * 32 + lr;
+  const KeyBlock blk(a, 32 * NW, (a.N + 31) >> 5);
+  if (blk.empty) return;
+  const int b = blk.b, qb_begin = blk.qb_begin, niter = blk.niter;
+  const int key = blk.kb * (32 * NW) + wave * 32 + lr;
   const bool kok = key < a.N;
   const float c = a.cexp;
-  const int nqb = (a.N + 31) >> 5;
-  const int qb_per = (nqb + a.qsplit - 1) / a.qsplit;
-  const int qb_begin = part * qb_per, qb_end = min(nqb, qb_begin + qb_per);
-  if (qb_begin >= qb_end) return;                                  // uniform per workgroup, before any barrier
-  const int niter = (qb_end - qb_begin) * a.H;
 
   bf16x8 kf[4], vf[4];
-  {
-    const long m = (long)b * a.N + key;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 z = {0u, 0u, 0u, 0u}, z2 = {0u, 0u, 0u, 0u};
-      if (kok) { z = *reinterpret_cast<const u32x4*>(a.k + m * a.ldk + 16 * ks + 8 * lh); z2 = *reinterpret_cast<const u32x4*>(a.v + m * a.ldv + 16 * ks + 8 * lh); }
-      kf[ks] = __builtin_bit_cast(bf16x8, z);
-      vf[ks] = __builtin_bit_cast(bf16x8, z2);
-    }
-  }
+  load_kv_frags(a, b, key, lh, kf, vf);
   f32x16 dk[2], dv[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { dk[i][r] = 0.f; dv[i][r] = 0.f; }
+  zero_acc(dk); zero_acc(dv);
 
   // stage loader (512 threads, one 16-B chunk each): chunks 0..255 = Q tile, 256..511 = dO tile; threads 0..31 lse, 32..63 delta
   const int lt = tid & 255, lrow = lt >> 3, lchunk = lt & 7;
@@ -975,14 +955,7 @@ __global__ __launch_bounds__(512) void mqa_bwd_dkv_pipe_kernel(AttnArgs a) {
     if (it + 1 < niter) iter(it + 1, sB, sC, sA, s1, dp1, s0, dp0);
     slot = sC;
   }
-  if (kok && a.qsplit > 1) {                                       // this part's partial sums, plain 16-byte stores (atomics measured
-    const long prow = ((long)part * a.B + b) * a.N + key;          // as slow as the iterations the split saves: 38 G atomics/s)
-    store_grad_row(a.wsk + prow * D, dk, 1.f, nullptr, nullptr, lh);
-    store_grad_row(a.wsv + prow * D, dv, 1.f, nullptr, nullptr, lh);
-  } else if (kok) {
-    store_grad(a.dk, a.lddk, (long)b * a.N + key, 0, a.g_bf16, dk, a.kmul, a.rcos, a.rsin, key, lh);
-    store_grad(a.dv, a.lddk, (long)b * a.N + key, 0, a.g_bf16, dv, 1.f, nullptr, nullptr, key, lh);
-  }
+  if (kok) store_dkv(a, blk.part, b, key, lh, dk, dv);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1019,39 +992,18 @@ __global__ __launch_bounds__(512) void mqa_bwd_fused_kernel(AttnArgs a, float* d
   char* eimg = kimg + 32768;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
-  const int nkb = (a.N + 32 * NW - 1) / (32 * NW);
-  const int per_split = (int)gridDim.x / a.qsplit;
-  const int part = (int)blockIdx.x / per_split, bid = (int)blockIdx.x - part * per_split;
-  const int xcd = bid & 7, qid = bid >> 3;
-  const int b = (qid / nkb) * 8 + xcd;
-  const int kb = qid % nkb;
-  if (b >= a.B) return;
+  const int nqb = (a.N + 31) >> 5;
+  const KeyBlock blk(a, 32 * NW, nqb);
+  if (blk.empty) return;
+  const int b = blk.b, kb = blk.kb, qb_begin = blk.qb_begin, qb_end = blk.qb_end, niter = blk.niter;
   const int key = kb * (32 * NW) + wave * 32 + lr;
   const bool kok = key < a.N;
   const float c = a.cexp;
-  const int nqb = (a.N + 31) >> 5;
-  const int qb_per = (nqb + a.qsplit - 1) / a.qsplit;
-  const int qb_begin = part * qb_per, qb_end = min(nqb, qb_begin + qb_per);
-  if (qb_begin >= qb_end) return;                                  // uniform per workgroup, before any barrier
-  const int niter = (qb_end - qb_begin) * a.H;
 
   bf16x8 kf[4], vf[4];
-  {
-    const long m = (long)b * a.N + key;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 z = {0u, 0u, 0u, 0u}, z2 = {0u, 0u, 0u, 0u};
-      if (kok) { z = *reinterpret_cast<const u32x4*>(a.k + m * a.ldk + 16 * ks + 8 * lh); z2 = *reinterpret_cast<const u32x4*>(a.v + m * a.ldv + 16 * ks + 8 * lh); }
-      kf[ks] = __builtin_bit_cast(bf16x8, z);
-      vf[ks] = __builtin_bit_cast(bf16x8, z2);
-      *reinterpret_cast<u32x4*>(kimg + tile_off(wave * 32 + lr, (2 * ks + lh) * 16)) = z;     // resident K image (zero rows beyond N)
-    }
-  }
+  load_kv_frags(a, b, key, lh, kf, vf, kimg, wave * 32 + lr);      // + the resident K image (zero rows beyond N)
   f32x16 dk[2], dv[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { dk[i][r] = 0.f; dv[i][r] = 0.f; }
+  zero_acc(dk); zero_acc(dv);
 
   // stage loader (512 threads, one 16-B chunk each): chunks 0..255 = Q tile, 256..511 = dO tile; threads 0..31 lse, 32..63 delta.
   // BRANCH-FREE on purpose: the kernel keeps float atomics in flight (they stay in the in-order vmcnt queue for ~3,000 cycles when
@@ -1217,7 +1169,7 @@ __global__ __launch_bounds__(512) void mqa_bwd_fused_kernel(AttnArgs a, float* d
   }
   dq_tile(eimg + ((niter - 1) & 1) * 16384, ph, ppb);
   if (kok && a.qsplit > 1) {
-    const long prow = ((long)part * a.B + b) * a.N + key;
+    const long prow = ((long)blk.part * a.B + b) * a.N + key;
     store_grad_row(a.wsk + prow * D, dk, 1.f, nullptr, nullptr, lh);
     store_grad_row(a.wsv + prow * D, dv, 1.f, nullptr, nullptr, lh);
   } else if (kok) {
@@ -1286,8 +1238,6 @@ __device__ __forceinline__ void mfma16_fence(f32x4& a0, f32x4& a1) { asm("s_nop 
 __device__ __forceinline__ void mfma32_fence_short(f32x16& acc) { asm("s_nop 3" : "+v"(acc)); }
 __device__ __forceinline__ void mfma32_fence_agpr(f32x16& acc) { asm("s_nop 15\n\ts_nop 3" : "+a"(acc)); }
 
-// ATOMICS = false: timing-only build of the sweep (dQ tiles are computed and dropped) -- prices the loop without its atomics
-template <bool ATOMICS>
 __global__ __launch_bounds__(256, 1) void mqa_bwd_fused512_kernel(AttnArgs a, float* dq32) {
   extern __shared__ __attribute__((aligned(16))) char smem[];        // [2][Q 4K | dO 4K | -lse/c 128 | -delta 128] | K image 64K | [2] dS image 32K
   constexpr int kStage = 4096 + 4096 + 256;
@@ -1295,41 +1245,20 @@ __global__ __launch_bounds__(256, 1) void mqa_bwd_fused512_kernel(AttnArgs a, fl
   char* eimg = kimg + 65536;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
-  const int nkb = (a.N + 511) / 512;
-  const int per_split = (int)gridDim.x / a.qsplit;
-  const int part = (int)blockIdx.x / per_split, bid = (int)blockIdx.x - part * per_split;
-  const int xcd = bid & 7, qid = bid >> 3;
-  const int b = (qid / nkb) * 8 + xcd;
-  const int kb = qid % nkb;
-  if (b >= a.B) return;
+  const KeyBlock blk(a, 512, a.N >> 5);
+  if (blk.empty) return;
+  const int b = blk.b, qb_begin = blk.qb_begin, qb_end = blk.qb_end, niter = blk.niter;
   const float c = a.cexp;
-  const int nqb = a.N >> 5;
-  const int qb_per = (nqb + a.qsplit - 1) / a.qsplit;
-  const int qb_begin = part * qb_per, qb_end = min(nqb, qb_begin + qb_per);
-  if (qb_begin >= qb_end) return;                                  // uniform per workgroup, before any barrier
-  const int niter = (qb_end - qb_begin) * a.H;
-  const int key0 = kb * 512 + wave * 128;                          // this wave's keys: key0 + 32 t + lr, t = 0..3
+  const int key0 = blk.kb * 512 + wave * 128;                      // this wave's keys: key0 + 32 t + lr, t = 0..3
 
   bf16x8 vf[4][4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int key = key0 + t * 32 + lr;
-    const long m = (long)b * a.N + key;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 z = {0u, 0u, 0u, 0u}, z2 = {0u, 0u, 0u, 0u};
-      if (key < a.N) { z = *reinterpret_cast<const u32x4*>(a.k + m * a.ldk + 16 * ks + 8 * lh); z2 = *reinterpret_cast<const u32x4*>(a.v + m * a.ldv + 16 * ks + 8 * lh); }
-      vf[t][ks] = __builtin_bit_cast(bf16x8, z2);
-      *reinterpret_cast<u32x4*>(kimg + tile_off(wave * 128 + t * 32 + lr, (2 * ks + lh) * 16)) = z;   // resident K image (zero rows beyond N)
-    }
-  }
   f32x16 dk[4][2], dv[4][2];
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { dk[t][i][r] = 0.f; dv[t][i][r] = 0.f; }
+  for (int t = 0; t < 4; ++t) {
+    bf16x8 kf_unused[4];                                           // (K is read back from the image, row-wise for S and column-wise for dQ)
+    load_kv_frags(a, b, key0 + t * 32 + lr, lh, kf_unused, vf[t], kimg, wave * 128 + t * 32 + lr);   // V fragments + the resident K image (zero rows beyond N)
+    zero_acc(dk[t]); zero_acc(dv[t]);
+  }
 
   // stage loader (256 threads): thread -> one 16-B chunk of the Q tile and the same chunk of the dO tile; threads 0..31 / 32..63 the
   // pair's lse / delta rows, stored as the INITIAL ACCUMULATORS -lse2 / c and -delta.  Branch-free, loads before the iteration's atomics
@@ -1383,28 +1312,20 @@ __global__ __launch_bounds__(256, 1) void mqa_bwd_fused512_kernel(AttnArgs a, fl
   char* dq_prev = reinterpret_cast<char*>(dq32 + ((long)b * a.N + qb_begin * 32) * (a.H * D));
   char* dq_cur = dq_prev;
   auto dq_add2 = [&](const f32x4& q0, const f32x4& q1, int r, int, int) {      // row r of both query halves
-    if constexpr (ATOMICS) {
-      char* sb = dq_prev;
-      unsigned ob = aoffb;
-      asm volatile("" : "+v"(ob));
-      atomic_add_f32(reinterpret_cast<float*>(sb + (ob + (unsigned)r * rowb)), q0[r]);
-      atomic_add_f32(reinterpret_cast<float*>(sb + (ob + (unsigned)(16 + r) * rowb)), q1[r]);
-    } else {
-      asm volatile("" :: "v"(q0[r]), "v"(q1[r]));
-    }
+    char* sb = dq_prev;
+    unsigned ob = aoffb;
+    asm volatile("" : "+v"(ob));
+    atomic_add_f32(reinterpret_cast<float*>(sb + (ob + (unsigned)r * rowb)), q0[r]);
+    atomic_add_f32(reinterpret_cast<float*>(sb + (ob + (unsigned)(16 + r) * rowb)), q1[r]);
   };
   auto dq_add = [&](const f32x4& q0, const f32x4& q1, int, int) {
-    if constexpr (ATOMICS) {
-      char* sb = dq_prev;
-      unsigned ob = aoffb;
-      asm volatile("" : "+v"(ob));                                  // opaque per call: keeps the eight offsets out of loop-invariant registers
+    char* sb = dq_prev;
+    unsigned ob = aoffb;
+    asm volatile("" : "+v"(ob));                                    // opaque per call: keeps the eight offsets out of loop-invariant registers
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        atomic_add_f32(reinterpret_cast<float*>(sb + (ob + (unsigned)r * rowb)), q0[r]);
-        atomic_add_f32(reinterpret_cast<float*>(sb + (ob + (unsigned)(16 + r) * rowb)), q1[r]);
-      }
-    } else {
-      asm volatile("" :: "v"(q0), "v"(q1));
+    for (int r = 0; r < 4; ++r) {
+      atomic_add_f32(reinterpret_cast<float*>(sb + (ob + (unsigned)r * rowb)), q0[r]);
+      atomic_add_f32(reinterpret_cast<float*>(sb + (ob + (unsigned)(16 + r) * rowb)), q1[r]);
     }
   };
   const int eoff[2][2] = {{ds_img_off512(8 * g4 + tq, tp), ds_img_off512(8 * g4 + tq + 4, tp)},
@@ -1560,14 +1481,7 @@ __global__ __launch_bounds__(256, 1) void mqa_bwd_fused512_kernel(AttnArgs a, fl
     const int key = key0 + t * 32 + lr;
 #pragma unroll
     for (int i = 0; i < 2; ++i) { mfma32_fence_agpr(dk[t][i]); mfma32_fence_agpr(dv[t][i]); }     // written back before the accumulators are read
-    if (key < a.N && a.qsplit > 1) {
-      const long prow = ((long)part * a.B + b) * a.N + key;
-      store_grad_row(a.wsk + prow * D, dk[t], 1.f, nullptr, nullptr, lh);
-      store_grad_row(a.wsv + prow * D, dv[t], 1.f, nullptr, nullptr, lh);
-    } else if (key < a.N) {
-      store_grad(a.dk, a.lddk, (long)b * a.N + key, 0, a.g_bf16, dk[t], a.kmul, a.rcos, a.rsin, key, lh);
-      store_grad(a.dv, a.lddk, (long)b * a.N + key, 0, a.g_bf16, dv[t], 1.f, nullptr, nullptr, key, lh);
-    }
+    if (key < a.N) store_dkv(a, blk.part, b, key, lh, dk[t], dv[t]);
   }
 }
 
@@ -1944,9 +1858,47 @@ static inline int ew_grid(long total_threads) {
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // head dims served by the generic kernels of attn_generic.hpp (64 has the tuned kernels of this file): padded tile width, 0 = unsupported
 static int gen_dp(int head_dim) { return head_dim == 16 || head_dim == 32 ? 32 : head_dim == 128 ? 128 : 0; }
+// argument checks and AttnArgs of the forward entry points
+static int fill_fwd_args(AttnArgs& a, const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
+                         float* lse2, int B, int H, int N, int head_dim, float scale) {
+  if (head_dim != D && !gen_dp(head_dim)) return OSUF_EUNSUPPORTED;
+  if (B <= 0 || H <= 0 || N <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || !al16(q) || !al16(k) || !al16(v) || !al16(o)) return OSUF_EINVAL;
+  a = AttnArgs{};
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.o = o; a.ldo = ldo; a.o_is_f32 = o_dtype == OSUF_DT_F32; a.lse2 = lse2; a.B = B; a.H = H; a.N = N; a.scale = scale; a.cexp = scale * kLog2e; a.kmul = scale;
+  return OSUF_OK;
+}
 struct FwdRope { const float* cos; const float* sin; float qmul; void* qout; long ldqo; };   // osuf_mqa_fwd_rope's extra operands
 static int mqa_fwd_impl(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
-                        float* lse2, int B, int H, int N, int head_dim, float scale, bool qs, hipStream_t stream, float* zdq, const FwdRope* rope = nullptr);
+                        float* lse2, int B, int H, int N, int head_dim, float scale, bool qs, hipStream_t stream, float* zdq, const FwdRope* rope = nullptr) {
+  AttnArgs a;
+  const int rc = fill_fwd_args(a, q, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, H, N, head_dim, scale);
+  if (rc) return rc;
+  if (zdq && (head_dim != D || !al16(zdq))) return OSUF_EINVAL;
+  if (rope && (head_dim != D || !qs || !rope->cos || !rope->sin || !(rope->qmul > 0.f) || (rope->qout && (rope->ldqo % 8 || !al16(rope->qout))))) return OSUF_EINVAL;
+  if (qs) a.cexp = 1.f;
+  a.zdq = zdq;
+  if (rope) { a.rcos = rope->cos; a.rsin = rope->sin; a.qmul = rope->qmul; a.qout = (bf16_t*)rope->qout; a.ldqo = rope->ldqo; }
+  const int nvb = ((N + 31) / 32) * H;
+  if (head_dim != D) {
+    const dim3 grid((nvb + 3) / 4, B);
+    if (gen_dp(head_dim) == 32) hipLaunchKernelGGL(mqa_gen_fwd_kernel<32>, grid, dim3(256), 2 * 64 * 64, stream, a, head_dim);
+    else hipLaunchKernelGGL(mqa_gen_fwd_kernel<128>, grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
+    return osuf_launch_status();
+  }
+  const bool whole = (N & 63) == 0 && getenv("OSUF_ATTN_FWD_NOWHOLE") == nullptr;
+  const dim3 grid((nvb + 7) / 8, B);
+  const int lds = 32768 + 8 * 4096;
+  if (rope) {
+    if (whole) hipLaunchKernelGGL((mqa_fwd_kernel<8, true, true, true>), grid, dim3(512), lds, stream, a);
+    else hipLaunchKernelGGL((mqa_fwd_kernel<8, true, false, true>), grid, dim3(512), lds, stream, a);
+  } else if (qs && getenv("OSUF_ATTN_FWD_NOQSK") == nullptr) {
+    if (whole) hipLaunchKernelGGL((mqa_fwd_kernel<8, true, true>), grid, dim3(512), lds, stream, a);
+    else hipLaunchKernelGGL((mqa_fwd_kernel<8, true>), grid, dim3(512), lds, stream, a);
+  } else if (whole) hipLaunchKernelGGL((mqa_fwd_kernel<8, false, true>), grid, dim3(512), lds, stream, a);
+  else hipLaunchKernelGGL(mqa_fwd_kernel<8>, grid, dim3(512), lds, stream, a);
+  return osuf_launch_status();
+}
 extern "C" int osuf_mqa_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
                             float* lse2, int B, int H, int N, int head_dim, float scale, hipStream_t stream) {
   return mqa_fwd_impl(q, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, H, N, head_dim, scale, false, stream, nullptr);
@@ -1975,50 +1927,16 @@ extern "C" int osuf_mqa_fwd_rope(const void* q_raw, long ldq, const void* k, lon
   const FwdRope r = {rope_cos, rope_sin, q_mul, q_out, ldqo};
   return mqa_fwd_impl(q_raw, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, H, N, head_dim, scale, true, stream, zero_dq, &r);
 }
-static int mqa_fwd_impl(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
-                        float* lse2, int B, int H, int N, int head_dim, float scale, bool qs, hipStream_t stream, float* zdq, const FwdRope* rope) {
-  if (head_dim != D && !gen_dp(head_dim)) return OSUF_EUNSUPPORTED;
-  if (zdq && (head_dim != D || !al16(zdq))) return OSUF_EINVAL;
-  if (rope && (head_dim != D || !qs || !rope->cos || !rope->sin || !(rope->qmul > 0.f) || (rope->qout && (rope->ldqo % 8 || !al16(rope->qout))))) return OSUF_EINVAL;
-  if (B <= 0 || H <= 0 || N <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || !al16(q) || !al16(k) || !al16(v) || !al16(o)) return OSUF_EINVAL;
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.o = o; a.ldo = ldo; a.o_is_f32 = o_dtype == OSUF_DT_F32; a.lse2 = lse2; a.B = B; a.H = H; a.N = N; a.scale = scale; a.cexp = scale * kLog2e; a.kmul = scale;
-  if (qs) a.cexp = 1.f;
-  a.zdq = zdq;
-  if (rope) { a.rcos = rope->cos; a.rsin = rope->sin; a.qmul = rope->qmul; a.qout = (bf16_t*)rope->qout; a.ldqo = rope->ldqo; }
-  const int nvb = ((N + 31) / 32) * H;
-  if (head_dim != D) {
-    const dim3 grid((nvb + 3) / 4, B);
-    if (gen_dp(head_dim) == 32) hipLaunchKernelGGL(mqa_gen_fwd_kernel<32>, grid, dim3(256), 2 * 64 * 64, stream, a, head_dim);
-    else hipLaunchKernelGGL(mqa_gen_fwd_kernel<128>, grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
-    return osuf_launch_status();
-  }
-  const bool whole = (N & 63) == 0 && getenv("OSUF_ATTN_FWD_NOWHOLE") == nullptr;
-  const dim3 grid((nvb + 7) / 8, B);
-  const int lds = 32768 + 8 * 4096;
-  if (rope) {
-    if (whole) hipLaunchKernelGGL((mqa_fwd_kernel<8, true, true, true>), grid, dim3(512), lds, stream, a);
-    else hipLaunchKernelGGL((mqa_fwd_kernel<8, true, false, true>), grid, dim3(512), lds, stream, a);
-  } else if (qs && getenv("OSUF_ATTN_FWD_NOQSK") == nullptr) {
-    if (whole) hipLaunchKernelGGL((mqa_fwd_kernel<8, true, true>), grid, dim3(512), lds, stream, a);
-    else hipLaunchKernelGGL((mqa_fwd_kernel<8, true>), grid, dim3(512), lds, stream, a);
-  } else if (whole) hipLaunchKernelGGL((mqa_fwd_kernel<8, false, true>), grid, dim3(512), lds, stream, a);
-  else hipLaunchKernelGGL(mqa_fwd_kernel<8>, grid, dim3(512), lds, stream, a);
-  return osuf_launch_status();
-}
 
 // Attend(q, k, v, attn_mask) (attention.py:77-99): the forward with an additive bf16 score bias, element strides over (b, h, q, key) with 0
 // for broadcast dimensions.  Inference path of the stand-alone Attend module; every head dim (64 included) runs the generic kernel.
 extern "C" int osuf_mqa_fwd_masked(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
                                    float* lse2, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k, int B, int H, int N,
                                    int head_dim, float scale, hipStream_t stream) {
-  if (head_dim != D && !gen_dp(head_dim)) return OSUF_EUNSUPPORTED;
-  if (B <= 0 || H <= 0 || N <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || !al16(q) || !al16(k) || !al16(v) || !al16(o) || !mask || scale == 0.f)
-    return OSUF_EINVAL;
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.o = o; a.ldo = ldo; a.o_is_f32 = o_dtype == OSUF_DT_F32; a.lse2 = lse2; a.B = B; a.H = H; a.N = N; a.scale = scale; a.cexp = scale * kLog2e; a.kmul = scale;
+  AttnArgs a;
+  const int rc = fill_fwd_args(a, q, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, H, N, head_dim, scale);
+  if (rc) return rc;
+  if (!mask || scale == 0.f) return OSUF_EINVAL;
   a.mask = (const bf16_t*)mask; a.mask_b = mask_b; a.mask_h = mask_h; a.mask_q = mask_q; a.mask_k = mask_k;
   const int nvb = ((N + 31) / 32) * H;
   const dim3 grid((nvb + 3) / 4, B);
@@ -2115,11 +2033,18 @@ extern "C" int osuf_mqa_bwd_dq(const void* q, long ldq, const void* k, long ldk,
   if (variant == OSUF_ATTN_AUTO) variant = N >= 2048 ? OSUF_ATTN_PIPE : OSUF_ATTN_PLAIN;
   if (variant == OSUF_ATTN_PLAIN) hipLaunchKernelGGL(mqa_bwd_dq_kernel<8>, dim3((nvb + 7) / 8, B), dim3(512), 32768, stream, a);
   else {
-    static bool once = ((void)hipFuncSetAttribute((const void*)mqa_bwd_dq_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536), true);
-    (void)once;
+    allow_lds<mqa_bwd_dq_pipe_kernel>(65536);
     hipLaunchKernelGGL(mqa_bwd_dq_pipe_kernel, dim3((nvb + 7) / 8, B), dim3(512), 65536, stream, a);
   }
   return osuf_launch_status();
+}
+
+// second half of a query-split dK/dV sweep (a.qsplit parts in a.wsk / a.wsv) into a.dk / a.dv
+static void launch_dkv_finish(const AttnArgs& a, hipStream_t stream) {
+  const long M = (long)a.B * a.N;
+  const unsigned fb = (unsigned)((M * 32 + 255) / 256);
+  if (a.g_bf16) hipLaunchKernelGGL(dkv_finish_kernel<bf16_t>, dim3(fb), dim3(256), 0, stream, a.wsk, a.wsv, a.qsplit, (bf16_t*)a.dk, (bf16_t*)a.dv, a.lddk, M, a.N, a.kmul, a.rcos, a.rsin);
+  else hipLaunchKernelGGL(dkv_finish_kernel<float>, dim3(fb), dim3(256), 0, stream, a.wsk, a.wsv, a.qsplit, (float*)a.dk, (float*)a.dv, a.lddk, M, a.N, a.kmul, a.rcos, a.rsin);
 }
 
 // dk, dv: [B*N][lddk] in out_dtype; rope tables as for dq (applied to dk only)
@@ -2169,10 +2094,7 @@ extern "C" int osuf_mqa_bwd_dkv(const void* q, long ldq, const void* k, long ldk
     a.qsplit = dkv_qsplit(B, N, qsplit);
     a.wsk = workspace; a.wsv = workspace + (long)a.qsplit * B * N * D;
     hipLaunchKernelGGL(mqa_bwd_dkv_pipe_kernel, dim3(grid.x * a.qsplit), dim3(512), 3 * (4096 + 4096 + 256), stream, a);
-    const long M = (long)B * N;
-    const unsigned fb = (unsigned)((M * 32 + 255) / 256);
-    if (a.g_bf16) hipLaunchKernelGGL(dkv_finish_kernel<bf16_t>, dim3(fb), dim3(256), 0, stream, a.wsk, a.wsv, a.qsplit, (bf16_t*)dk, (bf16_t*)dv, lddk, M, N, a.kmul, rope_cos, rope_sin);
-    else hipLaunchKernelGGL(dkv_finish_kernel<float>, dim3(fb), dim3(256), 0, stream, a.wsk, a.wsv, a.qsplit, (float*)dk, (float*)dv, lddk, M, N, a.kmul, rope_cos, rope_sin);
+    launch_dkv_finish(a, stream);
   } else {
     hipLaunchKernelGGL(mqa_bwd_dkv_pipe_kernel, grid, dim3(512), 3 * (4096 + 4096 + 256), stream, a);
   }
@@ -2191,14 +2113,12 @@ static long fused_dq_bytes(int B, int H, int N, int out_dtype, int dq_mode) {
 // Which sweep an atomic-dQ call runs, and in how many query parts.  512 keys per workgroup (mqa_bwd_fused512_kernel) halves the dQ
 // atomic bytes but gives half as many workgroups: it is taken where whole 32-query blocks and enough work per part remain.
 static bool fused_use512(int B, int N, int dq_mode) {
-  if (dq_mode == OSUF_DQ_ATOMIC_512 || dq_mode == OSUF_DQ_TIMING_512 || dq_mode == OSUF_DQ_ATOMIC_512A) return true;
+  if (dq_mode == OSUF_DQ_ATOMIC_512 || dq_mode == OSUF_DQ_ATOMIC_512A) return true;
   if (dq_mode != OSUF_DQ_ATOMIC) return false;
   // whole 512-key blocks only: a padded key's K / V rows are zero, but its S accumulator starts at -lse2 / c, so p = exp2(-lse2) and
   // dS = p * (-delta) are not -- for a row with lse2 < -128 p overflows and inf x 0 lands in dQ as NaN
   return (N % 512) == 0 && N >= 1024;
 }
-// the timing-only build returns OSUF_OK with dq all zeros: refused unless the caller's environment says it is pricing a loop
-static bool timing_builds_allowed() { const char* e = getenv("OSUF_ALLOW_TIMING_BUILDS"); return e && e[0] == '1'; }
 static int fused512_qsplit(int B, int N, int forced) {
   if (forced > 0) return forced;
   const int blocks = ((N + 511) / 512) * ((B + 7) / 8 * 8);
@@ -2206,7 +2126,8 @@ static int fused512_qsplit(int B, int N, int forced) {
   while (sp < 8 && blocks * sp < 256 && (N / 32) / (sp * 2) >= 8) sp *= 2;
   return sp;
 }
-static bool fused_mode_ok(int dq_mode) { return dq_mode >= OSUF_DQ_ATOMIC && dq_mode <= OSUF_DQ_ATOMIC_512A; }
+// (4 was the no-atomics timing build of the 512-key sweep, since removed: the other values keep their numbers)
+static bool fused_mode_ok(int dq_mode) { return (dq_mode >= OSUF_DQ_ATOMIC && dq_mode <= OSUF_DQ_ATOMIC_512) || dq_mode == OSUF_DQ_ATOMIC_512A; }
 // dq_mode | OSUF_DQ_PREZEROED: the dQ accumulator at the head of the workspace was zero-filled by osuf_mqa_fwd_zdq (no memset here)
 static int strip_prezeroed(int dq_mode, bool* prezeroed) {
   if (prezeroed) *prezeroed = (dq_mode & OSUF_DQ_PREZEROED) != 0;
@@ -2233,25 +2154,25 @@ extern "C" long osuf_mqa_bwd_fused_workspace_bytes(int B, int H, int N, int out_
   return fused_dq_bytes(B, H, N, out_dtype, dq_mode) + fused_dkv_ws_bytes(B, N, qsplit, dq_mode);
 }
 
-static int mqa_bwd_fused_impl(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
-                              const float* lse2, const float* delta, void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H,
-                              int N, int head_dim, float scale, int out_dtype, const float* rope_cos, const float* rope_sin,
-                              float* workspace, long workspace_bytes, int qsplit, int dq_mode, bool qs, hipStream_t stream);
-extern "C" int osuf_mqa_bwd_fused(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
-                                  const float* lse2, const float* delta, void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H,
-                                  int N, int head_dim, float scale, int out_dtype, const float* rope_cos, const float* rope_sin,
-                                  float* workspace, long workspace_bytes, int qsplit, int dq_mode, hipStream_t stream) {
-  return mqa_bwd_fused_impl(q, ldq, k, ldk, v, ldv, dout, lddo, lse2, delta, dq, lddq, dk, dv, lddk, B, H, N, head_dim, scale, out_dtype, rope_cos,
-                            rope_sin, workspace, workspace_bytes, qsplit, dq_mode, false, stream);
+// one fused sweep: the kernel's one-time dynamic-LDS opt-in, then the launch
+template <auto KERNEL> static void launch_fused(dim3 grid, int threads, int lds, hipStream_t stream, const AttnArgs& a, float* dq32) {
+  allow_lds<KERNEL>(lds);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, stream, a, dq32);
 }
-// q pre-scaled by c = scale * log2 e (osuf_rope_cast_qs; lse2 from osuf_mqa_fwd_qs): p = exp2(Qs K^T - lse2) with no multiply; dq = scale dS K
-// as before (the gradient of the UN-scaled rotated q), dk = (scale / c) dS^T Qs.  The generated 512-key loop drops its 64 v_mul per pair.
-extern "C" int osuf_mqa_bwd_fused_qs(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
-                                     const float* lse2, const float* delta, void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H,
-                                     int N, int head_dim, float scale, int out_dtype, const float* rope_cos, const float* rope_sin,
-                                     float* workspace, long workspace_bytes, int qsplit, int dq_mode, hipStream_t stream) {
-  return mqa_bwd_fused_impl(q, ldq, k, ldk, v, ldv, dout, lddo, lse2, delta, dq, lddq, dk, dv, lddk, B, H, N, head_dim, scale, out_dtype, rope_cos,
-                            rope_sin, workspace, workspace_bytes, qsplit, dq_mode, true, stream);
+// dQ of a fused sweep out of its workspace (fp32 sums, or the key-block slabs in the output's element type) into dq [B*N][lddq]
+static void launch_dq_finish(const AttnArgs& a, const float* dq32, bool slabs, void* dq, long lddq, hipStream_t stream) {
+  const int B = a.B, N = a.N, H = a.H;
+  const long M = (long)B * N;
+  const int qb = ew_grid(M * H * 8);
+  const int nkb = (N + 255) / 256, npad = (N + 31) / 32 * 32;
+  if (!slabs) {
+    if (a.g_bf16) hipLaunchKernelGGL(dq_finish_kernel<bf16_t>, dim3(qb), dim3(256), 0, stream, dq32, (bf16_t*)dq, lddq, M, N, H, a.scale, a.rcos, a.rsin);
+    else hipLaunchKernelGGL(dq_finish_kernel<float>, dim3(qb), dim3(256), 0, stream, dq32, (float*)dq, lddq, M, N, H, a.scale, a.rcos, a.rsin);
+  } else if (a.g_bf16) {
+    hipLaunchKernelGGL((dq_reduce_kernel<bf16_t, bf16_t>), dim3(qb), dim3(256), 0, stream, (const bf16_t*)dq32, nkb, (bf16_t*)dq, lddq, B, N, npad, H, a.scale, a.rcos, a.rsin);
+  } else {
+    hipLaunchKernelGGL((dq_reduce_kernel<float, float>), dim3(qb), dim3(256), 0, stream, (const float*)dq32, nkb, (float*)dq, lddq, B, N, npad, H, a.scale, a.rcos, a.rsin);
+  }
 }
 static int mqa_bwd_fused_impl(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
                               const float* lse2, const float* delta, void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H,
@@ -2271,9 +2192,7 @@ static int mqa_bwd_fused_impl(const void* q, long ldq, const void* k, long ldk, 
   if (head_dim != D) return OSUF_EUNSUPPORTED;                     // the fused sweeps are written for 64-wide heads (others: dq + dkv kernels)
   const bool use512 = fused_use512(B, N, dq_mode);
   if (use512 && (N % 512) != 0) return OSUF_EUNSUPPORTED;          // the 512-key sweep is written for whole 512-key blocks (see fused_use512)
-  if (dq_mode == OSUF_DQ_TIMING_512 && !timing_builds_allowed()) return OSUF_EUNSUPPORTED;
   a.dk = dk; a.dv = dv; a.lddk = lddk; a.g_bf16 = out_dtype == OSUF_DT_BF16; a.rcos = rope_cos; a.rsin = rope_sin;
-  const long M = (long)B * N;
   const long dq_bytes = fused_dq_bytes(B, H, N, out_dtype, dq_mode);
   float* dq32 = workspace;
   float* wsp = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + dq_bytes);
@@ -2286,71 +2205,48 @@ static int mqa_bwd_fused_impl(const void* q, long ldq, const void* k, long ldk, 
   }
   // the 512-key sweep runs its hand-placed loop wherever that loop's shape rules hold (every UNet level does), the compiled loop elsewhere
   const bool use512a = use512 && (dq_mode == OSUF_DQ_ATOMIC_512A || (dq_mode == OSUF_DQ_ATOMIC && fused512a_ok(a, N)));
+  const int lds512 = 2 * (4096 + 4096 + 256) + 65536 + 2 * 32768, lds256 = 2 * (4096 + 4096 + 256) + 32768 + 2 * 16384;
+  const dim3 grid512(((N + 511) / 512) * b8 * a.qsplit), grid256(((N + 255) / 256) * b8 * a.qsplit);
   if (use512a) {
     if (!fused512a_ok(a, N)) return OSUF_EUNSUPPORTED;
-    const int lds = 2 * (4096 + 4096 + 256) + 65536 + 2 * 32768;
-    static bool attr512a = false;
-    if (!attr512a) {
-      (void)hipFuncSetAttribute((const void*)mqa_bwd_fused512a_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      (void)hipFuncSetAttribute((const void*)mqa_bwd_fused512a_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      attr512a = true;
-    }
-    if (qs) hipLaunchKernelGGL(mqa_bwd_fused512a_kernel<true>, dim3((N / 512) * b8 * a.qsplit), dim3(256), lds, stream, a, dq32);
-    else hipLaunchKernelGGL(mqa_bwd_fused512a_kernel<false>, dim3((N / 512) * b8 * a.qsplit), dim3(256), lds, stream, a, dq32);
+    if (qs) launch_fused<mqa_bwd_fused512a_kernel<true>>(grid512, 256, lds512, stream, a, dq32);
+    else launch_fused<mqa_bwd_fused512a_kernel<false>>(grid512, 256, lds512, stream, a, dq32);
   } else if (use512) {
-    const int lds = 2 * (4096 + 4096 + 256) + 65536 + 2 * 32768;
-    void (*kern)(AttnArgs, float*) = dq_mode == OSUF_DQ_TIMING_512 ? mqa_bwd_fused512_kernel<false> : mqa_bwd_fused512_kernel<true>;
-    static bool attr512[2] = {false, false};
-    if (!attr512[dq_mode == OSUF_DQ_TIMING_512]) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      attr512[dq_mode == OSUF_DQ_TIMING_512] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(((N + 511) / 512) * b8 * a.qsplit), dim3(256), lds, stream, a, dq32);
+    launch_fused<mqa_bwd_fused512_kernel>(grid512, 256, lds512, stream, a, dq32);
   } else {
-    const int lds = 2 * (4096 + 4096 + 256) + 32768 + 2 * 16384;
     const bool ragged = (N % 32) != 0;
-    const int mode = dq_mode != OSUF_DQ_SLABS ? 0 : (a.g_bf16 ? 1 : 2);
-    void (*kern)(AttnArgs, float*) =
-        mode == 0 ? (ragged ? mqa_bwd_fused_kernel<0, true> : mqa_bwd_fused_kernel<0, false>)
-      : mode == 1 ? (ragged ? mqa_bwd_fused_kernel<1, true> : mqa_bwd_fused_kernel<1, false>)
-                  : (ragged ? mqa_bwd_fused_kernel<2, true> : mqa_bwd_fused_kernel<2, false>);
-    static bool attr_set[6] = {false, false, false, false, false, false};
-    if (!attr_set[2 * mode + ragged]) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      attr_set[2 * mode + ragged] = true;
+    if (dq_mode != OSUF_DQ_SLABS) {
+      if (ragged) launch_fused<mqa_bwd_fused_kernel<0, true>>(grid256, 512, lds256, stream, a, dq32);
+      else launch_fused<mqa_bwd_fused_kernel<0, false>>(grid256, 512, lds256, stream, a, dq32);
+    } else if (a.g_bf16) {
+      if (ragged) launch_fused<mqa_bwd_fused_kernel<1, true>>(grid256, 512, lds256, stream, a, dq32);
+      else launch_fused<mqa_bwd_fused_kernel<1, false>>(grid256, 512, lds256, stream, a, dq32);
+    } else {
+      if (ragged) launch_fused<mqa_bwd_fused_kernel<2, true>>(grid256, 512, lds256, stream, a, dq32);
+      else launch_fused<mqa_bwd_fused_kernel<2, false>>(grid256, 512, lds256, stream, a, dq32);
     }
-    hipLaunchKernelGGL(kern, dim3(((N + 255) / 256) * b8 * a.qsplit), dim3(512), lds, stream, a, dq32);
   }
-  if (a.qsplit > 1) {
-    const unsigned fb = (unsigned)((M * 32 + 255) / 256);
-    if (a.g_bf16) hipLaunchKernelGGL(dkv_finish_kernel<bf16_t>, dim3(fb), dim3(256), 0, stream, a.wsk, a.wsv, a.qsplit, (bf16_t*)dk, (bf16_t*)dv, lddk, M, N, a.kmul, rope_cos, rope_sin);
-    else hipLaunchKernelGGL(dkv_finish_kernel<float>, dim3(fb), dim3(256), 0, stream, a.wsk, a.wsv, a.qsplit, (float*)dk, (float*)dv, lddk, M, N, a.kmul, rope_cos, rope_sin);
-  }
-  const int qb = ew_grid(M * H * 8);
-  const int nkb = (N + 255) / 256, npad = (N + 31) / 32 * 32;
-  if (dq_mode != OSUF_DQ_SLABS) {
-    if (a.g_bf16) hipLaunchKernelGGL(dq_finish_kernel<bf16_t>, dim3(qb), dim3(256), 0, stream, dq32, (bf16_t*)dq, lddq, M, N, H, scale, rope_cos, rope_sin);
-    else hipLaunchKernelGGL(dq_finish_kernel<float>, dim3(qb), dim3(256), 0, stream, dq32, (float*)dq, lddq, M, N, H, scale, rope_cos, rope_sin);
-  } else if (a.g_bf16) {
-    hipLaunchKernelGGL((dq_reduce_kernel<bf16_t, bf16_t>), dim3(qb), dim3(256), 0, stream, (const bf16_t*)dq32, nkb, (bf16_t*)dq, lddq, B, N, npad, H, scale, rope_cos, rope_sin);
-  } else {
-    hipLaunchKernelGGL((dq_reduce_kernel<float, float>), dim3(qb), dim3(256), 0, stream, (const float*)dq32, nkb, (float*)dq, lddq, B, N, npad, H, scale, rope_cos, rope_sin);
-  }
+  if (a.qsplit > 1) launch_dkv_finish(a, stream);
+  launch_dq_finish(a, dq32, dq_mode == OSUF_DQ_SLABS, dq, lddq, stream);
   return osuf_launch_status();
 }
+extern "C" int osuf_mqa_bwd_fused(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
+                                  const float* lse2, const float* delta, void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H,
+                                  int N, int head_dim, float scale, int out_dtype, const float* rope_cos, const float* rope_sin,
+                                  float* workspace, long workspace_bytes, int qsplit, int dq_mode, hipStream_t stream) {
+  return mqa_bwd_fused_impl(q, ldq, k, ldk, v, ldv, dout, lddo, lse2, delta, dq, lddq, dk, dv, lddk, B, H, N, head_dim, scale, out_dtype, rope_cos,
+                            rope_sin, workspace, workspace_bytes, qsplit, dq_mode, false, stream);
+}
+// q pre-scaled by c = scale * log2 e (osuf_rope_cast_qs; lse2 from osuf_mqa_fwd_qs): p = exp2(Qs K^T - lse2) with no multiply; dq = scale dS K
+// as before (the gradient of the UN-scaled rotated q), dk = (scale / c) dS^T Qs.  The generated 512-key loop drops its 64 v_mul per pair.
+extern "C" int osuf_mqa_bwd_fused_qs(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
+                                     const float* lse2, const float* delta, void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H,
+                                     int N, int head_dim, float scale, int out_dtype, const float* rope_cos, const float* rope_sin,
+                                     float* workspace, long workspace_bytes, int qsplit, int dq_mode, hipStream_t stream) {
+  return mqa_bwd_fused_impl(q, ldq, k, ldk, v, ldv, dout, lddo, lse2, delta, dq, lddq, dk, dv, lddk, B, H, N, head_dim, scale, out_dtype, rope_cos,
+                            rope_sin, workspace, workspace_bytes, qsplit, dq_mode, true, stream);
+}
 
-static int rope_cast_impl(int dtype, const void* in, long ld_in, void* out, long ld_out, const float* cosb, const float* sinb,
-                          int M, int N, int n_rot_heads, int n_heads_total, int head_dim, float qmul, int n_q_heads, hipStream_t stream);
-extern "C" int osuf_rope_cast(int dtype, const void* in, long ld_in, void* out, long ld_out, const float* cosb, const float* sinb,
-                              int M, int N, int n_rot_heads, int n_heads_total, int head_dim, hipStream_t stream) {
-  return rope_cast_impl(dtype, in, ld_in, out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, head_dim, 1.f, 0, stream);
-}
-// as osuf_rope_cast, and the first n_q_heads heads (the queries) are multiplied by q_mul before their bf16 rounding (head_dim 64 only)
-extern "C" int osuf_rope_cast_qs(int dtype, const void* in, long ld_in, void* out, long ld_out, const float* cosb, const float* sinb,
-                                 int M, int N, int n_rot_heads, int n_heads_total, int head_dim, float q_mul, int n_q_heads, hipStream_t stream) {
-  if (head_dim != D || n_q_heads < 0 || n_q_heads > n_heads_total) return OSUF_EUNSUPPORTED;
-  return rope_cast_impl(dtype, in, ld_in, out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, head_dim, q_mul, n_q_heads, stream);
-}
 static int rope_cast_impl(int dtype, const void* in, long ld_in, void* out, long ld_out, const float* cosb, const float* sinb,
                           int M, int N, int n_rot_heads, int n_heads_total, int head_dim, float qmul, int n_q_heads, hipStream_t stream) {
   if (head_dim != D && (head_dim <= 0 || head_dim % 16)) return OSUF_EUNSUPPORTED;
@@ -2369,6 +2265,16 @@ static int rope_cast_impl(int dtype, const void* in, long ld_in, void* out, long
     hipLaunchKernelGGL(rope_cast_kernel<float>, dim3(ew_grid(tot)), dim3(256), 0, stream, (const float*)in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, qmul, n_q_heads);
   } else return OSUF_EUNSUPPORTED;
   return osuf_launch_status();
+}
+extern "C" int osuf_rope_cast(int dtype, const void* in, long ld_in, void* out, long ld_out, const float* cosb, const float* sinb,
+                              int M, int N, int n_rot_heads, int n_heads_total, int head_dim, hipStream_t stream) {
+  return rope_cast_impl(dtype, in, ld_in, out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, head_dim, 1.f, 0, stream);
+}
+// as osuf_rope_cast, and the first n_q_heads heads (the queries) are multiplied by q_mul before their bf16 rounding (head_dim 64 only)
+extern "C" int osuf_rope_cast_qs(int dtype, const void* in, long ld_in, void* out, long ld_out, const float* cosb, const float* sinb,
+                                 int M, int N, int n_rot_heads, int n_heads_total, int head_dim, float q_mul, int n_q_heads, hipStream_t stream) {
+  if (head_dim != D || n_q_heads < 0 || n_q_heads > n_heads_total) return OSUF_EUNSUPPORTED;
+  return rope_cast_impl(dtype, in, ld_in, out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, head_dim, q_mul, n_q_heads, stream);
 }
 
 extern "C" int osuf_rope_bwd(int dtype, const float* in, long ld_in, void* out, long ld_out, const float* cosb, const float* sinb,

@@ -42,7 +42,7 @@ static_assert(sizeof(osuf_linear_desc) == 56, "osuf_linear_desc is part of the C
 #define OSUF_DQ_SLABS 1
 #define OSUF_DQ_ATOMIC_256 2      /* force the 8-wave, 256-key sweep */
 #define OSUF_DQ_ATOMIC_512 3      /* force the 4-wave, 512-key sweep (N % 32 == 0) */
-#define OSUF_DQ_TIMING_512 4      /* the 512-key sweep WITHOUT its atomics: timing only, dq is zero */
+                                  /* (4: a timing-only build of the 512-key sweep, since removed; refused) */
 #define OSUF_DQ_ATOMIC_512A 5     /* the 512-key sweep with the generated, hand-placed loop (attn_bwd512_asm.inc) */
 #define OSUF_DQ_PREZEROED 0x100   /* flag: the dQ accumulator was zero-filled by osuf_mqa_fwd_zdq (no memset in the backward entry point) */
 
@@ -173,4 +173,10 @@ __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomic
 static inline int osuf_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? OSUF_OK : (int)e;
+}
+
+// lets KERNEL be launched with `bytes` of dynamic LDS (more than the 64 KiB default); takes effect once per kernel
+template <auto KERNEL> static void allow_lds(int bytes) {
+  static const bool once = ((void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), true);
+  (void)once;
 }

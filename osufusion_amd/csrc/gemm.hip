@@ -2416,12 +2416,6 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* Y, long ldy, int M
 // ---------------------------------------------------------------------------------------------------------
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// lets KERNEL be launched with `bytes` of dynamic LDS (more than the 64 KiB default); takes effect once per kernel
-template <auto KERNEL> static void allow_lds(int bytes) {
-  static const bool once = ((void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), true);
-  (void)once;
-}
-
 // OSUF_GEMM_BIG_MIN_TILES overrides when the 256^2 kernels are picked (tests: 1 forces them, 0 / "off" rules them out).  Read on
 // every call: tests flip it between calls.
 static std::optional<long> big_min_tiles_override() {

@@ -477,7 +477,7 @@ def fused_bwd_workspace(B: int, N: int, H: int, D: int, out_dtype: torch.dtype, 
     mqa_bwd(workspace=...): the dQ accumulator's memset (66 us per N = 4096 layer in front of the backward sweep) then rides the forward
     kernel, which is bound by the vector pipe and leaves HBM idle.  None where the path does not apply (head dim != 64, non-atomic dQ, OSUF_ATTN_NO_ZDQ=1)."""
     variant = ATTN_BWD_DEFAULT if variant is None else variant
-    if D != 64 or variant not in _FUSED_DQ_MODE or variant in (ATTN_FUSED_SLABS, ATTN_FUSED512_TIMING) or os.environ.get("OSUF_ATTN_NO_ZDQ") == "1":
+    if D != 64 or variant not in _FUSED_DQ_MODE or variant == ATTN_FUSED_SLABS or os.environ.get("OSUF_ATTN_NO_ZDQ") == "1":
         return None
     need = _lib.load().osuf_mqa_bwd_fused_workspace_bytes(B, H, N, _DT[out_dtype], qsplit, _FUSED_DQ_MODE[variant])
     if need <= 0:
@@ -550,9 +550,9 @@ def mqa_fwd_masked(qkv: torch.Tensor, mask4: torch.Tensor, B: int, N: int, H: in
 
 
 ATTN_AUTO, ATTN_PLAIN, ATTN_PIPE, ATTN_FUSED, ATTN_FUSED_SLABS = 0, 1, 2, 3, 4
-ATTN_FUSED256, ATTN_FUSED512, ATTN_FUSED512_TIMING = 5, 6, 7     # force the 256- / 512-key sweep of ATTN_FUSED; 512 without atomics (timing only)
+ATTN_FUSED256, ATTN_FUSED512 = 5, 6     # force the 256- / 512-key sweep of ATTN_FUSED (7 was a timing-only build, since removed)
 ATTN_FUSED512A = 8                                               # the 512-key sweep with the generated, hand-placed loop
-_FUSED_DQ_MODE = {ATTN_FUSED: 0, ATTN_FUSED_SLABS: 1, ATTN_FUSED256: 2, ATTN_FUSED512: 3, ATTN_FUSED512_TIMING: 4, ATTN_FUSED512A: 5}      # OSUF_DQ_*
+_FUSED_DQ_MODE = {ATTN_FUSED: 0, ATTN_FUSED_SLABS: 1, ATTN_FUSED256: 2, ATTN_FUSED512: 3, ATTN_FUSED512A: 5}      # OSUF_DQ_*
 # What AttentionFn.backward asks for: ATTN_FUSED = one key-stationary sweep, dQ by fp32 atomics (fastest at every UNet shape, measured
 # round 2); ATTN_FUSED_SLABS = the same sweep with a fixed-order dQ sum (bit-reproducible); ATTN_AUTO = the dQ + dK/dV kernel pair.
 ATTN_BWD_DEFAULT = ATTN_FUSED

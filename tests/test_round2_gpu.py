@@ -122,6 +122,15 @@ def test_attention_backward_rejects_unknown_variant():
     o, lse = ops.mqa_fwd(qkv, 1, 64, 4, 64, torch.bfloat16, 0.125)
     with pytest.raises(RuntimeError, match="invalid argument"):
         ops.mqa_bwd(qkv, o, o, lse, 1, 64, 4, 64, 0.125, variant=99)
+    # dq_mode 4 was the no-atomics timing build of the 512-key sweep (since removed): the number stays refused, and sizes no workspace
+    from osufusion_amd import _lib
+    assert _lib.load().osuf_mqa_bwd_fused_workspace_bytes(1, 4, 64, 0, 0, 4) == 0
+    dqkv, ws = torch.empty(1, 64, 6 * 64, device=DEV), torch.empty(1 << 16, device=DEV)
+    delta = torch.zeros(1, 4, 64, device=DEV)
+    q, st = qkv.data_ptr(), torch.cuda.current_stream().cuda_stream
+    with pytest.raises(RuntimeError, match="invalid argument"):
+        ops.call("osuf_mqa_bwd_fused", q, 384, q + 512, 384, q + 640, 384, o.data_ptr(), 256, lse.data_ptr(), delta.data_ptr(), dqkv.data_ptr(), 384,
+                 dqkv.data_ptr() + 1024, dqkv.data_ptr() + 1280, 384, 1, 4, 64, 64, 0.125, 0, None, None, ws.data_ptr(), ws.numel() * 4, 0, 4, st)
 
 
 # ---- clip + AdamW (trainer.py:305-307) -----------------------------------------------------------------------

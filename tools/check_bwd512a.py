@@ -1,9 +1,7 @@
 """The hand-placed 512-key attention backward (ATTN_FUSED512A) against the compiled 512-key sweep (ATTN_FUSED512): dK / dV must be bit-identical
 (same fragment maps, same order of every accumulation), dQ equal up to the order of its float atomics; then timings.
     python tools/check_bwd512a.py [--time]"""
-import os
 import sys
-os.environ["OSUF_ALLOW_TIMING_BUILDS"] = "1"
 sys.path.insert(0, "/root/repo")
 import torch
 from osufusion_amd import ops
@@ -50,7 +48,7 @@ def main():
             ops.call("osuf_attn_delta", do.data_ptr(), H * D, o.data_ptr(), H * D, 1, delta.data_ptr(), B, H, N, D, torch.cuda.current_stream().cuda_stream)
             f = 8.0 * B * H * N * N * D
             row = []
-            for name, var in (("fused512", ops.ATTN_FUSED512), ("fused512a", ops.ATTN_FUSED512A), ("fused512-noatomics", ops.ATTN_FUSED512_TIMING)):
+            for name, var in (("fused512", ops.ATTN_FUSED512), ("fused512a", ops.ATTN_FUSED512A)):
                 fn = lambda: ops.mqa_bwd(qkv, o, do, lse, B, N, H, D, D ** -0.5, torch.bfloat16, None, None, variant=var, delta=delta)
                 for _ in range(2): fn()
                 torch.cuda.synchronize()
