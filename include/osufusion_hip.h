@@ -204,6 +204,21 @@ int osuf_mqa_bwd_masked(const void* q, long ldq, const void* k, long ldk, const 
                         const float* lse2, const float* delta, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k,
                         void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H, int N, int head_dim, float scale,
                         int out_dtype, float* dbias, hipStream_t stream);
+/* Cross-attention: osuf_mqa_fwd_masked with keys and values of their own length.  q / o: [B*Nq] rows, k / v: [B*Nk] rows, one K/V head,
+ * lse2 [B][H][Nq].  mask (may be NULL: no bias): bf16, element strides over (batch, head, query, key) of a (B, H, Nq, Nk) bias, 0 for a
+ * broadcast dimension.  Head dims 16, 32, 64 and 128 all run the generic kernels (no tuned path).
+ * replaces: F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask) at attention.py:94-99 when k / v are longer or shorter than q. */
+int osuf_xattn_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
+                   float* lse2, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k, int B, int H, int Nq, int Nk,
+                   int head_dim, float scale, hipStream_t stream);
+/* The backward of osuf_xattn_fwd: lse2 from that forward, delta [B][H][Nq] from osuf_attn_delta with N = Nq.  dq: [B*Nq][lddq], head h at
+ * h * head_dim; dk / dv: [B*Nk][lddk], summed over the H query heads; all in out_dtype (OSUF_DT_F32 or OSUF_DT_BF16).  dbias (may be NULL;
+ * OSUF_EINVAL without a mask): dense fp32 [B][H][Nq][Nk], 16-byte aligned, never accumulated into.
+ * replaces: the backward of F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask) at attention.py:94-99 (as osuf_xattn_fwd). */
+int osuf_xattn_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
+                   const float* lse2, const float* delta, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k,
+                   void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H, int Nq, int Nk, int head_dim, float scale,
+                   int out_dtype, float* dbias, hipStream_t stream);
 int osuf_attn_delta(const void* dout, long lddo, const void* o, long ldo, int o_dtype, float* delta, int B, int H, int N,
                     int head_dim, hipStream_t stream);
 /* dq / dk / dv are written in out_dtype (OSUF_DT_F32 or OSUF_DT_BF16).  rope_cos / rope_sin ([N][32] fp32, or both NULL): q and k

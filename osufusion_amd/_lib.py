@@ -52,6 +52,8 @@ SIGNATURES = {
     "osuf_mqa_fwd_rope": [P, L, P, L, P, L, P, L, I, P, I, I, I, I, F, P, P, F, P, L, P, P],
     "osuf_mqa_fwd_masked": [P, L, P, L, P, L, P, L, I, P, P, L, L, L, L, I, I, I, I, F, P],
     "osuf_mqa_bwd_masked": [P, L, P, L, P, L, P, L, P, P, P, L, L, L, L, P, L, P, P, L, I, I, I, I, F, I, P, P],
+    "osuf_xattn_fwd": [P, L, P, L, P, L, P, L, I, P, P, L, L, L, L, I, I, I, I, I, F, P],
+    "osuf_xattn_bwd": [P, L, P, L, P, L, P, L, P, P, P, L, L, L, L, P, L, P, P, L, I, I, I, I, I, F, I, P, P],
     "osuf_attn_delta": [P, L, P, L, I, P, I, I, I, I, P],
     "osuf_mqa_bwd_dq": [P, L, P, L, P, L, P, L, P, P, P, L, I, I, I, I, F, I, P, P, I, P],
     "osuf_mqa_bwd_dkv": [P, L, P, L, P, L, P, L, P, P, P, P, L, I, I, I, I, F, I, P, P, P, L, I, I, P],

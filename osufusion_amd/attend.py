@@ -15,6 +15,7 @@ from typing import Optional
 
 import torch
 
+from . import cross_attend as Xa
 from . import ops
 
 # ---------------------------------------------------------------------------------------------------------
@@ -160,7 +161,10 @@ class AttendFn(torch.autograd.Function):
 
 
 def attend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """AttendFn when autograd has something to differentiate, else the bare launches (nothing kept)."""
+    """AttendFn when autograd has something to differentiate, else the bare launches (nothing kept).  k / v of another length than q:
+    cross_attend.py (the generic kernels with their own key count)."""
+    if k.shape[2] != q.shape[2]:
+        return Xa.cross_attend(q, k, v, attn_mask)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (attn_mask is not None and attn_mask.requires_grad)):
         return AttendFn.apply(q, k, v, attn_mask)
     return attend_forward(q, k, v, attn_mask)[0]

@@ -129,6 +129,7 @@ struct AttnArgs {
   int qsplit;                                   // dK/dV: > 1 = the query range is cut into qsplit parts (short sequences: more workgroups),
   float* wsk; float* wsv;                       //        per-part partial sums in [qsplit][B*N][64] workspaces, summed by dkv_finish_kernel
   const bf16_t* mask; long mask_b, mask_h, mask_q, mask_k;   // osuf_mqa_fwd_masked: additive bf16 score bias, element strides (0 = broadcast)
+  int Nk;                                       // key rows per batch element: = N everywhere but osuf_xattn_* (read by the kernels of attn_generic.hpp only)
 };
 
 // cooperative K/V tile stage: NT threads move one 64-key tile (64 x 128 B of K and of V = 512 + 512 16-B chunks)
@@ -1865,7 +1866,7 @@ static int fill_fwd_args(AttnArgs& a, const void* q, long ldq, const void* k, lo
   if (B <= 0 || H <= 0 || N <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || !al16(q) || !al16(k) || !al16(v) || !al16(o)) return OSUF_EINVAL;
   a = AttnArgs{};
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.o = o; a.ldo = ldo; a.o_is_f32 = o_dtype == OSUF_DT_F32; a.lse2 = lse2; a.B = B; a.H = H; a.N = N; a.scale = scale; a.cexp = scale * kLog2e; a.kmul = scale;
+  a.o = o; a.ldo = ldo; a.o_is_f32 = o_dtype == OSUF_DT_F32; a.lse2 = lse2; a.B = B; a.H = H; a.N = N; a.Nk = N; a.scale = scale; a.cexp = scale * kLog2e; a.kmul = scale;
   return OSUF_OK;
 }
 struct FwdRope { const float* cos; const float* sin; float qmul; void* qout; long ldqo; };   // osuf_mqa_fwd_rope's extra operands
@@ -1955,7 +1956,7 @@ static int fill_bwd_args(AttnArgs& a, const void* q, long ldq, const void* k, lo
   a = AttnArgs{};
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
   a.lse2 = const_cast<float*>(lse2); a.dout = (const bf16_t*)dout; a.lddo = lddo; a.delta = delta;
-  a.B = B; a.H = H; a.N = N; a.scale = scale; a.cexp = scale * kLog2e; a.kmul = scale; a.qsplit = 1;
+  a.B = B; a.H = H; a.N = N; a.Nk = N; a.scale = scale; a.cexp = scale * kLog2e; a.kmul = scale; a.qsplit = 1;
   return OSUF_OK;
 }
 
@@ -1985,6 +1986,67 @@ extern "C" int osuf_mqa_bwd_masked(const void* q, long ldq, const void* k, long 
   } else {
     hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<128, true>), grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
     hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<128, true>), ggrid, dim3(256), 2 * 32 * 256 + 256, stream, a, head_dim, dbias);
+  }
+  return osuf_launch_status();
+}
+
+// Cross-attention (attention.py:94-99 with k / v of their own length): Nq query rows and Nk key rows per batch element, one K/V head, mask
+// (may be NULL) as osuf_mqa_fwd_masked over (batch, head, query, key).  Every head dim (64 included) runs the generic kernels.
+template <int DP, bool MASKED> static void launch_xattn_fwd(const AttnArgs& a, int head_dim, hipStream_t stream) {
+  const int nvb = ((a.N + 31) / 32) * a.H;
+  hipLaunchKernelGGL((mqa_gen_fwd_kernel<DP, MASKED>), dim3((nvb + 3) / 4, a.B), dim3(256), 2 * 64 * 2 * DP, stream, a, head_dim);
+}
+extern "C" int osuf_xattn_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
+                              float* lse2, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k, int B, int H, int Nq, int Nk,
+                              int head_dim, float scale, hipStream_t stream) {
+  AttnArgs a;
+  const int rc = fill_fwd_args(a, q, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, H, Nq, head_dim, scale);
+  if (rc) return rc;
+  if (Nk <= 0 || !lse2 || scale == 0.f) return OSUF_EINVAL;
+  a.Nk = Nk;
+  a.mask = (const bf16_t*)mask; a.mask_b = mask_b; a.mask_h = mask_h; a.mask_q = mask_q; a.mask_k = mask_k;
+  const int dp = head_dim == D ? 64 : gen_dp(head_dim);
+  if (mask) {
+    if (dp == 32) launch_xattn_fwd<32, true>(a, head_dim, stream);
+    else if (dp == 64) launch_xattn_fwd<64, true>(a, head_dim, stream);
+    else launch_xattn_fwd<128, true>(a, head_dim, stream);
+  } else {
+    if (dp == 32) launch_xattn_fwd<32, false>(a, head_dim, stream);
+    else if (dp == 64) launch_xattn_fwd<64, false>(a, head_dim, stream);
+    else launch_xattn_fwd<128, false>(a, head_dim, stream);
+  }
+  return osuf_launch_status();
+}
+
+// The backward of osuf_xattn_fwd: lse2 / delta [B][H][Nq] (osuf_attn_delta with N = Nq), dq rows [B*Nq], dk / dv rows [B*Nk] (summed over
+// the H query heads), dbias (may be NULL; needs mask) dense fp32 [B][H][Nq][Nk].
+template <int DP, bool MASKED> static void launch_xattn_bwd(const AttnArgs& a, int head_dim, float* dbias, hipStream_t stream) {
+  const int nvb = ((a.N + 31) / 32) * a.H;
+  hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<DP, MASKED>), dim3((nvb + 3) / 4, a.B), dim3(256), 2 * 64 * 2 * DP, stream, a, head_dim);
+  hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<DP, MASKED>), dim3(((a.Nk + 127) / 128) * a.B), dim3(256), 2 * 32 * 2 * DP + 256, stream, a, head_dim, dbias);
+}
+extern "C" int osuf_xattn_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
+                              const float* lse2, const float* delta, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k,
+                              void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H, int Nq, int Nk, int head_dim, float scale,
+                              int out_dtype, float* dbias, hipStream_t stream) {
+  AttnArgs a;
+  int rc = fill_bwd_args(a, q, ldq, k, ldk, v, ldv, dout, lddo, lse2, delta, B, H, Nq, head_dim, scale);
+  if (rc) return rc;
+  if (Nk <= 0 || !lse2 || !delta || scale == 0.f || lddq % 8 || lddk % 8 || !al16(dq) || !al16(dk) || !al16(dv) ||
+      (out_dtype != OSUF_DT_F32 && out_dtype != OSUF_DT_BF16) || (dbias && (!mask || !al16(dbias))))
+    return OSUF_EINVAL;
+  a.Nk = Nk;
+  a.mask = (const bf16_t*)mask; a.mask_b = mask_b; a.mask_h = mask_h; a.mask_q = mask_q; a.mask_k = mask_k;
+  a.dq = dq; a.lddq = lddq; a.dk = dk; a.dv = dv; a.lddk = lddk; a.g_bf16 = out_dtype == OSUF_DT_BF16;
+  const int dp = head_dim == D ? 64 : gen_dp(head_dim);
+  if (mask) {
+    if (dp == 32) launch_xattn_bwd<32, true>(a, head_dim, dbias, stream);
+    else if (dp == 64) launch_xattn_bwd<64, true>(a, head_dim, dbias, stream);
+    else launch_xattn_bwd<128, true>(a, head_dim, dbias, stream);
+  } else {
+    if (dp == 32) launch_xattn_bwd<32, false>(a, head_dim, nullptr, stream);
+    else if (dp == 64) launch_xattn_bwd<64, false>(a, head_dim, nullptr, stream);
+    else launch_xattn_bwd<128, false>(a, head_dim, nullptr, stream);
   }
   return osuf_launch_status();
 }

@@ -4,6 +4,9 @@
 // there -- written once for a padded head dim DP in {32, 64, 128} (a 16-wide head runs as DP = 32 with zero columns), without the
 // software pipelines.  Tiles are [rows][DP] bf16 images, 16-byte chunks xor-swizzled by the row; both row reads (ds_read_b128) and
 // column reads (ds_read_b64_tr_b16) recompute the writer's address function, so any DP works by construction.
+// The three attention kernels take N query rows and Nk key rows per batch element (AttnArgs::Nk; every self-attention entry point sets
+// Nk = N, osuf_xattn_* pass their own): q, o, dO, dq, lse2, delta and the mask's query stride go by N, k, v, dk, dv and the mask's key
+// stride by Nk.
 // Included by attn.hip (it uses AttnArgs, acc_to_frag, fast_exp2, store4, kLog2e).
 #pragma once
 
@@ -92,15 +95,15 @@ __global__ __launch_bounds__(256) void mqa_gen_fwd_kernel(AttnArgs a, int hd) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
-  const int ntiles = (a.N + 63) >> 6;
+  const int ntiles = (a.Nk + 63) >> 6;
   for (int j = 0; j < ntiles; ++j) {
     __syncthreads();                                                   // the previous tile has been consumed
-    T::fill(smem, a.k + (long)b * a.N * a.ldk, a.ldk, 64, j * 64, a.N, hd, tid, 256);
-    T::fill(smem + TILE, a.v + (long)b * a.N * a.ldv, a.ldv, 64, j * 64, a.N, hd, tid, 256);
+    T::fill(smem, a.k + (long)b * a.Nk * a.ldk, a.ldk, 64, j * 64, a.Nk, hd, tid, 256);
+    T::fill(smem + TILE, a.v + (long)b * a.Nk * a.ldv, a.ldv, 64, j * 64, a.Nk, hd, tid, 256);
     __syncthreads();
     f32x16 s[2];
     if constexpr (MASKED) {                                            // the bias starts the accumulator, in units of the raw dot product
-      // (loads issued ahead of the MFMAs; indices clamped instead of branched on: rows / keys past N are discarded below)
+      // (loads issued ahead of the MFMAs; indices clamped instead of branched on: rows past N / keys past Nk are discarded below)
       const bf16_t* mrow = a.mask + (long)b * a.mask_b + (long)h * a.mask_h + (long)(qok ? qrow : 0) * a.mask_q;
       const float inv_scale = 1.f / a.scale;
 #pragma unroll
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(256) void mqa_gen_fwd_kernel(AttnArgs a, int hd) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          s[kt][r] = bf16_to_f32(mrow[(long)(key < a.N ? key : a.N - 1) * a.mask_k]) * inv_scale;
+          s[kt][r] = bf16_to_f32(mrow[(long)(key < a.Nk ? key : a.Nk - 1) * a.mask_k]) * inv_scale;
         }
     } else {
 #pragma unroll
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(256) void mqa_gen_fwd_kernel(AttnArgs a, int hd) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (key >= a.N) s[kt][r] = -INFINITY;
+        if (key >= a.Nk) s[kt][r] = -INFINITY;
         mx = fmaxf(mx, s[kt][r]);
       }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * c;
@@ -199,14 +202,14 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
   for (int i = 0; i < T::DT; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-  const int ntiles = (a.N + 63) >> 6;
+  const int ntiles = (a.Nk + 63) >> 6;
   for (int j = 0; j < ntiles; ++j) {
     __syncthreads();
-    T::fill(smem, a.k + (long)b * a.N * a.ldk, a.ldk, 64, j * 64, a.N, hd, tid, 256);
-    T::fill(smem + TILE, a.v + (long)b * a.N * a.ldv, a.ldv, 64, j * 64, a.N, hd, tid, 256);
+    T::fill(smem, a.k + (long)b * a.Nk * a.ldk, a.ldk, 64, j * 64, a.Nk, hd, tid, 256);
+    T::fill(smem + TILE, a.v + (long)b * a.Nk * a.ldv, a.ldv, 64, j * 64, a.Nk, hd, tid, 256);
     __syncthreads();
     f32x16 s[2], dp[2];
-    if constexpr (MASKED) {                                            // as in the forward: bias / scale, rows / keys past N clamped
+    if constexpr (MASKED) {                                            // as in the forward: bias / scale, rows past N / keys past Nk clamped
       const bf16_t* mrow = a.mask + (long)b * a.mask_b + (long)h * a.mask_h + (long)(qok ? qrow : 0) * a.mask_q;
       const float inv_scale = 1.f / a.scale;
 #pragma unroll
@@ -214,7 +217,7 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          s[kt][r] = bf16_to_f32(mrow[(long)(key < a.N ? key : a.N - 1) * a.mask_k]) * inv_scale;
+          s[kt][r] = bf16_to_f32(mrow[(long)(key < a.Nk ? key : a.Nk - 1) * a.mask_k]) * inv_scale;
         }
     } else {
 #pragma unroll
@@ -236,10 +239,10 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float p = fast_exp2(fmaf(s[kt][r], c, -L2));                  // keys past N: zero K rows -> their dS meets zero K rows below
+        float p = fast_exp2(fmaf(s[kt][r], c, -L2));                  // keys past Nk: zero K rows -> their dS meets zero K rows below
         if constexpr (MASKED) {                                        // (a clamped bias could make p large there: drop it outright)
           const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          p = key < a.N ? p : 0.f;
+          p = key < a.Nk ? p : 0.f;
         }
         s[kt][r] = p * (dp[kt][r] - dl);
       }
@@ -257,22 +260,22 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
 // ---- backward, dK / dV (key-stationary): 4 waves = 128 keys sweep every (head, 32-query block) pair; gradients of the ROTATED k (x scale) and v
 // MASKED: the bias starts S as in the forward; here the accumulator rows are queries and the lanes keys, so the 32 lanes of a row read 32
 // consecutive keys of mask[b][h][q][*].  dbias != null (MASKED only): dS = P (dP - delta) -- dL/dbias, the bias being added to the scaled
-// scores -- is stored to the dense fp32 [B][H][N][N] dbias for every valid (query, key); padded rows and keys are not written.
+// scores -- is stored to the dense fp32 [B][H][N][Nk] dbias for every valid (query, key); padded rows and keys are not written.
 template <int DP, bool MASKED = false>
 __global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd, float* dbias) {
   using T = GenTile<DP>;
   extern __shared__ __attribute__((aligned(16))) char smem[];        // Q image 32 x RB | dO image 32 x RB | lse 128 | delta 128
   constexpr int TILE = 32 * T::RB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
-  const int nkb = (a.N + 127) / 128;
+  const int nkb = (a.Nk + 127) / 128;
   const int b = blockIdx.x / nkb, kb = blockIdx.x - b * nkb;
   const int key = kb * 128 + wave * 32 + lr;
-  const bool kok = key < a.N;
+  const bool kok = key < a.Nk;
   const float c = a.cexp;
   const int nqb = (a.N + 31) >> 5;
   bf16x8 kf[T::KS], vf[T::KS];
-  gen_load_row_frags<DP>(kf, a.k + ((long)b * a.N + key) * a.ldk, kok, hd, lh);
-  gen_load_row_frags<DP>(vf, a.v + ((long)b * a.N + key) * a.ldv, kok, hd, lh);
+  gen_load_row_frags<DP>(kf, a.k + ((long)b * a.Nk + key) * a.ldk, kok, hd, lh);
+  gen_load_row_frags<DP>(vf, a.v + ((long)b * a.Nk + key) * a.ldv, kok, hd, lh);
   f32x16 dk[T::DT], dv[T::DT];
 #pragma unroll
   for (int i = 0; i < T::DT; ++i)
@@ -292,7 +295,7 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd
       __syncthreads();
       f32x16 s, dp;
       if constexpr (MASKED) {
-        const bf16_t* mcol = a.mask + (long)b * a.mask_b + (long)h * a.mask_h + (long)(kok ? key : a.N - 1) * a.mask_k;
+        const bf16_t* mcol = a.mask + (long)b * a.mask_b + (long)h * a.mask_h + (long)(kok ? key : a.Nk - 1) * a.mask_k;
         const float inv_scale = 1.f / a.scale;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -320,11 +323,11 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd
       }
       if constexpr (MASKED) {
         if (dbias && kok) {                                            // lanes = 32 consecutive keys of one query row: 128-byte rows
-          float* drow = dbias + (((long)b * a.H + h) * a.N + pb * 32) * a.N + key;
+          float* drow = dbias + (((long)b * a.H + h) * a.N + pb * 32) * a.Nk + key;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int qi = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (pb * 32 + qi < a.N) drow[(long)qi * a.N] = ds[r];
+            if (pb * 32 + qi < a.N) drow[(long)qi * a.Nk] = ds[r];
           }
         }
       }
@@ -340,8 +343,8 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd
       }
     }
   if (kok) {
-    gen_store_row<DP>(a.dk, ((long)b * a.N + key) * a.lddk, a.g_bf16, dk, a.scale, hd, lh);
-    gen_store_row<DP>(a.dv, ((long)b * a.N + key) * a.lddk, a.g_bf16, dv, 1.f, hd, lh);
+    gen_store_row<DP>(a.dk, ((long)b * a.Nk + key) * a.lddk, a.g_bf16, dk, a.scale, hd, lh);
+    gen_store_row<DP>(a.dv, ((long)b * a.Nk + key) * a.lddk, a.g_bf16, dv, 1.f, hd, lh);
   }
 }
 

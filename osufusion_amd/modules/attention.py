@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import attend as At
+from .. import cross_attend as Xa
 from .. import functional as Fn
 from .. import runtime as rt
 
@@ -36,14 +37,13 @@ class RotaryPositionEmbedding(nn.Module):
 
 class Attend(nn.Module):
     """attention.py:61-101: q, k, v -> bf16, softmax(q k^T / sqrt(d) + attn_mask.to(bf16)) v, back to the input dtype.  k / v carry 1 or
-    H heads.  Differentiable in q, k, v and a floating-point attn_mask (a k / v with one head gets the gradient summed over the query
-    heads).  Rows whose every key is masked with -inf are NaN, as in SDPA."""
+    H heads and may be of another length than q (cross-attention: osufusion_amd/cross_attend.py).  Differentiable in q, k, v and a
+    floating-point attn_mask (a k / v with one head gets the gradient summed over the query heads).  Rows whose every key is masked with
+    -inf are NaN, as in SDPA."""
 
     def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         rt.require_gpu(q)
-        B, H, N, D = q.shape
+        D = Xa.check_shapes(q, k, v, attn_mask)[4]
         if D not in (16, 32, 64, 128):
             raise NotImplementedError("the HIP attention kernels cover head dims 16, 32, 64 and 128")
-        if k.shape[1] not in (1, H) or v.shape[1] != k.shape[1]:
-            raise ValueError(f"k / v must carry 1 or {H} heads (got {k.shape[1]} / {v.shape[1]})")
         return At.attend(q, k, v, attn_mask)
