@@ -47,16 +47,18 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* y, long ldy, dou
   const ColGeom cg = col_geom(chunks);
   const int ch = threadIdx.x % cg.cp, rl = threadIdx.x / cg.cp;
   const int n_begin = blockIdx.x * rows_per_block, n_end = min(L, n_begin + rows_per_block);
-  float s1 = 0.f, s2 = 0.f;
+  // fp64 from the first addition on: the variance is E[y^2] - mean^2, and a thread's 64 squares summed in fp32 cost rstd a relative
+  // 6e-6 at mean / std = 30 (the fp64 sums of the GEMM epilogue: 3e-8); a product of two fp32 values is exact in fp64
+  double s1 = 0.0, s2 = 0.0;
   if (rl < cg.rp) {
     for (int n = n_begin + rl; n < n_end; n += cg.rp) {
       float v[8];
       load8(y + ((long)b * L + n) * ldy + ch * 8, v);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { s1 += v[e]; s2 += v[e] * v[e]; }
+      for (int e = 0; e < 8; ++e) { const double d = (double)v[e]; s1 += d; s2 = fma(d, d, s2); }
     }
   }
-  const double d1 = group_sum_f64((double)s1), d2 = group_sum_f64((double)s2);
+  const double d1 = group_sum_f64(s1), d2 = group_sum_f64(s2);
   __shared__ double red[4][2];
   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = d1; red[threadIdx.x >> 6][1] = d2; }
   __syncthreads();
