@@ -1850,13 +1850,12 @@ __global__ __launch_bounds__(256) void rope_bwd_kernel(const float* in, long ld_
 // ------------------------------------------------------------------------------------------------------
 #include "attn_generic.hpp"
 
-static inline int ew_grid(long total_threads) {
+static inline int attn_ew_grid(long total_threads) {        // common.hpp's ew_grid with twice the cap
   long blocks = (total_threads + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
 }
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // head dims served by the generic kernels of attn_generic.hpp (64 has the tuned kernels of this file): padded tile width, 0 = unsupported
 static int gen_dp(int head_dim) { return head_dim == 16 || head_dim == 32 ? 32 : head_dim == 128 ? 128 : 0; }
 // argument checks and AttnArgs of the forward entry points
@@ -2057,16 +2056,16 @@ extern "C" int osuf_attn_delta(const void* dout, long lddo, const void* o, long 
   if (head_dim != D && !gen_dp(head_dim)) return OSUF_EUNSUPPORTED;
   if (B <= 0 || H <= 0 || N <= 0 || ldo % 8 || lddo % 8 || !al16(o) || !al16(dout)) return OSUF_EINVAL;
   if (head_dim != D) {
-    const int gb = ew_grid((long)B * N * H);
+    const int gb = attn_ew_grid((long)B * N * H);
     if (o_dtype == OSUF_DT_F32) hipLaunchKernelGGL(attn_delta_gen_kernel<float>, dim3(gb), dim3(256), 0, stream, (const bf16_t*)dout, lddo, (const float*)o, ldo, delta, B, H, N, head_dim);
     else hipLaunchKernelGGL(attn_delta_gen_kernel<bf16_t>, dim3(gb), dim3(256), 0, stream, (const bf16_t*)dout, lddo, (const bf16_t*)o, ldo, delta, B, H, N, head_dim);
     return osuf_launch_status();
   }
   const long tot = (long)B * N * H * 8;
   if (o_dtype == OSUF_DT_F32) {
-    hipLaunchKernelGGL(attn_delta_kernel<float>, dim3(ew_grid(tot)), dim3(256), 0, stream, (const bf16_t*)dout, lddo, (const float*)o, ldo, delta, B, H, N);
+    hipLaunchKernelGGL(attn_delta_kernel<float>, dim3(attn_ew_grid(tot)), dim3(256), 0, stream, (const bf16_t*)dout, lddo, (const float*)o, ldo, delta, B, H, N);
   } else {
-    hipLaunchKernelGGL(attn_delta_kernel<bf16_t>, dim3(ew_grid(tot)), dim3(256), 0, stream, (const bf16_t*)dout, lddo, (const bf16_t*)o, ldo, delta, B, H, N);
+    hipLaunchKernelGGL(attn_delta_kernel<bf16_t>, dim3(attn_ew_grid(tot)), dim3(256), 0, stream, (const bf16_t*)dout, lddo, (const bf16_t*)o, ldo, delta, B, H, N);
   }
   return osuf_launch_status();
 }
@@ -2225,7 +2224,7 @@ template <auto KERNEL> static void launch_fused(dim3 grid, int threads, int lds,
 static void launch_dq_finish(const AttnArgs& a, const float* dq32, bool slabs, void* dq, long lddq, hipStream_t stream) {
   const int B = a.B, N = a.N, H = a.H;
   const long M = (long)B * N;
-  const int qb = ew_grid(M * H * 8);
+  const int qb = attn_ew_grid(M * H * 8);
   const int nkb = (N + 255) / 256, npad = (N + 31) / 32 * 32;
   if (!slabs) {
     if (a.g_bf16) hipLaunchKernelGGL(dq_finish_kernel<bf16_t>, dim3(qb), dim3(256), 0, stream, dq32, (bf16_t*)dq, lddq, M, N, H, a.scale, a.rcos, a.rsin);
@@ -2314,7 +2313,7 @@ static int rope_cast_impl(int dtype, const void* in, long ld_in, void* out, long
   if (head_dim != D && (head_dim <= 0 || head_dim % 16)) return OSUF_EUNSUPPORTED;
   if (M <= 0 || N <= 0 || M % N || ld_in % 8 || ld_out % 8 || !al16(in) || !al16(out)) return OSUF_EINVAL;
   if (head_dim != D) {                                            // any head dim that is a multiple of 16: tables [N][head_dim / 2]
-    const int gb = ew_grid((long)M * n_heads_total * (head_dim / 16));
+    const int gb = attn_ew_grid((long)M * n_heads_total * (head_dim / 16));
     if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL((rope_gen_kernel<bf16_t, bf16_t, 1>), dim3(gb), dim3(256), 0, stream, (const bf16_t*)in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, head_dim);
     else if (dtype == OSUF_DT_F32) hipLaunchKernelGGL((rope_gen_kernel<float, bf16_t, 1>), dim3(gb), dim3(256), 0, stream, (const float*)in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, head_dim);
     else return OSUF_EUNSUPPORTED;
@@ -2322,9 +2321,9 @@ static int rope_cast_impl(int dtype, const void* in, long ld_in, void* out, long
   }
   const long tot = (long)M * n_heads_total * 4;
   if (dtype == OSUF_DT_BF16) {
-    hipLaunchKernelGGL(rope_cast_kernel<bf16_t>, dim3(ew_grid(tot)), dim3(256), 0, stream, (const bf16_t*)in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, qmul, n_q_heads);
+    hipLaunchKernelGGL(rope_cast_kernel<bf16_t>, dim3(attn_ew_grid(tot)), dim3(256), 0, stream, (const bf16_t*)in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, qmul, n_q_heads);
   } else if (dtype == OSUF_DT_F32) {
-    hipLaunchKernelGGL(rope_cast_kernel<float>, dim3(ew_grid(tot)), dim3(256), 0, stream, (const float*)in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, qmul, n_q_heads);
+    hipLaunchKernelGGL(rope_cast_kernel<float>, dim3(attn_ew_grid(tot)), dim3(256), 0, stream, (const float*)in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, qmul, n_q_heads);
   } else return OSUF_EUNSUPPORTED;
   return osuf_launch_status();
 }
@@ -2344,7 +2343,7 @@ extern "C" int osuf_rope_bwd(int dtype, const float* in, long ld_in, void* out, 
   if (head_dim != D && (head_dim <= 0 || head_dim % 16)) return OSUF_EUNSUPPORTED;
   if (M <= 0 || N <= 0 || M % N || ld_in % 8 || ld_out % 8 || !al16(in) || !al16(out)) return OSUF_EINVAL;
   if (head_dim != D) {
-    const int gb = ew_grid((long)M * n_heads_total * (head_dim / 16));
+    const int gb = attn_ew_grid((long)M * n_heads_total * (head_dim / 16));
     if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL((rope_gen_kernel<float, bf16_t, -1>), dim3(gb), dim3(256), 0, stream, in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, head_dim);
     else if (dtype == OSUF_DT_F32) hipLaunchKernelGGL((rope_gen_kernel<float, float, -1>), dim3(gb), dim3(256), 0, stream, in, ld_in, (float*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total, head_dim);
     else return OSUF_EUNSUPPORTED;
@@ -2352,9 +2351,9 @@ extern "C" int osuf_rope_bwd(int dtype, const float* in, long ld_in, void* out, 
   }
   const long tot = (long)M * n_heads_total * 4;
   if (dtype == OSUF_DT_BF16) {
-    hipLaunchKernelGGL(rope_bwd_kernel<bf16_t>, dim3(ew_grid(tot)), dim3(256), 0, stream, in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total);
+    hipLaunchKernelGGL(rope_bwd_kernel<bf16_t>, dim3(attn_ew_grid(tot)), dim3(256), 0, stream, in, ld_in, (bf16_t*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total);
   } else if (dtype == OSUF_DT_F32) {
-    hipLaunchKernelGGL(rope_bwd_kernel<float>, dim3(ew_grid(tot)), dim3(256), 0, stream, in, ld_in, (float*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total);
+    hipLaunchKernelGGL(rope_bwd_kernel<float>, dim3(attn_ew_grid(tot)), dim3(256), 0, stream, in, ld_in, (float*)out, ld_out, cosb, sinb, M, N, n_rot_heads, n_heads_total);
   } else return OSUF_EUNSUPPORTED;
   return osuf_launch_status();
 }

@@ -175,6 +175,21 @@ static inline int osuf_launch_status() {
   return e == hipSuccess ? OSUF_OK : (int)e;
 }
 
+// host side of the entry points: `using T` by dtype code around a launch (unknown code: OSUF_EUNSUPPORTED), the grid of a grid-stride
+// elementwise kernel, 16-byte pointer alignment, and the channel widths the 8-channel-chunk kernels serve
+#define DISPATCH_T(dtype, ...)                                  \
+  if ((dtype) == OSUF_DT_BF16) { using T = bf16_t; __VA_ARGS__; } \
+  else if ((dtype) == OSUF_DT_F32) { using T = float; __VA_ARGS__; } \
+  else return OSUF_EUNSUPPORTED;
+static inline int ew_grid(long total_threads) {
+  long blocks = (total_threads + 255) / 256;
+  if (blocks > 2048) blocks = 2048;                   // 256 CUs x 8, grid-stride the rest
+  if (blocks < 1) blocks = 1;
+  return (int)blocks;
+}
+static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool bad_c(int C) { return C <= 0 || (C & 7) || C > 2048; }
+
 // lets KERNEL be launched with `bytes` of dynamic LDS (more than the 64 KiB default); takes effect once per kernel
 template <auto KERNEL> static void allow_lds(int bytes) {
   static const bool once = ((void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), true);

@@ -5,13 +5,6 @@
 // second kernel adds them in workgroup order, so the results are bit-identical from launch to launch.
 #include "common.hpp"
 
-#define DISPATCH_T(dtype, ...)                                  \
-  if ((dtype) == OSUF_DT_BF16) { using T = bf16_t; __VA_ARGS__; } \
-  else if ((dtype) == OSUF_DT_F32) { using T = float; __VA_ARGS__; } \
-  else return OSUF_EUNSUPPORTED;
-
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline bool bad_rows_c(int C) { return C <= 0 || (C & 7) || C > 2048; }
 static inline int chunk_iters(int chunks) { const int j = (chunks + 63) / 64; return j <= 1 ? 1 : j <= 2 ? 2 : j <= 4 ? 4 : j <= 8 ? 8 : 0; }
 
 // ------------------------------------------------------------------------------------------------
@@ -173,7 +166,7 @@ static int adaln_bwd_blocks(int B, int L) {
 
 extern "C" int osuf_adaln_fwd(int dtype, const void* x, long ldx, void* out, long ldo, float* mr, const float* shift, const float* scale, long ldm,
                               int M, int C, int L, float eps, hipStream_t stream) {
-  if (bad_rows_c(C) || M <= 0 || L <= 0 || M % L || ldx % 8 || ldo % 8 || ldm % 4 || !al16(x) || !al16(out) || !al16(shift) || !al16(scale))
+  if (bad_c(C) || M <= 0 || L <= 0 || M % L || ldx % 8 || ldo % 8 || ldm % 4 || !al16(x) || !al16(out) || !al16(shift) || !al16(scale))
     return OSUF_EINVAL;
   const int J = chunk_iters(C / 8);
   long blocks = ((long)M + 3) / 4;
@@ -185,7 +178,7 @@ extern "C" int osuf_adaln_fwd(int dtype, const void* x, long ldx, void* out, lon
 }
 
 extern "C" long osuf_adaln_bwd_workspace_bytes(int M, int C, int L) {
-  if (bad_rows_c(C) || M <= 0 || L <= 0 || M % L || M / L > 65535) return 0;
+  if (bad_c(C) || M <= 0 || L <= 0 || M % L || M / L > 65535) return 0;
   const int B = M / L;
   return (long)B * adaln_bwd_blocks(B, L) * 2 * C * (long)sizeof(float);
 }
@@ -195,7 +188,7 @@ extern "C" long osuf_adaln_bwd_workspace_bytes(int M, int C, int L) {
 extern "C" int osuf_adaln_bwd(int dtype, const void* dy, long lddy, const void* x, long ldx, const void* dres, long ldr, void* dx, long lddx,
                               const float* mr, const float* scale, long ldm, float* dmod, long ldd, long off2, float* workspace,
                               long workspace_bytes, int M, int C, int L, hipStream_t stream) {
-  if (bad_rows_c(C) || M <= 0 || L <= 0 || M % L || M / L > 65535 || lddy % 8 || ldx % 8 || lddx % 8 || (dres && ldr % 8) || ldm % 4 || !mr || !dmod || !workspace)
+  if (bad_c(C) || M <= 0 || L <= 0 || M % L || M / L > 65535 || lddy % 8 || ldx % 8 || lddx % 8 || (dres && ldr % 8) || ldm % 4 || !mr || !dmod || !workspace)
     return OSUF_EINVAL;
   if (!al16(dy) || !al16(x) || !al16(dx) || (dres && !al16(dres)) || !al16(scale)) return OSUF_EINVAL;
   if (workspace_bytes < osuf_adaln_bwd_workspace_bytes(M, C, L)) return OSUF_EINVAL;

@@ -1,12 +1,6 @@
 // Layout conversion, diffusion-scheduler algebra and optimizer kernels (HBM-bound, 16 B per lane), gfx950.
 #include "common.hpp"
 
-static inline int ew_grid(long total_threads) {
-  long blocks = (total_threads + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
 #define GRID_STRIDE(idx, total) \
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < (total); idx += (long)gridDim.x * blockDim.x)
 
@@ -194,7 +188,6 @@ __global__ __launch_bounds__(256) void cast_flat_kernel(const float* src, bf16_t
 }
 
 // ------------------------------------------------------------------------------------------------------------
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" int osuf_ncl_to_rows(int dtype, const float* in, void* out, long ld, int width, int B, int C, int L, int KT, hipStream_t stream) {
   if (B <= 0 || C <= 0 || L <= 0 || KT <= 0 || width % 8 || ld % 8 || width < C * KT || width > ld || !al16(out)) return OSUF_EINVAL;

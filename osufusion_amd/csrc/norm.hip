@@ -5,19 +5,73 @@
 // Two skeletons: "column reduce" (a workgroup owns a row chunk of ONE sample, threads own 8-channel
 // chunks, partials go out as fp32 atomics to [B][C]) and "row-wise" (G lanes of a wave own one row,
 // wave64 xor-shuffle reductions).  All loads/stores are 16 B per lane.
+// ColLane decodes a thread's place in the column skeleton and col_reduce_rows is the reduction that ends its workgroups; mean_rstd_from_sums
+// and load_film are the GroupNorm arithmetic several kernels share.  The row-wise kernels keep their own prologues and folds: sharing them
+// moved their register counts (profiles/norm_fold_codegen.md).
 #include "common.hpp"
 
-struct ColGeom {
-  int cp, rp;          // chunk lanes, row lanes (cp * rp <= 256)
+static constexpr float kEps = 1e-5f;
+
+// column reduce, grid (row blocks of one sample, sample): C / 8 chunk lanes x rp row lanes (<= 256 threads, the surplus idle)
+struct ColLane {
+  int rp;                    // row lanes of the workgroup
+  int ch, rl, c;             // this thread's chunk, row lane and first channel
+  int n_begin, n_end;        // the block's rows within its sample
+  __device__ __forceinline__ ColLane(int C, int L, int rows_per_block) {
+    const int cp = C >> 3;
+    rp = 256 / cp;
+    ch = threadIdx.x % cp; rl = threadIdx.x / cp;
+    c = ch * 8;
+    n_begin = blockIdx.x * rows_per_block; n_end = min(L, n_begin + rows_per_block);
+  }
+  __device__ __forceinline__ bool active() const { return rl < rp; }
 };
-__device__ __forceinline__ ColGeom col_geom(int chunks) {
-  ColGeom g;
-  g.cp = chunks;
-  g.rp = 256 / chunks;
-  return g;
+
+// (sum, sum of squares) over 1 / inv_count elements -> mean and 1 / sqrt(biased variance + eps), in fp64 until the final cast
+__device__ __forceinline__ void mean_rstd_from_sums(double s1, double s2, double inv_count, float& mean, float& rstd) {
+  const double m = s1 * inv_count;
+  double var = s2 * inv_count - m * m;                          // biased variance (torch semantics)
+  if (var < 0.0) var = 0.0;
+  mean = (float)m;
+  rstd = (float)(1.0 / sqrt(var + (double)kEps));
 }
 
-static constexpr float kEps = 1e-5f;
+// gamma, beta and the FiLM operands k = 1 + scale, sh = shift of channels c .. c + 7 of sample b (ss = [B][2C] scale | shift; null: k = 1, sh = 0)
+__device__ __forceinline__ void load_film(const float* gamma, const float* beta, const float* ss, int b, int C, int c,
+                                          float (&g)[8], float (&bt)[8], float (&k)[8], float (&sh)[8]) {
+  load8(gamma + c, g);
+  load8(beta + c, bt);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { k[e] = 1.f; sh[e] = 0.f; }
+  if (ss) {
+    float sc[8];
+    load8(ss + (long)b * 2 * C + c, sc);
+    load8(ss + (long)b * 2 * C + C + c, sh);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) k[e] = 1.f + sc[e];
+  }
+}
+
+// end of a column-reduce workgroup: the row lanes' partials t[plane][8] meet in LDS ([NP][rp][C] floats of dynamic LDS), then
+// out(plane, channel, sum over the row lanes r = 0 .. rp - 1 in that order)
+template <int NP, typename F>
+__device__ __forceinline__ void col_reduce_rows(const ColLane& cl, int C, const float (&t)[NP][8], F out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* red = reinterpret_cast<float*>(smem);
+  if (cl.active()) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+      for (int w = 0; w < NP; ++w) red[(w * cl.rp + cl.rl) * C + cl.c + e] = t[w][e];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < NP * C; i += blockDim.x) {
+    const int w = NP == 1 ? 0 : i / C, cc = i - w * C;
+    float s = 0.f;
+    for (int r = 0; r < cl.rp; ++r) s += red[(w * cl.rp + r) * C + cc];
+    out(w, cc, s);
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 // GroupNorm(1, C)
@@ -25,11 +79,7 @@ static constexpr float kEps = 1e-5f;
 __global__ void gn_finalize_kernel(const double* stats, float* mr, int B, double inv_count) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  double mean = stats[2 * b] * inv_count;
-  double var = stats[2 * b + 1] * inv_count - mean * mean;      // biased variance (torch semantics)
-  if (var < 0.0) var = 0.0;
-  mr[2 * b] = (float)mean;
-  mr[2 * b + 1] = (float)(1.0 / sqrt(var + (double)kEps));
+  mean_rstd_from_sums(stats[2 * b], stats[2 * b + 1], inv_count, mr[2 * b], mr[2 * b + 1]);
 }
 
 // Statistics without atomics (osuf_gn_stats; the sampler's bit-reproducible path): stage 1, grid (row chunks, samples) -- every
@@ -42,18 +92,15 @@ __device__ __forceinline__ double group_sum_f64(double v) {
 }
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const T* y, long ldy, double* part, int C, int L, int rows_per_block, int nchunk) {
-  const int chunks = C >> 3;
   const int b = blockIdx.y;
-  const ColGeom cg = col_geom(chunks);
-  const int ch = threadIdx.x % cg.cp, rl = threadIdx.x / cg.cp;
-  const int n_begin = blockIdx.x * rows_per_block, n_end = min(L, n_begin + rows_per_block);
+  const ColLane cl(C, L, rows_per_block);
   // fp64 from the first addition on: the variance is E[y^2] - mean^2, and a thread's 64 squares summed in fp32 cost rstd a relative
   // 6e-6 at mean / std = 30 (the fp64 sums of the GEMM epilogue: 3e-8); a product of two fp32 values is exact in fp64
   double s1 = 0.0, s2 = 0.0;
-  if (rl < cg.rp) {
-    for (int n = n_begin + rl; n < n_end; n += cg.rp) {
+  if (cl.active()) {
+    for (int n = cl.n_begin + cl.rl; n < cl.n_end; n += cl.rp) {
       float v[8];
-      load8(y + ((long)b * L + n) * ldy + ch * 8, v);
+      load8(y + ((long)b * L + n) * ldy + cl.c, v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) { const double d = (double)v[e]; s1 += d; s2 = fma(d, d, s2); }
     }
@@ -72,11 +119,7 @@ __global__ void gn_finalize_parts_kernel(const double* part, float* mr, int B, i
   if (b >= B) return;
   double s1 = 0.0, s2 = 0.0;
   for (int i = 0; i < nchunk; ++i) { s1 += part[((long)b * nchunk + i) * 2]; s2 += part[((long)b * nchunk + i) * 2 + 1]; }
-  double mean = s1 * inv_count;
-  double var = s2 * inv_count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  mr[2 * b] = (float)mean;
-  mr[2 * b + 1] = (float)(1.0 / sqrt(var + (double)kEps));
+  mean_rstd_from_sums(s1, s2, inv_count, mr[2 * b], mr[2 * b + 1]);
 }
 
 // h = silu( ((y-mean)*rstd*gamma + beta) * (1+scale) + shift );  ss = [B][2C] (scale | shift) or null
@@ -88,10 +131,8 @@ __global__ __launch_bounds__(256) void gn_apply_fwd_kernel(const T* y, long ldy,
   // grid (row blocks of one sample, sample): a thread keeps ONE 8-channel chunk and walks rows, so gamma / beta / scale / shift /
   // mean / rstd are loaded once per thread and no index division runs per element (the flat idx / chunks, m / L form spent more
   // VALU on 64-bit divisions and operand reloads than on the normalisation itself)
-  const int chunks = C >> 3;
   const int b = blockIdx.y;
-  const ColGeom cg = col_geom(chunks);
-  const int ch = threadIdx.x % cg.cp, rl = threadIdx.x / cg.cp;
+  const ColLane cl(C, L, rows_per_block);
   float mean, rstd;
   if (stats) {                                             // (sum, sum of squares) of the sample, finalised here (what osuf_gn_finalize computes):
     double t1, t2;
@@ -107,35 +148,20 @@ __global__ __launch_bounds__(256) void gn_apply_fwd_kernel(const T* y, long ldy,
     } else {                                               // ... as the producing GEMM's epilogue left them (102 tiny launches per step less)
       t1 = stats[2 * b]; t2 = stats[2 * b + 1];
     }
-    const double m1 = t1 * inv_count;
-    double var = t2 * inv_count - m1 * m1;
-    if (var < 0.0) var = 0.0;
-    mean = (float)m1;
-    rstd = (float)(1.0 / sqrt(var + (double)kEps));
+    mean_rstd_from_sums(t1, t2, inv_count, mean, rstd);
     if (blockIdx.x == 0 && threadIdx.x == 0) { mr_out[2 * b] = mean; mr_out[2 * b + 1] = rstd; }   // kept for the backward
   } else {
     mean = mr[2 * b]; rstd = mr[2 * b + 1];
   }
-  if (rl >= cg.rp) return;
-  const int c = ch * 8;
+  if (!cl.active()) return;
+  const int c = cl.c;
   float g[8], bt[8], k[8], sh[8];
-  load8(gamma + c, g);
-  load8(beta + c, bt);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { k[e] = 1.f; sh[e] = 0.f; }
-  if (ss) {
-    float sc[8];
-    load8(ss + (long)b * 2 * C + c, sc);
-    load8(ss + (long)b * 2 * C + C + c, sh);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) k[e] = 1.f + sc[e];
-  }
+  load_film(gamma, beta, ss, b, C, c, g, bt, k, sh);
   // out = silu(((v - mean) * rstd * g + bt) * k + sh) = silu(v * A + Bc)
   float A[8], Bc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { A[e] = rstd * g[e] * k[e]; Bc[e] = (bt[e] - mean * rstd * g[e]) * k[e] + sh[e]; }
-  const int n_end = min(L, (int)(blockIdx.x + 1) * rows_per_block);
-  for (int n = blockIdx.x * rows_per_block + rl; n < n_end; n += cg.rp) {
+  for (int n = cl.n_begin + cl.rl; n < cl.n_end; n += cl.rp) {
     const long m = (long)b * L + n;
     float v[8];
     load8(y + m * ldy + c, v);
@@ -145,21 +171,16 @@ __global__ __launch_bounds__(256) void gn_apply_fwd_kernel(const T* y, long ldy,
   }
 }
 
-// column-reduce geometry shared by several kernels
-
 // T1[b][c] = sum_n du * xhat, T2[b][c] = sum_n du   with du = dh * silu'(u)
 template <typename T>
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* dh, long lddh, const T* y, long ldy, const float* mr,
                                                             const float* gamma, const float* beta, const float* ss,
                                                             float* T12, int C, int L, int rows_per_block) {
-  const int chunks = C >> 3;
   const int b = blockIdx.y;
-  const ColGeom cg = col_geom(chunks);
-  const int ch = threadIdx.x % cg.cp, rl = threadIdx.x / cg.cp;
-  const int c = ch * 8;
-  const int n_begin = blockIdx.x * rows_per_block, n_end = min(L, n_begin + rows_per_block);
+  const ColLane cl(C, L, rows_per_block);
+  const int c = cl.c, n_end = cl.n_end;
   float t1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t2[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t3[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t4[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (rl < cg.rp) {
+  if (cl.active()) {
     const float mean = mr[2 * b], rstd = mr[2 * b + 1];
     float g[8], bt[8], sc[8], sh[8];
     load8(gamma + c, g);
@@ -169,17 +190,17 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* dh, long ld
     if (ss) { load8(ss + (long)b * 2 * C + c, sc); load8(ss + (long)b * 2 * C + C + c, sh); }
     // four row steps per trip, their eight 16-byte loads issued together (rows clamped, the surplus masked out below): one step
     // per trip kept 8 KB in flight per CU at the deep levels (C = 1024: 2 rows per step, 256 workgroups) and ran at 1.5 TB/s
-    for (int n0 = n_begin + rl; n0 < n_end; n0 += 4 * cg.rp) {
+    for (int n0 = cl.n_begin + cl.rl; n0 < n_end; n0 += 4 * cl.rp) {
       float v[4][8], d[4][8];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const long m = (long)b * L + min(n0 + q * cg.rp, n_end - 1);
+        const long m = (long)b * L + min(n0 + q * cl.rp, n_end - 1);
         load8(y + m * ldy + c, v[q]);
         load8(dh + m * lddh + c, d[q]);
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const bool ok = n0 + q * cg.rp < n_end;
+        const bool ok = n0 + q * cl.rp < n_end;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           float xh = (v[q][e] - mean) * rstd;
@@ -194,23 +215,12 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* dh, long ld
       }
     }
   }
-  // reduce over row lanes through LDS, then one atomic per (b, c)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = reinterpret_cast<float*>(smem);            // [4][rp][C]
-  if (rl < cg.rp) {
+  // reduce over row lanes through LDS, then one atomic per (plane, b, c) from the lambda.  The copy is free; one t[4][8] inside the row loop
+  // reordered that loop and cost 9 / 19 VGPRs (profiles/norm_fold_codegen.md)
+  float t[4][8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      red[(0 * cg.rp + rl) * C + c + e] = t1[e]; red[(1 * cg.rp + rl) * C + c + e] = t2[e]; red[(2 * cg.rp + rl) * C + c + e] = t3[e];
-      red[(3 * cg.rp + rl) * C + c + e] = t4[e];
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 4 * C; i += blockDim.x) {
-    const int w = i / C, cc = i - w * C;
-    float s = 0.f;
-    for (int r = 0; r < cg.rp; ++r) s += red[(w * cg.rp + r) * C + cc];
-    atomic_add_f32(T12 + ((long)b * 4 + w) * C + cc, s);
-  }
+  for (int e = 0; e < 8; ++e) { t[0][e] = t1[e]; t[1][e] = t2[e]; t[2][e] = t3[e]; t[3][e] = t4[e]; }
+  col_reduce_rows<4>(cl, C, t, [&](int w, int cc, float s) { atomic_add_f32(T12 + ((long)b * 4 + w) * C + cc, s); });
 }
 
 // per sample: S1 = sum_c gamma*(1+scale)*T2, S2 = sum_c gamma*(1+scale)*T1 ; dscale, dshift ; dgamma, dbeta (atomics over b);
@@ -270,30 +280,17 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* dh, long ldd
                                                            const float* mr, const float* gamma, const float* beta, const float* ss,
                                                            const float* T12, float* S, float* dss, float* dgamma, float* dbeta, float* dbias, float* dyy,
                                                            int M, int C, int L, float inv_count, int rows_per_block) {
-  const int chunks = C >> 3;
   const int b = blockIdx.y;
-  const ColGeom cg = col_geom(chunks);
-  const int ch = threadIdx.x % cg.cp, rl = threadIdx.x / cg.cp;
+  const ColLane cl(C, L, rows_per_block);
   float S1, S2;
   gn_bwd_sums(T12, gamma, beta, ss, S, dss, dgamma, dbeta, dbias, dyy, mr, b, C, L, inv_count, blockIdx.x == 0, S1, S2);
-  if (rl >= cg.rp) return;
-  const int c = ch * 8;
+  if (!cl.active()) return;
+  const int c = cl.c;
   const float mean = mr[2 * b], rstd = mr[2 * b + 1];
   const float a1 = S1 * inv_count, a2 = S2 * inv_count;
   float g[8], bt[8], k[8], sh[8];
-  load8(gamma + c, g);
-  load8(beta + c, bt);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { k[e] = 1.f; sh[e] = 0.f; }
-  if (ss) {
-    float sc[8];
-    load8(ss + (long)b * 2 * C + c, sc);
-    load8(ss + (long)b * 2 * C + C + c, sh);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) k[e] = 1.f + sc[e];
-  }
-  const int n_end = min(L, (int)(blockIdx.x + 1) * rows_per_block);
-  for (int n = blockIdx.x * rows_per_block + rl; n < n_end; n += cg.rp) {
+  load_film(gamma, beta, ss, b, C, c, g, bt, k, sh);
+  for (int n = cl.n_begin + cl.rl; n < cl.n_end; n += cl.rp) {
     const long m = (long)b * L + n;
     float v[8], d[8];
     load8(y + m * ldy + c, v);
@@ -653,44 +650,32 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* p, int L) {
 template <typename T>
 __global__ __launch_bounds__(256) void wcolsum_kernel(const T* a, long lda, const T* bmul, long ldb, const float* w, float* out,
                                                       int C, int L, int rows_per_block, float* part) {
-  const int chunks = C >> 3;
   const int b = blockIdx.y;
-  const ColGeom cg = col_geom(chunks);
-  const int ch = threadIdx.x % cg.cp, rl = threadIdx.x / cg.cp;
-  const int c = ch * 8;
-  const int n_begin = blockIdx.x * rows_per_block, n_end = min(L, n_begin + rows_per_block);
-  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (rl < cg.rp) {
-    for (int n0 = n_begin + rl; n0 < n_end; n0 += 4 * cg.rp) {       // four row steps per trip, loads first (see gn_bwd_reduce_kernel)
+  const ColLane cl(C, L, rows_per_block);
+  const int c = cl.c, n_end = cl.n_end;
+  float acc[1][8] = {};
+  if (cl.active()) {
+    for (int n0 = cl.n_begin + cl.rl; n0 < n_end; n0 += 4 * cl.rp) {       // four row steps per trip, loads first (see gn_bwd_reduce_kernel)
       float v[4][8], u[4][8], wv[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const long m = (long)b * L + min(n0 + q * cg.rp, n_end - 1);
+        const long m = (long)b * L + min(n0 + q * cl.rp, n_end - 1);
         load8(a + m * lda + c, v[q]);
         if (bmul) load8(bmul + m * ldb + c, u[q]);                     // (uniform conditions: no exec mask)
         wv[q] = w ? w[m] : 1.f;
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float wq = n0 + q * cg.rp < n_end ? wv[q] : 0.f;
+        const float wq = n0 + q * cl.rp < n_end ? wv[q] : 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += wq * (bmul ? v[q][e] * u[q][e] : v[q][e]);
+        for (int e = 0; e < 8; ++e) acc[0][e] += wq * (bmul ? v[q][e] * u[q][e] : v[q][e]);
       }
     }
   }
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = reinterpret_cast<float*>(smem);            // [rp][C]
-  if (rl < cg.rp) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[rl * C + c + e] = acc[e];
-  }
-  __syncthreads();
-  for (int cc = threadIdx.x; cc < C; cc += blockDim.x) {
-    float s = 0.f;
-    for (int r = 0; r < cg.rp; ++r) s += red[r * C + cc];
+  col_reduce_rows<1>(cl, C, acc, [&](int, int cc, float s) {
     if (part) part[((long)b * gridDim.x + blockIdx.x) * C + cc] = s;      // reproducible path: summed in chunk order below
     else atomic_add_f32(out + (long)b * C + cc, s);
-  }
+  });
 }
 // out[b][c] = sum over a sample's row chunks, in chunk order, of the wcolsum partials (no atomics)
 __global__ __launch_bounds__(256) void colsum_parts_kernel(const float* part, float* out, int C, int nchunk) {
@@ -861,24 +846,20 @@ static inline int pick_group(int chunks) {
   while (g < chunks && g < 64) g <<= 1;
   return g;
 }
-static inline int ew_grid(long total_threads) {
-  long blocks = (total_threads + 255) / 256;
-  if (blocks > 2048) blocks = 2048;                   // 256 CUs x 8, grid-stride the rest
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
 static inline int row_grid(long M, int G) {
   long rows_per_block = 4L * (64 / G);
   long blocks = (M + rows_per_block - 1) / rows_per_block;
   if (blocks > 4096) blocks = 4096;
   return (int)blocks;
 }
-#define DISPATCH_T(dtype, ...)                                  \
-  if ((dtype) == OSUF_DT_BF16) { using T = bf16_t; __VA_ARGS__; } \
-  else if ((dtype) == OSUF_DT_F32) { using T = float; __VA_ARGS__; } \
-  else return OSUF_EUNSUPPORTED;
-
-static inline bool bad_c(int C) { return C <= 0 || (C & 7) || C > 8 * 256; }
+// rows per workgroup of the GroupNorm statistics / apply kernels (8 per thread of the column skeleton) and the row chunks of a sample at that size:
+// the layout of the partial sums [B][chunks][2] depends on every launch and the workspace query agreeing on both
+static inline int gn_rows_per_block(int C) { return (256 / (C / 8)) * 8; }
+static inline int gn_chunks(int L, int C) { return (L + gn_rows_per_block(C) - 1) / gn_rows_per_block(C); }
+// chunks of 8 channels per lane of the row-wise kernels (1 .. 4 for C <= 2048) -> LAUNCH(NCH).  N3 = the instantiation that serves three chunks:
+// 4 where a launcher has only the 1 / 2 / 4 bodies, 3 where it has a three-chunk body of its own (gca_bwd_apply)
+#define DISPATCH_NCH(nch, N3, LAUNCH) \
+  if ((nch) == 1) { LAUNCH(1); } else if ((nch) == 2) { LAUNCH(2); } else if ((nch) == 3) { LAUNCH(N3); } else { LAUNCH(4); }
 
 extern "C" int osuf_gn_finalize(const double* stats, float* mr, int B, long count, hipStream_t stream) {
   if (B <= 0 || count <= 0) return OSUF_EINVAL;
@@ -887,38 +868,39 @@ extern "C" int osuf_gn_finalize(const double* stats, float* mr, int B, long coun
 }
 
 extern "C" long osuf_gn_stats_workspace_bytes(int M, int C, int L) {
-  if (M <= 0 || L <= 0 || M % L || C <= 0 || C % 8 || C > 2048) return 0;
-  const int rpb = (256 / (C / 8)) * 8;
-  return (long)(M / L) * ((L + rpb - 1) / rpb) * 2 * (long)sizeof(double);
+  if (M <= 0 || L <= 0 || M % L || bad_c(C)) return 0;
+  return (long)(M / L) * gn_chunks(L, C) * 2 * (long)sizeof(double);
+}
+// stage 1: per-(sample, row chunk) partial sums into partial[B][gn_chunks][2]
+static int gn_stats_launch(int dtype, const void* y, long ldy, double* partial, int M, int C, int L, hipStream_t stream) {
+  if (bad_c(C) || M <= 0 || L <= 0 || M % L || ldy % 8 || !partial) return OSUF_EINVAL;
+  const int nchunk = gn_chunks(L, C);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(nchunk, M / L), dim3(256), 0, stream, (const T*)y, ldy, partial, C, L,
+                                       gn_rows_per_block(C), nchunk));
+  return OSUF_OK;
 }
 // mean / rstd of GroupNorm(1, C) over each sample of y, by two fixed-order reduction stages (bit-reproducible; one extra read of y)
 extern "C" int osuf_gn_stats(int dtype, const void* y, long ldy, double* partial, float* mr, int M, int C, int L, hipStream_t stream) {
-  if (bad_c(C) || M <= 0 || L <= 0 || M % L || ldy % 8 || !partial) return OSUF_EINVAL;
-  const int rpb = (256 / (C / 8)) * 8, nchunk = (L + rpb - 1) / rpb, B = M / L;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(nchunk, B), dim3(256), 0, stream, (const T*)y, ldy, partial, C, L, rpb, nchunk));
-  hipLaunchKernelGGL(gn_finalize_parts_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, partial, mr, B, nchunk, 1.0 / ((double)L * C));
+  const int rc = gn_stats_launch(dtype, y, ldy, partial, M, C, L, stream);
+  if (rc) return rc;
+  const int B = M / L;
+  hipLaunchKernelGGL(gn_finalize_parts_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, partial, mr, B, gn_chunks(L, C), 1.0 / ((double)L * C));
   return osuf_launch_status();
 }
 
 // stage 1 of osuf_gn_stats alone: per-(sample, row chunk) partial sums into partial[B][nparts][2], nparts = osuf_gn_stats_workspace_bytes / (16 B);
 // osuf_gn_apply_fwd_parts finishes them inside the apply kernel
 extern "C" int osuf_gn_stats_parts(int dtype, const void* y, long ldy, double* partial, int M, int C, int L, hipStream_t stream) {
-  if (bad_c(C) || M <= 0 || L <= 0 || M % L || ldy % 8 || !partial) return OSUF_EINVAL;
-  const int rpb = (256 / (C / 8)) * 8, nchunk = (L + rpb - 1) / rpb, B = M / L;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(nchunk, B), dim3(256), 0, stream, (const T*)y, ldy, partial, C, L, rpb, nchunk));
-  return osuf_launch_status();
+  const int rc = gn_stats_launch(dtype, y, ldy, partial, M, C, L, stream);
+  return rc ? rc : osuf_launch_status();
 }
 
 static int gn_apply_fwd_launch(int dtype, const void* y, long ldy, void* h, long ldh, const float* mr, const float* gamma, const float* beta,
                                const float* ss, int M, int C, int L, const double* stats, long count, float* mr_out, hipStream_t stream, int nparts = 0) {
   if (bad_c(C) || M <= 0 || L <= 0 || M % L || ldy % 8 || ldh % 8) return OSUF_EINVAL;
-  {
-    const int rp = 256 / (C / 8);
-    const int rpb = rp * 8;                                // 8 rows per thread
-    DISPATCH_T(dtype, hipLaunchKernelGGL(gn_apply_fwd_kernel<T>, dim3((L + rpb - 1) / rpb, M / L), dim3(256), 0, stream,
-                                         (const T*)y, ldy, (T*)h, ldh, mr, gamma, beta, ss, M, C, L, rpb, stats,
-                                         stats ? 1.0 / (double)count : 0.0, mr_out, nparts));
-  }
+  DISPATCH_T(dtype, hipLaunchKernelGGL(gn_apply_fwd_kernel<T>, dim3(gn_chunks(L, C), M / L), dim3(256), 0, stream,
+                                       (const T*)y, ldy, (T*)h, ldh, mr, gamma, beta, ss, M, C, L, gn_rows_per_block(C), stats,
+                                       stats ? 1.0 / (double)count : 0.0, mr_out, nparts));
   return osuf_launch_status();
 }
 extern "C" int osuf_gn_apply_fwd(int dtype, const void* y, long ldy, void* h, long ldh, const float* mr, const float* gamma,
@@ -937,8 +919,7 @@ extern "C" int osuf_gn_apply_fwd_stats(int dtype, const void* y, long ldy, void*
 extern "C" int osuf_gn_apply_fwd_parts(int dtype, const void* y, long ldy, void* h, long ldh, const double* partial, float* mr_out,
                                        const float* gamma, const float* beta, const float* ss, int M, int C, int L, hipStream_t stream) {
   if (!partial || !mr_out || bad_c(C) || L <= 0) return OSUF_EINVAL;
-  const int rpb = (256 / (C / 8)) * 8, nchunk = (L + rpb - 1) / rpb;
-  return gn_apply_fwd_launch(dtype, y, ldy, h, ldh, nullptr, gamma, beta, ss, M, C, L, partial, (long)L * C, mr_out, stream, nchunk);
+  return gn_apply_fwd_launch(dtype, y, ldy, h, ldh, nullptr, gamma, beta, ss, M, C, L, partial, (long)L * C, mr_out, stream, gn_chunks(L, C));
 }
 
 // T1234: [B][4][C] fp32, must be zero on entry.  dss may be null (no FiLM).  dgamma / dbeta / dbias (the latter optional: gradient
@@ -956,12 +937,10 @@ extern "C" int osuf_gn_bwd(int dtype, const void* dh, long lddh, const void* y, 
   const float inv_count = 1.0f / ((float)L * (float)C);
   DISPATCH_T(dtype, hipLaunchKernelGGL(gn_bwd_reduce_kernel<T>, dim3((L + rows_per_block - 1) / rows_per_block, B), dim3(256), lds,
                                        stream, (const T*)dh, lddh, (const T*)y, ldy, mr, gamma, beta, ss, T123, C, L, rows_per_block));
-  {
-    const int rpb = rp * 8;                                // 8 rows per thread; the per-sample sums + side outputs (the former finalize launch) ride along
-    DISPATCH_T(dtype, hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, dim3((L + rpb - 1) / rpb, B), dim3(256), 0, stream, (const T*)dh,
-                                         lddh, (const T*)y, ldy, (T*)dy, lddy, mr, gamma, beta, ss, T123, S, dss, dgamma, dbeta, dbias, dyy,
-                                         M, C, L, inv_count, rpb));
-  }
+  // the per-sample sums + side outputs (the former finalize launch) ride along
+  DISPATCH_T(dtype, hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, dim3(gn_chunks(L, C), B), dim3(256), 0, stream, (const T*)dh,
+                                       lddh, (const T*)y, ldy, (T*)dy, lddy, mr, gamma, beta, ss, T123, S, dss, dgamma, dbeta, dbias, dyy,
+                                       M, C, L, inv_count, gn_rows_per_block(C)));
   return osuf_launch_status();
 }
 
@@ -971,7 +950,7 @@ extern "C" int osuf_ln_fwd(int dtype, const void* x, long ldx, void* out, long l
   const int G = pick_group(C / 8);
   const int nch = (C / 8 + G - 1) / G;
 #define LN_FWD_LAUNCH(NCH_) hipLaunchKernelGGL((ln_fwd_kernel<T, NCH_>), dim3(row_grid(M, G)), dim3(256), 0, stream, (const T*)x, ldx, (T*)out, ldo, mr, gamma, beta, M, C, G)
-  DISPATCH_T(dtype, if (nch == 1) LN_FWD_LAUNCH(1); else if (nch == 2) LN_FWD_LAUNCH(2); else LN_FWD_LAUNCH(4));
+  DISPATCH_T(dtype, DISPATCH_NCH(nch, /* three chunks run */ 4, LN_FWD_LAUNCH));
 #undef LN_FWD_LAUNCH
   return osuf_launch_status();
 }
@@ -982,14 +961,14 @@ extern "C" int osuf_ln_bwd(int dtype, const void* dy, long lddy, const void* x, 
   const int G = pick_group(C / 8);
   const int nch = (C / 8 + G - 1) / G;                // chunks per lane: 1 (C <= 512), 2 (<= 1024), 3 or 4 (<= 2048)
   // one chunk per lane: 1,024 threads; two: 512 (the LDS reduction holds NT / 64 x 2 C floats <= 64 KiB)
-  const int nt = nch == 1 ? 1024 : nch == 2 ? 512 : 256;
+  const int nt = 1024 / (nch == 3 ? 4 : nch);          // = the NT of the instantiation DISPATCH_NCH picks below
   long blocks = (M + (nt / 64) * (64 / G) - 1) / ((nt / 64) * (64 / G));
   const long cap = (nt == 256 || (nt == 512 && M >= 32768)) ? 512 : 256;   // bounds the dgamma / dbeta atomics (one per channel and block)
   if (blocks > cap) blocks = cap;
   const size_t lds = (size_t)(nt / 64) * 2 * C * sizeof(float);
-#define LN_BWD_LAUNCH(NCH_, NT_) hipLaunchKernelGGL((ln_bwd_kernel<T, NCH_, NT_>), dim3((int)blocks), dim3(NT_), lds, stream, (const T*)dy, lddy, \
-                                                    (const T*)x, ldx, (T*)dx, lddx, mr, gamma, dgamma, dbeta, M, C, G)
-  DISPATCH_T(dtype, if (nch == 1) LN_BWD_LAUNCH(1, 1024); else if (nch == 2) LN_BWD_LAUNCH(2, 512); else LN_BWD_LAUNCH(4, 256));
+#define LN_BWD_LAUNCH(NCH_) hipLaunchKernelGGL((ln_bwd_kernel<T, NCH_, 1024 / NCH_>), dim3((int)blocks), dim3(1024 / NCH_), lds, stream, (const T*)dy, lddy, \
+                                               (const T*)x, ldx, (T*)dx, lddx, mr, gamma, dgamma, dbeta, M, C, G)
+  DISPATCH_T(dtype, DISPATCH_NCH(nch, /* three chunks run */ 4, LN_BWD_LAUNCH));
 #undef LN_BWD_LAUNCH
   return osuf_launch_status();
 }
@@ -1011,7 +990,7 @@ static int gca_pool_rows_per_block(int M) {
   return r;
 }
 extern "C" long osuf_gca_pool_workspace_bytes(int M, int C, int L) {
-  if (M <= 0 || L <= 0 || M % L || C <= 0 || C % 8 || C > 2048) return 0;
+  if (M <= 0 || L <= 0 || M % L || bad_c(C)) return 0;
   const int rpb = 32;                                    // the smallest block the launch may pick: an upper bound
   return (long)(M / L) * ((L + rpb - 1) / rpb) * (C + 2) * (long)sizeof(float);
 }
@@ -1025,7 +1004,7 @@ extern "C" int osuf_gca_pool(int dtype, const void* h, long ldh, const float* wk
   const size_t lds = (size_t)4 * (C + 2) * sizeof(float);
   if ((size_t)nblk * sizeof(float) > 60000) return OSUF_EUNSUPPORTED;
 #define GCA_POOL_LAUNCH(NCH_) hipLaunchKernelGGL((gca_pool_kernel<T, NCH_>), dim3(nblk, B), dim3(256), lds, stream, (const T*)h, ldh, wk, bk, part, p, C, L, G, rpb)
-  DISPATCH_T(dtype, if (nch == 1) GCA_POOL_LAUNCH(1); else if (nch == 2) GCA_POOL_LAUNCH(2); else GCA_POOL_LAUNCH(4));
+  DISPATCH_T(dtype, DISPATCH_NCH(nch, /* three chunks run */ 4, GCA_POOL_LAUNCH));
 #undef GCA_POOL_LAUNCH
   hipLaunchKernelGGL(gca_pool_finish_kernel, dim3(B), dim3(256), (size_t)nblk * sizeof(float), stream, part, p, pooled, C, L, nblk);
   return osuf_launch_status();
@@ -1081,9 +1060,9 @@ extern "C" int osuf_gca_bwd_apply(int dtype, const void* dout, long lddo, const 
   const int blocks = gca_blocks(M, C, dwk != nullptr);
   float* part = (dwk && workspace && workspace_bytes >= (long)blocks * (C + 1) * (long)sizeof(float)) ? workspace : nullptr;
   const int nch = (C / 8 + G - 1) / G;                     // 1..4 (C <= 2048, G = 64 from 512 channels on)
-#define GCA_LAUNCH(NCH) DISPATCH_T(dtype, hipLaunchKernelGGL((gca_bwd_apply_kernel<T, NCH>), dim3(blocks), dim3(256), lds, stream, \
-    (const T*)dout, lddo, (const T*)h, ldh, (T*)dh, lddh, p, gate, dpooled, sdot, wk, dlogit, M, C, L, G, dwk, dbk, part))
-  if (nch == 1) { GCA_LAUNCH(1); } else if (nch == 2) { GCA_LAUNCH(2); } else if (nch == 3) { GCA_LAUNCH(3); } else { GCA_LAUNCH(4); }
+#define GCA_LAUNCH(NCH) hipLaunchKernelGGL((gca_bwd_apply_kernel<T, NCH>), dim3(blocks), dim3(256), lds, stream, \
+    (const T*)dout, lddo, (const T*)h, ldh, (T*)dh, lddh, p, gate, dpooled, sdot, wk, dlogit, M, C, L, G, dwk, dbk, part)
+  DISPATCH_T(dtype, DISPATCH_NCH(nch, /* three chunks run */ 3, GCA_LAUNCH));
 #undef GCA_LAUNCH
   if (part) hipLaunchKernelGGL(gca_dwk_reduce_kernel, dim3((C + 1 + 63) / 64, 16), dim3(256), 0, stream, part, blocks, C, dwk, dbk);
   return osuf_launch_status();

@@ -294,12 +294,16 @@ def gn_finalize(stats: torch.Tensor, count: int) -> torch.Tensor:
     return mr
 
 
+def _gn_stats_parts_len(M: int, C: int, L: int) -> int:
+    """Doubles of scratch for the per-(sample, row chunk) partial sums of osuf_gn_stats / osuf_gn_stats_parts (the callers allocate)."""
+    return max(_lib.load().osuf_gn_stats_workspace_bytes(M, C, L) // 8, 1)
+
+
 def gn_stats(y: torch.Tensor, L: int) -> torch.Tensor:
     """(mean, rstd) per sample of GroupNorm(1, C) over rows y, by fixed-order reductions (bit-reproducible)."""
     M, C, ld = _rows(y)
     B = M // L
-    need = _lib.load().osuf_gn_stats_workspace_bytes(M, C, L)
-    part = torch.empty(max(need // 8, 1), dtype=torch.float64, device=y.device)
+    part = torch.empty(_gn_stats_parts_len(M, C, L), dtype=torch.float64, device=y.device)
     mr = torch.empty((B, 2), dtype=torch.float32, device=y.device)
     call("osuf_gn_stats", dt_of(y), _p(y), ld, _p(part), _p(mr), M, C, L, _stream())
     return mr
@@ -310,8 +314,7 @@ def gn_apply_reproducible(y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tens
     order itself -> (h, mean_rstd (B, 2)).  Same result on every call; not the same bits as gn_stats' serial second stage."""
     M, C, ld = _rows(y)
     B = M // L
-    need = _lib.load().osuf_gn_stats_workspace_bytes(M, C, L)
-    part = torch.empty(max(need // 8, 1), dtype=torch.float64, device=y.device)
+    part = torch.empty(_gn_stats_parts_len(M, C, L), dtype=torch.float64, device=y.device)
     h = torch.empty(y.shape, dtype=y.dtype, device=y.device)
     mr = torch.empty((B, 2), dtype=torch.float32, device=y.device)
     call("osuf_gn_stats_parts", dt_of(y), _p(y), ld, _p(part), M, C, L, _stream())

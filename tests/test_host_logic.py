@@ -348,3 +348,20 @@ def test_capi_descriptor_structs_match_their_numpy_layouts():
 def test_capi_library_loads_and_reports_version():
     lib = _lib.load()
     assert lib.osuf_version() == 1          # host-only entry point: no GPU needed
+
+
+def test_capi_norm_workspace_queries_pin_the_host_geometry():
+    """The three workspace queries of norm.hip (host-only) at M = 129 = 3 samples x L = 43.  The expected bytes follow from the launch geometry
+    the kernels share: GroupNorm statistics B * ceil(L / rpb) * 2 doubles with rpb = (256 / (C / 8)) * 8 rows per block; pooling
+    B * ceil(L / 32) * (C + 2) floats; the dwk slab min(ceil(M / (4 * (64 / G))), 2048) * (C + 1) floats, G = lanes per row."""
+    lib = _lib.load()
+    M, L = 129, 43
+    assert [lib.osuf_gn_stats_workspace_bytes(M, C, L) for C in (8, 520, 2048)] == [48, 96, 288]
+    assert [lib.osuf_gca_pool_workspace_bytes(M, C, L) for C in (8, 2048)] == [240, 49200]
+    assert [lib.osuf_gca_bwd_apply_workspace_bytes(M, C) for C in (8, 2048)] == [36, 270468]
+    for C in (12, 2056):                     # not a multiple of 8; wider than the kernels serve
+        assert lib.osuf_gn_stats_workspace_bytes(M, C, L) == 0
+        assert lib.osuf_gca_pool_workspace_bytes(M, C, L) == 0
+        assert lib.osuf_gca_bwd_apply_workspace_bytes(M, C) == 0
+    assert lib.osuf_gn_stats_workspace_bytes(M, 8, 42) == 0      # M % L != 0
+    assert lib.osuf_gca_pool_workspace_bytes(M, 8, 42) == 0
