@@ -406,6 +406,34 @@ int osuf_qknorm_bwd(int dtype, const float* g, long ldg, const void* x, long ldx
                     int M, int H, int D, hipStream_t stream);
 int osuf_stat_pool(const float* a, float* out, int B, int C, int L, hipStream_t stream);
 
+/* ---- joint attention rows (dit.hip)    replaces: osu_fusion/modules/mmdit.py:99-121 (rearrange, MultiHeadRMSNorm, the GQA repeat and
+ *      pack([.._a, .._x], "b h * d") of JointAttention) and 124-126 (unpack + rearrange), and autograd's transposes of them.
+ *      The joint buffer holds, per sample b, Nj rows: a stream with Ns rows per sample at row offset `off` (0 <= off, off + Ns <= Nj) owns
+ *      rows b * Nj + off .. + Ns - 1; M = B * Ns is the stream's row count.  Every call serves ONE stream and leaves the joint rows of
+ *      the other untouched (a layer calls each entry point once per stream).  Joint columns are what osuf_mqa_* read with G K/V heads:
+ *      [H q heads group-major | G k heads | G v heads], D each; natural query head j (which reads K/V head j % G, as the reference's
+ *      "b h n d -> b (r h) n d" repeat has it) sits in column block (j % G) * (H / G) + j / G.  The stream side is always in natural
+ *      head order.  D in {16, 32, 64, 128}, H % G == 0, (H + 2G) D <= 4096.
+ * osuf_joint_qknorm_fwd: raw q|k|v projection rows [M][(H + 2G) D] (dtype) -> bf16 joint rows; q and k heads
+ *      x / max(||x||, 1e-12) * gamma[h] * sqrt(D) with one bf16 rounding (osuf_qknorm_fwd's arithmetic; gamma_q [H][D], gamma_k [G][D]),
+ *      v copied; inv[m][H + G] = 1 / max(||x||, 1e-12) of the stream's q then k heads.  gamma_q == gamma_k == NULL: cast and permute
+ *      only (qk_norm=False), inv unused.
+ * osuf_joint_pack: a stream's rows [M][H D] (dtype, natural head order) -> its bf16 joint rows [..][H D] group-major (dO).
+ * osuf_joint_unpack: the transpose: bf16 joint rows -> the stream's rows in `dtype` (the attention output).
+ * osuf_joint_qknorm_bwd: fp32 dq|dk|dv joint rows -> gradient of the stream's raw projections (dtype); dgamma = [dgamma_q [H][D] |
+ *      dgamma_k [G][D]] fp32 stored, summed in a fixed order; workspace: osuf_joint_qknorm_bwd_workspace_bytes(M, H, G, D) bytes.
+ *      Both gammas NULL: permute and cast only (x, inv, dgamma, workspace unused). ---- */
+int osuf_joint_qknorm_fwd(int dtype, const void* x, long ldx, void* y, long ldy, float* inv, const float* gamma_q, const float* gamma_k,
+                          int M, int Ns, int Nj, int off, int H, int G, int D, hipStream_t stream);
+int osuf_joint_pack(int dtype, const void* x, long ldx, void* joint, long ldj, int M, int Ns, int Nj, int off, int H, int G, int D,
+                    hipStream_t stream);
+int osuf_joint_unpack(int dtype, const void* joint, long ldj, void* out, long ldo, int M, int Ns, int Nj, int off, int H, int G, int D,
+                      hipStream_t stream);
+long osuf_joint_qknorm_bwd_workspace_bytes(int M, int H, int G, int D);
+int osuf_joint_qknorm_bwd(int dtype, const float* g, long ldg, const void* x, long ldx, const float* inv, const float* gamma_q,
+                          const float* gamma_k, void* dx, long lddx, float* dgamma, float* workspace, long workspace_bytes,
+                          int M, int Ns, int Nj, int off, int H, int G, int D, hipStream_t stream);
+
 /* Measurement aid (no reference counterpart): sustained shader clock under an MFMA (mode 1) or VALU (mode 0) load.
  * out[2*block] = shader cycles, out[2*block+1] = 100 MHz wall ticks. */
 int osuf_clock_probe(int blocks, int iters, int mode, long* out, hipStream_t stream);

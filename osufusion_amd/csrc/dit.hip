@@ -350,6 +350,216 @@ extern "C" int osuf_qknorm_bwd(int dtype, const float* g, long ldg, const void* 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Joint attention rows (mmdit.py:94-127): two streams' q|k|v projections packed into one bf16 buffer over [audio; map].
+//   rows:    sample b owns Nj joint rows; a stream with Ns rows per sample at row offset `off` puts its row m = b * Ns + n at b * Nj + off + n
+//   columns: [H q heads GROUP-MAJOR | G k heads | G v heads], D each.  The reference repeats K/V as "b h n d -> b (r h) n d", so natural
+//            query head j reads K/V head j % G: it goes to column block (j % G) * (H / G) + j / G (what ops.mqa_fwd(kv_heads=G) reads)
+// One entry-point call serves ONE stream (a layer calls each twice); the other stream's joint rows are never touched.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long joint_row(long m, int Ns, int Nj, int off) {
+  const long b = m / Ns;
+  return b * Nj + off + (m - b * Ns);
+}
+// 8-element chunk `ch` of a stream's row (natural head order, hc chunks per head) -> its chunk in the joint row
+__device__ __forceinline__ int joint_chunk(int ch, int hc, int H, int G) {
+  const int head = ch / hc;
+  if (head >= H) return ch;                                      // k and v heads keep their place
+  return ((head % G) * (H / G) + head / G) * hc + (ch - head * hc);
+}
+
+// raw q|k|v rows [M][(H + 2G) D] (T) -> bf16 joint rows; the q and k heads normed as qknorm_fwd_kernel does (the same operations in the
+// same order); gq == NULL: cast only.  inv[m][H + G]: the stream's own rows, natural head order (q heads, then k heads).
+template <typename T, int J>
+__global__ __launch_bounds__(256) void joint_qknorm_fwd_kernel(const T* x, long ldx, bf16_t* y, long ldy, float* inv, const float* gq, const float* gk,
+                                                               int M, int Ns, int Nj, int off, int H, int G, int D) {
+  const int hc = D / 8, chunks = (H + 2 * G) * hc, qk = (H + G) * hc;
+  const int lane = threadIdx.x & 63;
+  const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const long waves = ((long)gridDim.x * blockDim.x) >> 6;
+  const float sD = sqrtf((float)D);
+  for (long m = wave; m < M; m += waves) {
+    const long jr = joint_row(m, Ns, Nj, off);
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const int ch = lane + 64 * j;
+      if (ch >= chunks) break;                                  // whole heads drop out together (64 and chunks are multiples of D / 8)
+      float v[8];
+      load8(x + m * ldx + ch * 8, v);
+      if (gq && ch < qk) {
+        float q = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) q += v[e] * v[e];
+        q = group_sum_dyn(q, hc);
+        const float r = 1.f / fmaxf(sqrtf(q), kNormEps);
+        const int head = ch / hc;                               // 0 .. H + G - 1: q heads, then k heads
+        const float* g = (head < H ? gq + head * D : gk + (head - H) * D) + (ch % hc) * 8;
+        float gv[8];
+        load8(g, gv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = v[e] * r * gv[e] * sD;
+        if (ch % hc == 0) inv[m * (H + G) + head] = r;
+      }
+      store8(y + jr * ldy + joint_chunk(ch, hc, H, G) * 8, v);
+    }
+  }
+}
+
+// PACK: a stream's rows [M][H D] (T, natural head order) -> its bf16 joint rows (group-major); else the way back.
+template <typename T, bool PACK>
+__global__ __launch_bounds__(256) void joint_perm_kernel(T* s, long lds, bf16_t* joint, long ldj, int M, int Ns, int Nj, int off, int H, int G, int D) {
+  const int hc = D / 8, chunks = H * hc;
+  const long total = (long)M * chunks;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long m = i / chunks;
+    const int ch = (int)(i - m * chunks);
+    T* ps = s + m * lds + ch * 8;
+    bf16_t* pj = joint + joint_row(m, Ns, Nj, off) * ldj + joint_chunk(ch, hc, H, G) * 8;
+    float v[8];
+    if (PACK) { load8(ps, v); store8(pj, v); }
+    else { load8(pj, v); store8(ps, v); }
+  }
+}
+
+// fp32 dq|dk|dv JOINT rows (ops.mqa_bwd) -> gradient of one stream's raw projections (T, natural head order); the arithmetic of
+// qknorm_bwd_kernel.  dgamma partials part[k][(H + G) D] (gq != NULL only).
+template <typename T, int J>
+__global__ __launch_bounds__(256) void joint_qknorm_bwd_kernel(const float* g, long ldg, const T* x, long ldx, const float* inv, const float* gq,
+                                                               const float* gk, T* dx, long lddx, float* part, int M, int Ns, int Nj, int off,
+                                                               int H, int G, int D) {
+  const int hc = D / 8, chunks = (H + 2 * G) * hc, qk = (H + G) * hc;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float sD = sqrtf((float)D);
+  float acc[J][8];
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+  for (long m = 4L * blockIdx.x + wv; m < M; m += 4L * gridDim.x) {
+    const long jr = joint_row(m, Ns, Nj, off);
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const int ch = lane + 64 * j;
+      if (ch >= chunks) break;
+      float gv[8];
+      load8(g + jr * ldg + joint_chunk(ch, hc, H, G) * 8, gv);
+      if (gq && ch < qk) {
+        float xv[8], ga[8];
+        load8(x + m * ldx + ch * 8, xv);
+        const int head = ch / hc;
+        load8((head < H ? gq + head * D : gk + (head - H) * D) + (ch % hc) * 8, ga);
+        const float r = inv[m * (H + G) + head];
+        float q = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) q += xv[e] * xv[e];
+        q = group_sum_dyn(q, hc);
+        const bool clamped = sqrtf(q) < kNormEps;
+        float d = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float u = xv[e] * r;
+          acc[j][e] += gv[e] * u * sD;
+          gv[e] *= ga[e] * sD;                                  // gu
+          xv[e] = u;
+          d += u * gv[e];
+        }
+        d = group_sum_dyn(d, hc);
+        if (clamped) d = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gv[e] = (gv[e] - xv[e] * d) * r;
+      }
+      store8(dx + m * lddx + ch * 8, gv);
+    }
+  }
+  if (!gq) return;                                               // (uniform: no workgroup meets the barrier half way)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* red = reinterpret_cast<float*>(smem);                 // [4][(H + G) D]
+  const int W = (H + G) * D;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int ch = lane + 64 * j;
+    if (ch < qk) store8(red + wv * W + ch * 8, acc[j]);
+  }
+  __syncthreads();
+  float* dst = part + (long)blockIdx.x * W;
+  for (int i = threadIdx.x; i < W; i += blockDim.x) dst[i] = red[i] + red[W + i] + red[2 * W + i] + red[3 * W + i];
+}
+
+static bool bad_joint(int M, int Ns, int Nj, int off, int H, int G, int D) {
+  return M <= 0 || Ns <= 0 || Nj <= 0 || off < 0 || (long)off + Ns > Nj || M % Ns || H <= 0 || G <= 0 || H % G ||
+         !(D == 16 || D == 32 || D == 64 || D == 128) || ((long)H + 2L * G) * D > 4096;
+}
+
+extern "C" int osuf_joint_qknorm_fwd(int dtype, const void* x, long ldx, void* y, long ldy, float* inv, const float* gamma_q, const float* gamma_k,
+                                     int M, int Ns, int Nj, int off, int H, int G, int D, hipStream_t stream) {
+  if (bad_joint(M, Ns, Nj, off, H, G, D) || ldx % 8 || ldy % 8 || ldx < (long)(H + 2 * G) * D || ldy < (long)(H + 2 * G) * D || !al16(x) || !x || !y || !al16(y))
+    return OSUF_EINVAL;
+  if ((gamma_q == nullptr) != (gamma_k == nullptr) || (gamma_q && !inv) || !al16(gamma_q) || !al16(gamma_k)) return OSUF_EINVAL;
+  const int J = chunk_iters((H + 2 * G) * D / 8);
+  if (J == 0) return OSUF_EUNSUPPORTED;
+  long blocks = ((long)M + 3) / 4;
+  if (blocks > 4096) blocks = 4096;
+#define JQKN_FWD(J_) hipLaunchKernelGGL((joint_qknorm_fwd_kernel<T, J_>), dim3((int)blocks), dim3(256), 0, stream, (const T*)x, ldx, (bf16_t*)y, ldy, inv, \
+                                        gamma_q, gamma_k, M, Ns, Nj, off, H, G, D)
+  DISPATCH_T(dtype, if (J == 1) JQKN_FWD(1); else if (J == 2) JQKN_FWD(2); else if (J == 4) JQKN_FWD(4); else JQKN_FWD(8));
+#undef JQKN_FWD
+  return osuf_launch_status();
+}
+
+static int joint_perm(bool pack, int dtype, void* s, long lds, void* joint, long ldj, int M, int Ns, int Nj, int off, int H, int G, int D,
+                      hipStream_t stream) {
+  if (bad_joint(M, Ns, Nj, off, H, G, D) || lds % 8 || ldj % 8 || lds < (long)H * D || ldj < (long)H * D || !s || !joint || !al16(s) || !al16(joint))
+    return OSUF_EINVAL;
+  const int grid = ew_grid((long)M * (H * D / 8));
+#define JPERM(P_) hipLaunchKernelGGL((joint_perm_kernel<T, P_>), dim3(grid), dim3(256), 0, stream, (T*)s, lds, (bf16_t*)joint, ldj, M, Ns, Nj, off, H, G, D)
+  DISPATCH_T(dtype, if (pack) JPERM(true); else JPERM(false));
+#undef JPERM
+  return osuf_launch_status();
+}
+
+extern "C" int osuf_joint_pack(int dtype, const void* x, long ldx, void* joint, long ldj, int M, int Ns, int Nj, int off, int H, int G, int D,
+                               hipStream_t stream) {
+  return joint_perm(true, dtype, const_cast<void*>(x), ldx, joint, ldj, M, Ns, Nj, off, H, G, D, stream);
+}
+
+extern "C" int osuf_joint_unpack(int dtype, const void* joint, long ldj, void* out, long ldo, int M, int Ns, int Nj, int off, int H, int G, int D,
+                                 hipStream_t stream) {
+  return joint_perm(false, dtype, out, ldo, const_cast<void*>(joint), ldj, M, Ns, Nj, off, H, G, D, stream);
+}
+
+extern "C" long osuf_joint_qknorm_bwd_workspace_bytes(int M, int H, int G, int D) {
+  if (bad_joint(M, 1, 1, 0, H, G, D)) return 0;
+  return (long)qknorm_bwd_blocks(M) * (H + G) * D * (long)sizeof(float);
+}
+
+/* g: fp32 dq|dk|dv joint rows; x: the stream's raw projections (T), inv: the forward's [M][H + G].  dx in T, natural head order.  With
+ * gammas, dgamma = [dgamma_q [H][D] | dgamma_k [G][D]] fp32 is stored (not added), summed in a fixed order through `workspace`
+ * (osuf_joint_qknorm_bwd_workspace_bytes bytes); without (both NULL) the kernel only permutes and casts: inv, dgamma and workspace unused. */
+extern "C" int osuf_joint_qknorm_bwd(int dtype, const float* g, long ldg, const void* x, long ldx, const float* inv, const float* gamma_q,
+                                     const float* gamma_k, void* dx, long lddx, float* dgamma, float* workspace, long workspace_bytes,
+                                     int M, int Ns, int Nj, int off, int H, int G, int D, hipStream_t stream) {
+  if (bad_joint(M, Ns, Nj, off, H, G, D) || ldg % 4 || ldx % 8 || lddx % 8 || ldg < (long)(H + 2 * G) * D || lddx < (long)(H + 2 * G) * D || !g || !dx ||
+      !al16(g) || !al16(dx))
+    return OSUF_EINVAL;
+  if ((gamma_q == nullptr) != (gamma_k == nullptr) || !al16(gamma_q) || !al16(gamma_k)) return OSUF_EINVAL;
+  const bool norm = gamma_q != nullptr;
+  if (norm && (!x || !al16(x) || ldx < (long)(H + 2 * G) * D || !inv || !dgamma || !workspace ||
+               workspace_bytes < osuf_joint_qknorm_bwd_workspace_bytes(M, H, G, D)))
+    return OSUF_EINVAL;
+  const int J = chunk_iters((H + 2 * G) * D / 8), nblk = qknorm_bwd_blocks(M), W = (H + G) * D;
+  if (J == 0) return OSUF_EUNSUPPORTED;
+  const size_t lds = norm ? (size_t)4 * W * sizeof(float) : 0;
+#define JQKN_BWD(J_) hipLaunchKernelGGL((joint_qknorm_bwd_kernel<T, J_>), dim3(nblk), dim3(256), lds, stream, g, ldg, (const T*)x, ldx, inv, gamma_q, gamma_k, \
+                                        (T*)dx, lddx, workspace, M, Ns, Nj, off, H, G, D)
+  DISPATCH_T(dtype, if (J == 1) JQKN_BWD(1); else if (J == 2) JQKN_BWD(2); else if (J == 4) JQKN_BWD(4); else JQKN_BWD(8));
+#undef JQKN_BWD
+  // one "sample" of (H + G) D columns: the first H D go to dgamma, the rest behind them (off2 = H D): [dgamma_q | dgamma_k]
+  if (norm)
+    hipLaunchKernelGGL(rowpart_finish_kernel, dim3((W + kFinCols - 1) / kFinCols, 1), dim3(kFinCols * kFinSlices), 0, stream, workspace, nblk, W, dgamma,
+                       (long)0, (long)H * D, H * D);
+  return osuf_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
 // audio statistics pooling (dit.py:275-277): out[b] = [mean_l a[b][c][l] | std_l a[b][c][l] (unbiased)], fp32 (B, C, L) contiguous
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void stat_pool_kernel(const float* a, float* out, int C, int L) {
