@@ -170,6 +170,14 @@ int osuf_rope_bwd(int dtype, const float* in, long ld_in, void* out, long ld_out
  * q/k/v/dout are bf16; o is written bf16-rounded in o_dtype; lse2 = log2-domain logsumexp [B][H][N]. */
 int osuf_mqa_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
                  float* lse2, int B, int H, int N, int head_dim, float scale, hipStream_t stream);
+/* Grouped-query attention forward in one launch: H query heads on G K/V heads (H % G == 0, r = H / G), the query heads and o laid out
+ * GROUP-MAJOR.  Group g reads its queries at column g * r * head_dim of q, its K / V head at column g * head_dim of k / v, and writes o at
+ * column g * r * head_dim and lse2 at [g][B][r][N]: the operands of G osuf_mqa_fwd calls with H = r, and the same bits in o and lse2.  The
+ * group is a grid dimension of the same kernels (head dim 64 tuned, 16 / 32 / 128 generic); G == 1 is osuf_mqa_fwd itself.  There are no
+ * pre-scaled-query, zero-fill or RoPE forms for groups.
+ * replaces: the GQA repeat (modules/unet.py:135, mmdit.py:112-116) + F.scaled_dot_product_attention (attention.py:94-99), forward only. */
+int osuf_gqa_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
+                 float* lse2, int B, int H, int G, int N, int head_dim, float scale, hipStream_t stream);
 /* osuf_mqa_fwd for queries pre-scaled by scale * log2(e) (osuf_rope_cast_qs); same outputs, same lse2 convention; head_dim 64.
  * replaces: F.scaled_dot_product_attention at attention.py:94-99 (as osuf_mqa_fwd). */
 int osuf_mqa_fwd_qs(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,

@@ -47,6 +47,7 @@ SIGNATURES = {
     "osuf_rope_cast_qs": [I, P, L, P, L, P, P, I, I, I, I, I, F, I, P],
     "osuf_rope_bwd": [I, P, L, P, L, P, P, I, I, I, I, I, P],
     "osuf_mqa_fwd": [P, L, P, L, P, L, P, L, I, P, I, I, I, I, F, P],
+    "osuf_gqa_fwd": [P, L, P, L, P, L, P, L, I, P, I, I, I, I, I, F, P],
     "osuf_mqa_fwd_qs": [P, L, P, L, P, L, P, L, I, P, I, I, I, I, F, P],
     "osuf_mqa_fwd_zdq": [P, L, P, L, P, L, P, L, I, P, I, I, I, I, F, I, P, P],
     "osuf_mqa_fwd_rope": [P, L, P, L, P, L, P, L, I, P, I, I, I, I, F, P, P, F, P, L, P, P],

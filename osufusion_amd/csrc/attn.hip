@@ -132,6 +132,15 @@ struct AttnArgs {
   int Nk;                                       // key rows per batch element: = N everywhere but osuf_xattn_* (read by the kernels of attn_generic.hpp only)
 };
 
+// Grouped-query forward (osuf_gqa_fwd): the operands of K/V group g when a.H = r query heads share each K/V head and hd is the head dim.  The
+// queries and o are laid out group-major (group g at column g r hd), K / V head g at column g hd, lse2 is [G][B][r][N].
+__device__ __forceinline__ void select_group(AttnArgs& a, int g, int hd) {
+  const long qcol = (long)g * a.H * hd;
+  a.q += qcol; a.k += g * hd; a.v += g * hd;
+  a.o = a.o_is_f32 ? (void*)(reinterpret_cast<float*>(a.o) + qcol) : (void*)(reinterpret_cast<bf16_t*>(a.o) + qcol);
+  a.lse2 += (long)g * a.B * a.H * a.N;
+}
+
 // cooperative K/V tile stage: NT threads move one 64-key tile (64 x 128 B of K and of V = 512 + 512 16-B chunks)
 template <int NT>
 struct KVStage {
@@ -220,9 +229,12 @@ struct KVStageInc {
 // WHOLE (N % 64 == 0): the K / V loads carry no bounds check and there is no masked copy of the tile body
 // ROPE (osuf_mqa_fwd_rope): the query tile is rotated (rcos / rsin) and multiplied by qmul in the prologue, rounded to bf16 once -- the arithmetic of
 // rope_cast_kernel, which then only has the K | V columns left to do -- and written to qout for the backward when that is given
-template <int NW, bool QS = false, bool WHOLE = false, bool ROPE = false>
+// GROUPS (osuf_gqa_fwd): blockIdx.z = the K/V group; a.H counts the query heads of ONE group and the workgroup first moves its operands to the group's
+// column blocks (select_group), so all its waves still share one staged K/V ring and each wave's arithmetic is that of the one-group launch
+template <int NW, bool QS = false, bool WHOLE = false, bool ROPE = false, bool GROUPS = false>
 __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void mqa_fwd_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];        // [2][K 8K | V 8K]
+  if constexpr (GROUPS) select_group(a, blockIdx.z, D);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
   const int b = blockIdx.y;
@@ -1902,6 +1914,31 @@ static int mqa_fwd_impl(const void* q, long ldq, const void* k, long ldk, const 
 extern "C" int osuf_mqa_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
                             float* lse2, int B, int H, int N, int head_dim, float scale, hipStream_t stream) {
   return mqa_fwd_impl(q, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, H, N, head_dim, scale, false, stream, nullptr);
+}
+// Grouped-query attention in ONE launch: H query heads laid out group-major on G K/V heads, r = H / G.  Group g reads its queries at column g r D of q,
+// its K / V head at column g D of k / v, writes o at column g r D and lse2 at [g][B][r][N] -- the operands of G osuf_mqa_fwd calls with H = r, which it
+// equals bit for bit (a wave's arithmetic depends on its (head, query block) and the key order alone).  The group is blockIdx.z; G = 1 IS osuf_mqa_fwd.
+extern "C" int osuf_gqa_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
+                            float* lse2, int B, int H, int G, int N, int head_dim, float scale, hipStream_t stream) {
+  if (G <= 0 || H <= 0 || H % G) return OSUF_EINVAL;
+  const int r = H / G;
+  if (G == 1) return mqa_fwd_impl(q, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, H, N, head_dim, scale, false, stream, nullptr);
+  AttnArgs a;
+  const int rc = fill_fwd_args(a, q, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, r, N, head_dim, scale);
+  if (rc) return rc;
+  if (head_dim % 8 || G > 65535) return OSUF_EINVAL;              // the groups' column offsets keep the 16-byte alignment; gridDim.z
+  const int nvb = ((N + 31) / 32) * r;
+  if (head_dim != D) {
+    const dim3 grid((nvb + 3) / 4, B, G);
+    if (gen_dp(head_dim) == 32) hipLaunchKernelGGL((mqa_gen_fwd_kernel<32, false, true>), grid, dim3(256), 2 * 64 * 64, stream, a, head_dim);
+    else hipLaunchKernelGGL((mqa_gen_fwd_kernel<128, false, true>), grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
+    return osuf_launch_status();
+  }
+  const dim3 grid((nvb + 7) / 8, B, G);
+  const int lds = 32768 + 8 * 4096;
+  if ((N & 63) == 0) hipLaunchKernelGGL((mqa_fwd_kernel<8, false, true, false, true>), grid, dim3(512), lds, stream, a);
+  else hipLaunchKernelGGL((mqa_fwd_kernel<8, false, false, false, true>), grid, dim3(512), lds, stream, a);
+  return osuf_launch_status();
 }
 // q holds the rotated queries ALREADY multiplied by scale * log2 e (osuf_rope_cast_qs): the scores leave the MFMA chain in the log2 domain
 extern "C" int osuf_mqa_fwd_qs(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,

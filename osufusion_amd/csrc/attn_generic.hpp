@@ -7,7 +7,7 @@
 // The three attention kernels take N query rows and Nk key rows per batch element (AttnArgs::Nk; every self-attention entry point sets
 // Nk = N, osuf_xattn_* pass their own): q, o, dO, dq, lse2, delta and the mask's query stride go by N, k, v, dk, dv and the mask's key
 // stride by Nk.
-// Included by attn.hip (it uses AttnArgs, acc_to_frag, fast_exp2, store4, kLog2e).
+// Included by attn.hip (it uses AttnArgs, select_group, acc_to_frag, fast_exp2, store4, kLog2e).
 #pragma once
 
 template <int DP>
@@ -74,10 +74,12 @@ __device__ __forceinline__ void gen_store_row(void* base, long elem_off, int is_
 // ---- forward (attention.py:94-99 under unet.py:125-141): 4 waves = 4 (head, 32-query block) pairs share each 64-key K / V tile.
 // MASKED: Attend's attn_mask (attention.py:77-99) -- the reference casts it to bf16 and hands it to SDPA as an ADDITIVE bias of the
 // scaled scores (a bool mask therefore adds 1.0 / 0.0; that is the reference's behaviour and is kept), broadcast over (B, H, N, N).
-template <int DP, bool MASKED = false>
+// GROUPS (osuf_gqa_fwd): blockIdx.z = the K/V group, a.H = the query heads of one group (select_group, attn.hip).
+template <int DP, bool MASKED = false, bool GROUPS = false>
 __global__ __launch_bounds__(256) void mqa_gen_fwd_kernel(AttnArgs a, int hd) {
   using T = GenTile<DP>;
   extern __shared__ __attribute__((aligned(16))) char smem[];        // K image 64 x RB | V image 64 x RB
+  if constexpr (GROUPS) select_group(a, blockIdx.z, hd);
   constexpr int TILE = 64 * T::RB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
   const int b = blockIdx.y, nqb = (a.N + 31) >> 5;

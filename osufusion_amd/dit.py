@@ -149,15 +149,17 @@ def adaln(x: torch.Tensor, mod: torch.Tensor, i_shift: int, i_scale: int, link=N
     return adaln_fwd(x, mod[:, i_shift * C:(i_shift + 1) * C], mod[:, i_scale * C:(i_scale + 1) * C])[0]
 
 
-def _attn_rows(x, w, gq, gk, cache, H: int, D: int):
-    """-> (raw projections, bf16 q|k|v rows, inv norms or None, o (bf16), lse2)."""
+def _attn_rows(x, w, gq, gk, cache, H: int, D: int, one_launch: bool = False):
+    """-> (raw projections, bf16 q|k|v rows, inv norms or None, o (bf16), lse2).  one_launch (inference): all H heads in one osuf_gqa_fwd
+    launch instead of one osuf_mqa_fwd launch per head; the same bits."""
     B, L, _ = x.shape
     raw = Fn.conv_forward(x, w, None, cache, "same")
     if gq is not None:
         qkv, inv = qknorm_fwd(raw, gq, gk, H, D)
     else:
         qkv, inv = ops.cast_rows(raw, torch.bfloat16), None
-    o, lse = ops.mqa_fwd(qkv, B, L, H, D, torch.bfloat16, D ** -0.5, kv_heads=H)
+    fwd = ops.gqa_fwd if one_launch else ops.mqa_fwd
+    o, lse = fwd(qkv, B, L, H, D, torch.bfloat16, D ** -0.5, kv_heads=H)
     return raw, qkv, inv, o, lse
 
 
@@ -195,7 +197,7 @@ class DiTAttentionFn(torch.autograd.Function):
 def dit_attention(x, w, gq, gk, cache, H: int, D: int) -> torch.Tensor:
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, gq, gk)):
         return DiTAttentionFn.apply(x, w, gq, gk, cache, H, D)
-    return ops.cast_rows(_attn_rows(x, w, gq, gk, cache, H, D)[3], x.dtype)      # nothing kept
+    return ops.cast_rows(_attn_rows(x, w, gq, gk, cache, H, D, one_launch=ops.one_launch_attention_on())[3], x.dtype)      # nothing kept
 
 
 class DiTFeedForwardFn(torch.autograd.Function):

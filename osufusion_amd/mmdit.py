@@ -99,8 +99,9 @@ def _qkv_packs(cache, dt, tag: str, wq, wk, wv):
     return cache.packs(("qkv", tag, dt), (wq, wk, wv), (wq, wk, wv), "same", dt)
 
 
-def _joint_rows(x, a, wx, wa, gx, ga, cache, H: int, G: int, D: int):
-    """-> (raw_x, raw_a, bf16 joint q|k|v rows, inv_x, inv_a, joint o (bf16), lse2).  Audio rows first."""
+def _joint_rows(x, a, wx, wa, gx, ga, cache, H: int, G: int, D: int, one_launch: bool = False):
+    """-> (raw_x, raw_a, bf16 joint q|k|v rows, inv_x, inv_a, joint o (bf16), lse2).  Audio rows first.  one_launch (inference): the G groups
+    in one osuf_gqa_fwd launch instead of one osuf_mqa_fwd launch each; the same bits."""
     B, Nx, _ = x.shape
     Na = a.shape[1]
     W = (H + 2 * G) * D
@@ -110,7 +111,8 @@ def _joint_rows(x, a, wx, wa, gx, ga, cache, H: int, G: int, D: int):
     qkv = joint_buffer(B, Na + Nx, W, x.device)
     inv_a = joint_qknorm_fwd(raw_a, qkv, 0, ga[0], ga[1], H, G, D)
     inv_x = joint_qknorm_fwd(raw_x, qkv, Na, gx[0], gx[1], H, G, D)
-    o, lse = ops.mqa_fwd(qkv, B, Na + Nx, H, D, torch.bfloat16, D ** -0.5, kv_heads=G)
+    fwd = ops.gqa_fwd if one_launch else ops.mqa_fwd
+    o, lse = fwd(qkv, B, Na + Nx, H, D, torch.bfloat16, D ** -0.5, kv_heads=G)
     return raw_x, raw_a, qkv, inv_x, inv_a, o, lse
 
 
@@ -186,5 +188,5 @@ def joint_attention(x, a, wx, wa, gx, ga, cache, H: int, G: int, D: int):
     """wx / wa: (to_q, to_k, to_v) weights of the map / audio stream; gx / ga: (gamma_q, gamma_k) or (None, None)."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, a, *wx, *wa, *gx, *ga)):
         return JointAttentionFn.apply(x, a, *wx, *wa, *gx, *ga, cache, H, G, D)
-    o = _joint_rows(x, a, wx, wa, gx, ga, cache, H, G, D)[5]                          # nothing kept
+    o = _joint_rows(x, a, wx, wa, gx, ga, cache, H, G, D, one_launch=ops.one_launch_attention_on())[5]    # nothing kept
     return joint_unpack(o, x.shape[1], a.shape[1], x.dtype, H, G, D), joint_unpack(o, a.shape[1], 0, a.dtype, H, G, D)

@@ -1,0 +1,177 @@
+"""The DiT / MMDiT backbones behind the reference's ``OsuFusion`` interface: ``DiffusionOsuFusionDiT`` mirrors models/diffusion.OsuFusion and
+``RectifiedFlowOsuFusionDiT`` models/rectified_flow.OsuFusion method for method (``forward`` = training loss, ``loss_with``, ``sample``,
+``set_full_bf16``).  The backbone is stored as ``self.unet``: the reference trainers call ``model.unet.set_gradient_checkpointing`` and write
+checkpoints with ``unet.``-prefixed keys, so train.py / data.py take these models as they are.
+
+``sample`` is restructured like the UNet samplers: everything that does not depend on the step -- the audio's embedding rows and
+where(keep, mlp_cond(c), null_cond) + mlp_a(feature_extractor_a(stat_pool(a))) -- is computed once per call, the conditional and null
+branches of classifier-free guidance run as one batch of 2B, the guidance combine rides the DDIM-step kernel, and the attention forward of
+every block is one launch over all K/V groups (ops.one_launch_attention -> osuf_gqa_fwd).  Not here: hipGraph capture of the step, LoRA
+on these backbones.
+"""
+from typing import Optional
+
+import torch
+import torch.nn as nn
+
+from .. import ops
+from .. import runtime as rt
+from ..modules.dit import DiT
+from ..modules.mmdit import MMDiT
+from .diffusion import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, DDIMSchedule, _MSEFn
+from .rectified_flow import cosmap
+
+BACKBONES = {"mmdit": MMDiT, "dit": DiT}
+
+
+class _TransformerOsuFusion(nn.Module):
+    """What the two variants share: the backbone as `unet`, the compute-dtype switch and the step-independent part of a sample call."""
+
+    def __init__(self, dim_h: int, backbone: str, cond_drop_prob: float, **backbone_kwargs) -> None:
+        super().__init__()
+        if backbone not in BACKBONES:
+            raise ValueError(f"backbone must be one of {sorted(BACKBONES)} (got {backbone!r})")
+        self.backbone = backbone
+        self.unet = BACKBONES[backbone](dim_in_x=TOTAL_DIM, dim_in_a=AUDIO_DIM, dim_in_c=CONTEXT_DIM, dim_h=dim_h, **backbone_kwargs)
+        self.cond_drop_prob = cond_drop_prob
+        self._full_bf16 = False
+
+    def set_full_bf16(self) -> None:
+        """Keeps fp32 master weights; all kernels compute in bf16 (see models/diffusion.py)."""
+        self._full_bf16 = True
+
+    def _dtype_ctx(self):
+        return rt.forced_compute_dtype(torch.bfloat16 if self._full_bf16 else None)
+
+    def _denoiser(self, a: torch.Tensor, c: torch.Tensor, cfg: bool):
+        """-> f(x (b, 6, n) fp32, t (nb,)) = the prediction (nb, 6, n), nb = 2b with guidance (conditional rows first), else b.  The audio
+        rows and the step-independent conditioning vector are computed here, once."""
+        net = self.unet
+        b, n = a.shape[0], a.shape[-1]
+        dtype = rt.compute_dtype(next(net.parameters()).dtype)
+        keep = torch.ones(b, dtype=torch.bool, device=a.device)
+        a_rows = net.encode_audio(a, dtype)
+        if cfg:
+            a_rows = torch.cat([a_rows, a_rows], 0)
+            static = net.embed_static(torch.cat([a, a], 0), torch.cat([c, c], 0), torch.cat([keep, ~keep], 0))
+        else:
+            static = net.embed_static(a, c, keep)
+
+        def f(x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+            xin = torch.cat([x, x], 0) if cfg else x
+            cvec = (static + net.embed_time(t)).contiguous()
+            if self.backbone == "mmdit":
+                return net.denoise_rows(net.encode_x(xin, dtype), a_rows, cvec, n).contiguous()
+            return net.denoise_rows(net.encode_x(xin, a_rows, dtype), cvec, n).contiguous()
+        return f
+
+    def _start(self, a: torch.Tensor, x: Optional[torch.Tensor]) -> torch.Tensor:
+        rt.require_gpu(a)
+        if x is None:
+            x = torch.randn((a.shape[0], TOTAL_DIM, a.shape[-1]), device=a.device)
+        rt.require_gpu(x)
+        return x.float().contiguous()
+
+
+class DiffusionOsuFusionDiT(_TransformerOsuFusion):
+    def __init__(self, dim_h: int, backbone: str = "mmdit", cond_drop_prob: float = 0.5, train_timesteps: int = 1000,
+                 sampling_timesteps: int = 35, **backbone_kwargs) -> None:
+        super().__init__(dim_h, backbone, cond_drop_prob, **backbone_kwargs)
+        self.scheduler = DDIMSchedule(num_train_timesteps=train_timesteps)
+        self.train_timesteps = train_timesteps
+        self.sampling_timesteps = sampling_timesteps
+        self.stop_after: Optional[int] = None
+
+    @torch.inference_mode()
+    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0) -> torch.Tensor:
+        """diffusion.py:59-77 on the transformer backbones.  Bit-reproducible.  (Attribute `stop_after`, None by default: return the iterate
+        after that many of the sampling_timesteps steps, as models/diffusion.OsuFusion.)"""
+        with ops.reproducible_mode(True), ops.one_launch_attention(True):
+            return self._sample(a, c, x, cond_scale, self.stop_after)
+
+    def _sample(self, a, c, x, cond_scale, stop_after):
+        x_buf = self._start(a, x)
+        b, device = a.shape[0], a.device
+        cfg = cond_scale != 1.0
+        self.scheduler.set_timesteps(self.sampling_timesteps)
+        steps = self.scheduler.timesteps.tolist()
+        if stop_after is not None:
+            steps = steps[:stop_after]
+        nb = 2 * b if cfg else b
+        with self._dtype_ctx():
+            f = self._denoiser(a, c, cfg)
+            coef_table = torch.tensor([[self.scheduler.step_coefficients(t)] * b for t in steps], dtype=torch.float32, device=device)
+            t_table = torch.tensor([[t] * nb for t in steps], dtype=torch.int64, device=device)
+            for i in range(len(steps)):
+                pred = f(x_buf, t_table[i])
+                x_buf = ops.ddim_step(x_buf, pred[:b], pred[b:] if cfg else None, cond_scale, coef_table[i])
+        return x_buf
+
+    def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+        assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"
+        rt.require_gpu(x)
+        noise = torch.randn_like(x, device=x.device)
+        timesteps = torch.randint(0, self.scheduler.num_train_timesteps, (x.shape[0],), dtype=torch.int64, device=x.device)
+        return self.loss_with(x, a, c, noise, timesteps, orig_len)
+
+    def loss_with(self, x, a, c, noise, timesteps, orig_len=None, cond_drop_prob: Optional[float] = None) -> torch.Tensor:
+        """forward() with the RNG draws passed in (parity tests, benchmarks)."""
+        p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
+        with self._dtype_ctx():
+            x_noisy = self.scheduler.add_noise(x, noise, timesteps)
+            pred = self.unet(x_noisy, a, timesteps, c, cond_drop_prob=p)
+        return _MSEFn.apply(pred, noise.float(), orig_len)
+
+
+class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
+    def __init__(self, dim_h: int, backbone: str = "mmdit", cond_drop_prob: float = 0.5, sampling_timesteps: int = 16,
+                 **backbone_kwargs) -> None:
+        super().__init__(dim_h, backbone, cond_drop_prob, **backbone_kwargs)
+        self.sample_timesteps = sampling_timesteps
+
+    @torch.inference_mode()
+    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0) -> torch.Tensor:
+        """rectified_flow.py:57-79 on the transformer backbones: the fixed-grid midpoint loop, 2 * (S - 1) evaluations.  Bit-reproducible."""
+        with ops.reproducible_mode(True), ops.one_launch_attention(True):
+            return self._sample(a, c, x, cond_scale)
+
+    def _sample(self, a, c, x, cond_scale):
+        x = self._start(a, x)
+        b, device = a.shape[0], a.device
+        cfg = cond_scale != 1.0
+        ones = torch.ones(b, dtype=torch.float32, device=device)
+        with self._dtype_ctx():
+            den = self._denoiser(a, c, cfg)
+
+            def f(t: float, y: torch.Tensor) -> torch.Tensor:
+                out = den(y, torch.full((2 * b if cfg else b,), t, dtype=torch.float32, device=device))
+                if cfg:                                    # null + (cond - null) * s  ==  (1 - s) * null + s * cond
+                    out = ops.axpby_rows(out[b:].contiguous(), out[:b].contiguous(), ones * (1.0 - cond_scale), ones * cond_scale)
+                return out
+
+            times = torch.linspace(0.0, 1.0, self.sample_timesteps).tolist()
+            for t0, t1 in zip(times[:-1], times[1:]):
+                dt = t1 - t0
+                k1 = f(t0, x)
+                k2 = f(t0 + 0.5 * dt, ops.axpby_rows(x, k1, ones, ones * (0.5 * dt)))
+                x = ops.axpby_rows(x, k2, ones, ones * dt)
+        return x
+
+    def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+        assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"
+        rt.require_gpu(x)
+        noise = torch.randn_like(x, device=x.device)
+        times = torch.rand(x.shape[0], device=x.device)
+        return self.loss_with(x, a, c, noise, times, orig_len)
+
+    def loss_with(self, x, a, c, noise, times, orig_len=None, cond_drop_prob: Optional[float] = None) -> torch.Tensor:
+        """forward() with the RNG draws passed in (parity tests, benchmarks)."""
+        p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
+        x, noise = x.float().contiguous(), noise.float().contiguous()
+        t = cosmap(times.float())
+        ones = torch.ones_like(t)
+        with self._dtype_ctx():
+            x_noisy = ops.axpby_rows(x, noise, t.contiguous(), (1 - t).contiguous())
+            flow = ops.axpby_rows(x, noise, ones, -ones)
+            pred = self.unet(x_noisy, a, times.float(), c, cond_drop_prob=p)
+        return _MSEFn.apply(pred, flow, orig_len)

@@ -226,6 +226,55 @@ class DiT(nn.Module):
         ae = rt.small_linear(ae, self.mlp_audio[2].weight, self.mlp_audio[2].bias, in_act=ops.ACT_SILU)
         return e + te + ae
 
+    def embed_static(self, a: torch.Tensor, c: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
+        """The part of embed() that does not depend on t: where(keep, mlp_cond(c), null_cond) + mlp_audio(feature_extractor_a(stat_pool(a))),
+        fp32 (B, dim_h).  keep: bool (B,).  A sampler computes it once per call and adds embed_time(t) per step."""
+        fe = self.feature_extractor_a
+        h_a = rt.small_linear(Dt.stat_pool(a), fe.weight, fe.bias)
+        B = a.shape[0]
+        e = rt.small_linear(c.float(), self.mlp_cond[0].weight, self.mlp_cond[0].bias)
+        e = rt.small_linear(e, self.mlp_cond[2].weight, self.mlp_cond[2].bias, in_act=ops.ACT_SILU)
+        e = torch.where(keep[:, None], e, self.null_cond.float()[None, :].expand(B, -1))
+        ae = rt.small_linear(h_a, self.mlp_audio[0].weight, self.mlp_audio[0].bias)
+        ae = rt.small_linear(ae, self.mlp_audio[2].weight, self.mlp_audio[2].bias, in_act=ops.ACT_SILU)
+        return e + ae
+
+    def embed_time(self, t: torch.Tensor) -> torch.Tensor:
+        """mlp_time(t), fp32 (B, dim_h)."""
+        te = rt.small_linear(self.mlp_time[0](t), self.mlp_time[1].weight, None)
+        return rt.small_linear(te, self.mlp_time[3].weight, None, in_act=ops.ACT_SILU)
+
+    def encode_audio(self, a: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+        """The audio's share of the stem, rows (B, L, dim_h): preprocess is linear in cat(x, a), so its audio input channels (and the bias)
+        are applied once per sample call; encode_x adds the map channels' share per step.  Differs from _stem by one rounding of this
+        partial sum to the compute dtype and the order of the sum."""
+        pre = self.preprocess
+        w, b = pre._merged()
+        nx = self.dim_in_x
+        rows = Fn.RowsFromNCLFn.apply(a.float().contiguous(), dtype, a.shape[1], 1)
+        return Fn.ConvFn.apply(rows, w[:, nx:].contiguous(), b, self._stem_cache, "same", ("dit_stem_a", *[c.weight for c in pre.convs]))
+
+    def encode_x(self, x: torch.Tensor, a_rows: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+        """preprocess(cat(x, a)) as rows from the audio's share (encode_audio): the map channels' tap GEMM with a_rows added in its epilogue."""
+        pre = self.preprocess
+        nx = self.dim_in_x
+        npad = (nx + 7) // 8 * 8
+        w = F.pad(pre._merged()[0][:, :nx], (0, 0, 0, npad - nx))
+        rows = Fn.RowsFromNCLFn.apply(F.pad(x.float(), (0, 0, 0, npad - nx)).contiguous(), dtype, npad, 1)
+        return Fn.conv_forward(rows, w, None, self._stem_cache, "same", ("dit_stem_x", *[c.weight for c in pre.convs]), residual=a_rows)
+
+    def denoise_rows(self, h: torch.Tensor, cvec: torch.Tensor, n: int) -> torch.Tensor:
+        """The stem's rows (B, L, dim_h) and the conditioning vector (fp32 (B, dim_h), contiguous) -> the prediction (B, dim_in_x, n)."""
+        mods = self._modulations(cvec)
+        for block, mod in zip(self.blocks, mods[:-1]):
+            h = block.forward_rows(h, mod)
+        h = self.final.forward_rows(h, mods[-1])
+        nx = self.dim_in_x
+        npad = (nx + 7) // 8 * 8
+        w = F.pad(self.postprocess.weight[:, :, 0], (0, 0, 0, npad - nx))
+        y = Fn.ConvFn.apply(h, w, None, self._post_cache, "same", ("post", self.postprocess.weight))
+        return Fn.NCLFromRowsFn.apply(y, nx)[:, :, :n]
+
     def _modulations(self, cvec: torch.Tensor):
         """The depth + 1 Sequential(SiLU, Linear) projections of c: one grouped launch (runtime.film_prepare), else one each."""
         lins = [b.modulation[1] for b in self.blocks] + [self.final.modulation[1]]
@@ -243,12 +292,4 @@ class DiT(nn.Module):
         dtype = rt.compute_dtype(self.postprocess.weight.dtype)
         h = self._stem(x, a, dtype)
         cvec = self.embed(a, t, c, cond_drop_prob).contiguous()
-        mods = self._modulations(cvec)
-        for block, mod in zip(self.blocks, mods[:-1]):
-            h = block.forward_rows(h, mod)
-        h = self.final.forward_rows(h, mods[-1])
-        nx = self.dim_in_x
-        npad = (nx + 7) // 8 * 8
-        w = F.pad(self.postprocess.weight[:, :, 0], (0, 0, 0, npad - nx))
-        y = Fn.ConvFn.apply(h, w, None, self._post_cache, "same", ("post", self.postprocess.weight))
-        return Fn.NCLFromRowsFn.apply(y, nx)[:, :, :n]
+        return self.denoise_rows(h, cvec, n)

@@ -265,6 +265,47 @@ class MMDiT(nn.Module):
         e = torch.where(cond_mask[:, None], e, self.null_cond.float()[None, :].expand(B, -1))
         return e + self._ff(self.mlp_time[0](t).float(), self.mlp_time[1]) + self._ff(h_a, self.mlp_a)
 
+    def embed_static(self, a: torch.Tensor, c: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
+        """The part of embed() that does not depend on t: where(keep, mlp_cond(c), null_cond) + mlp_a(feature_extractor_a(stat_pool(a))),
+        fp32 (B, dim_h).  keep: bool (B,).  A sampler computes it once per call and adds embed_time(t) per step."""
+        fe = self.feature_extractor_a
+        h_a = rt.small_linear(Dt.stat_pool(a), fe.weight, fe.bias)
+        B = a.shape[0]
+        e = self._ff(rt.small_linear(c.float(), self.mlp_cond[0].weight, self.mlp_cond[0].bias), self.mlp_cond[1])
+        e = torch.where(keep[:, None], e, self.null_cond.float()[None, :].expand(B, -1))
+        return e + self._ff(h_a, self.mlp_a)
+
+    def embed_time(self, t: torch.Tensor) -> torch.Tensor:
+        """mlp_time(t), fp32 (B, dim_h)."""
+        return self._ff(self.mlp_time[0](t).float(), self.mlp_time[1])
+
+    def pad_len(self, n: int) -> int:
+        p = self.patch_size
+        return (p - n % p) % p
+
+    def encode_audio(self, a: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+        """The audio stream's patch-embedding rows (B, ceil(L / p), dim_h): independent of t and x."""
+        return self.emb_a.forward_rows(F.pad(a.float(), (0, self.pad_len(a.shape[-1])), value=-23.0), dtype)
+
+    def encode_x(self, x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+        return self.emb_x.forward_rows(F.pad(x.float(), (0, self.pad_len(x.shape[-1])), value=-1.0), dtype)
+
+    def denoise_rows(self, h_x: torch.Tensor, h_a: torch.Tensor, cvec: torch.Tensor, n: int) -> torch.Tensor:
+        """The two streams' patch rows and the conditioning vector (fp32 (B, dim_h), contiguous) -> the prediction (B, dim_in_x, n)."""
+        p = self.patch_size
+        mods = self._modulations(cvec)
+        for i, block in enumerate(self.blocks):
+            h_x, h_a = block.forward_rows(h_x, h_a, mods[2 * i], mods[2 * i + 1])
+        h = self.final_layer.forward_rows(h_x, mods[-1])                        # (B, N, p dim_h)
+        B, N, _ = h.shape
+        h = h.view(B, N * p, self.dim_h)                                        # "b n (p d) -> b (n p) d": a view of the rows
+        nx = self.dim_in_x
+        npad = _pad8(nx)
+        w = F.pad(self.out.weight[:, :, 0], (0, 0, 0, npad - nx))
+        b = F.pad(self.out.bias, (0, npad - nx))
+        y = Fn.ConvFn.apply(h, w, b, self._out_cache, "same", ("out", self.out.weight))
+        return Fn.NCLFromRowsFn.apply(y, nx)[:, :, :n]
+
     def _modulations(self, cvec: torch.Tensor):
         """The 2 depth + 1 Sequential(SiLU, Linear) projections of c: one grouped launch (runtime.film_prepare), else one each."""
         lins = [m for b in self.blocks for m in (b.modulation_x[1], b.modulation_a[1])] + [self.final_layer.modulation[1]]
@@ -285,15 +326,4 @@ class MMDiT(nn.Module):
         pad_len = (p - n % p) % p
         h_x = self.emb_x.forward_rows(F.pad(x.float(), (0, pad_len), value=-1.0), dtype)
         h_a = self.emb_a.forward_rows(F.pad(a.float(), (0, pad_len), value=-23.0), dtype)
-        mods = self._modulations(cvec)
-        for i, block in enumerate(self.blocks):
-            h_x, h_a = block.forward_rows(h_x, h_a, mods[2 * i], mods[2 * i + 1])
-        h = self.final_layer.forward_rows(h_x, mods[-1])                        # (B, N, p dim_h)
-        B, N, _ = h.shape
-        h = h.view(B, N * p, self.dim_h)                                        # "b n (p d) -> b (n p) d": a view of the rows
-        nx = self.dim_in_x
-        npad = _pad8(nx)
-        w = F.pad(self.out.weight[:, :, 0], (0, 0, 0, npad - nx))
-        b = F.pad(self.out.bias, (0, npad - nx))
-        y = Fn.ConvFn.apply(h, w, b, self._out_cache, "same", ("out", self.out.weight))
-        return Fn.NCLFromRowsFn.apply(y, nx)[:, :, :n]
+        return self.denoise_rows(h_x, h_a, cvec, n)

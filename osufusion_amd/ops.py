@@ -112,6 +112,30 @@ class reproducible_mode:
         return False
 
 
+# One-launch grouped attention (the DiT / MMDiT samplers): the no-grad attention of osufusion_amd/dit.py and mmdit.py issues gqa_fwd -- every
+# K/V group in one launch -- instead of mqa_fwd's launch per group.  Off everywhere else: training and the plain no-grad forward keep their launches.
+_ONE_LAUNCH_ATTENTION = False
+
+
+def one_launch_attention_on() -> bool:
+    return _ONE_LAUNCH_ATTENTION
+
+
+class one_launch_attention:
+    def __init__(self, flag: bool = True) -> None:
+        self.flag = bool(flag)
+
+    def __enter__(self):
+        global _ONE_LAUNCH_ATTENTION
+        self.prev, _ONE_LAUNCH_ATTENTION = _ONE_LAUNCH_ATTENTION, self.flag
+        return self
+
+    def __exit__(self, *exc):
+        global _ONE_LAUNCH_ATTENTION
+        _ONE_LAUNCH_ATTENTION = self.prev
+        return False
+
+
 def set_kernel_timer(t: Optional[KernelTimer]) -> None:
     global _TIMER
     _TIMER = t
@@ -513,6 +537,14 @@ def mqa_fwd(qkv: torch.Tensor, B: int, N: int, H: int, D: int, out_dtype: torch.
         call("osuf_mqa_fwd_qs" if qs else "osuf_mqa_fwd", base + 2 * g * r * D, ld, base + 2 * (H + g) * D, ld, base + 2 * (H + G + g) * D, ld, o.data_ptr() + eo * g * r * D,
              H * D, _DT[out_dtype], lse.data_ptr() + 4 * g * B * r * N, B, r, N, D, scale, _stream(), meta=LaunchSize(N, B))
     return o, lse
+
+
+def gqa_fwd(qkv: torch.Tensor, B: int, N: int, H: int, D: int, out_dtype: torch.dtype, scale: float, kv_heads: int = 1):
+    """mqa_fwd(kv_heads=G) in ONE launch (osuf_gqa_fwd: the K/V group is a grid dimension): same operands, same (o, lse2) shapes and layouts
+    -- lse2 [B][H][N] for G == 1, else [G][B][H/G][N] -- and the same bits.  Forward only (inference): no pre-scaled-query / zero_dq forms.
+    The allocating wrapper lives in osufusion_amd/gqa.py (its guarded-memory case in tests/test_gqa_fwd_gpu.py)."""
+    from . import gqa
+    return gqa.gqa_fwd(qkv, B, N, H, D, out_dtype, scale, kv_heads)
 
 
 def fwd_rope_ok(qkv: torch.Tensor, head_dim: int, kv_heads: int, qs: bool) -> bool:
