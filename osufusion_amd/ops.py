@@ -232,11 +232,12 @@ def gemm_nt(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = Non
     Mo, No, ldc = _rows(out)
     assert Mo == M and No >= N
     pre = torch.empty_like(out) if want_pre else None
+    ldc2 = _rows(pre)[2] if want_pre else 0                    # its own row stride: empty_like of a column slice is dense
     ldr = _rows(residual)[2] if residual is not None else 0
     ldu = _rows(dact)[2] if dact is not None else 0
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() >= N
-    call("osuf_gemm_nt", gemm_dt(a), _p(a), lda, _p(w3), K, N * K if taps > 1 else 0, _p(out), ldc, _p(pre), ldc, _p(residual), ldr,
+    call("osuf_gemm_nt", gemm_dt(a), _p(a), lda, _p(w3), K, N * K if taps > 1 else 0, _p(out), ldc, _p(pre), ldc2, _p(residual), ldr,
          _p(dact), ldu, _p(bias), _p(rscale), _p(stats), M, N, K, taps, lin, lout, stride, pad, mode, act, _stream())
     return (out, pre) if want_pre else out
 

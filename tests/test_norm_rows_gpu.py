@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from osufusion_amd import ops
+from tests import bound_check
 from tests import norm_reference as R
 from tests.test_hip_parity import report
 from tests.test_poisoned_memory import relmax, rell2, rnd
@@ -41,35 +42,8 @@ def tag(dtype):
     return "f32" if dtype == F32 else "bf16"
 
 
-class Check:
-    """Collects (quantity, achieved error, bound) of one case; done() reports all of them, then asserts."""
-
-    def __init__(self, kernel, dtype, **where):
-        self.kernel, self.dtype, self.where, self.rows = kernel, dtype, where, []
-
-    def bound(self, ref32, ref64, metric, cap, extra=0.0):
-        return min(max(16 * metric(ref32, ref64), FLOOR) + extra, cap)
-
-    def f32(self, key, got, ref64, ref32, metric, cap, extra=0.0):
-        """An output of fp32 arithmetic (in either storage mode)."""
-        assert got.dtype == F32, (key, got.dtype)
-        self.rows.append((key, metric(got.cpu(), ref64), self.bound(ref32, ref64, metric, cap, extra)))
-
-    def out(self, key, got, ref64, ref32, cap, extra=0.0):
-        """An elementwise output in the storage dtype."""
-        if got.dtype == F32:
-            return self.f32(key, got, ref64, ref32, relmax, cap, extra)
-        assert got.dtype == torch.bfloat16, (key, got.dtype)
-        b = self.bound(ref32, ref64, relmax, cap, extra)
-        allow = 2.0 ** -7 * ref64.abs() + b * ref64.abs().max()
-        self.rows.append((key + "_bf16", ((got.cpu().double() - ref64).abs() / allow).max().item(), 1.0))
-
-    def done(self):
-        report(f"norm_rows::{self.kernel}", dtype=tag(self.dtype), **self.where,
-               **{k: e for k, e, _ in self.rows}, **{k + "_bound": b for k, _, b in self.rows})
-        print(self.kernel, tag(self.dtype), self.where, [(k, f"{e:.3g}", f"{b:.3g}") for k, e, b in self.rows])
-        bad = [(k, e, b) for k, e, b in self.rows if not e <= b]
-        assert not bad, bad
+class Check(bound_check.Check):
+    prefix = "norm_rows"
 
 
 def affine(C):
