@@ -198,6 +198,8 @@ int osuf_mqa_fwd_rope(const void* q_raw, long ldq, const void* k, long ldk, cons
 /* Attend(q, k, v, attn_mask) (attention.py:77-99): the reference casts the mask to bf16 and passes it to SDPA as an additive bias of
  * the scaled scores (so a bool mask adds 1.0 / 0.0 -- kept).  mask: bf16, element strides over (batch, head, query, key), 0 for a
  * broadcast dimension.  All head dims go through the generic kernel; its backward is osuf_mqa_bwd_masked.
+ * It is osuf_xattn_fwd with Nk = N and a mask that must be there (OSUF_EINVAL for mask == NULL), so lse2 is required: the kernel
+ * writes it unconditionally, and lse2 == NULL returns OSUF_EINVAL (earlier versions did not check it).
  * replaces: F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask) at attention.py:94-99. */
 int osuf_mqa_fwd_masked(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
                         float* lse2, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k, int B, int H, int N,
@@ -206,7 +208,7 @@ int osuf_mqa_fwd_masked(const void* q, long ldq, const void* k, long ldk, const 
  * h * head_dim), dk / dv ([B*N][lddk]) in out_dtype (OSUF_DT_F32 or OSUF_DT_BF16) are the gradients of the ROTATED q / k and of v (no RoPE
  * tables: the caller applies osuf_rope_bwd).  The bias restarts the scores exactly as in the forward.  dbias (may be NULL): dense fp32
  * [B][H][N][N], 16-byte aligned, receives dL/d(bias) = P (dP - delta) for every (query, key); it is never accumulated into.  Rows whose
- * every key is -inf are NaN in the forward and therefore in the backward.
+ * every key is -inf are NaN in the forward and therefore in the backward.  It is osuf_xattn_bwd with Nk = N and a mask that must be there.
  * replaces: the backward of F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask) at attention.py:94-99. */
 int osuf_mqa_bwd_masked(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
                         const float* lse2, const float* delta, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k,

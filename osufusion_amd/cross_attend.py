@@ -1,12 +1,12 @@
-"""Cross-attention for the stand-alone ``Attend`` module: keys and values of their own length (modules/attention.py).
+"""The generic path of the stand-alone ``Attend`` module (modules/attention.py): any query count, any key count, mask or none.
 
 The reference's Attend is F.scaled_dot_product_attention on bf16 copies (attention.py:61-101): q (B, H, Nq, D), k / v (B, 1|H, Nk, D), an
-optional additive mask broadcastable to (B, H, Nq, Nk).  attend.py serves Nk == Nq (one q|k|v row image per launch, the tuned kernels at
-head dim 64); a call with another key count comes here and runs osuf_xattn_fwd / osuf_xattn_bwd -- the generic kernels of
-csrc/attn_generic.hpp with separate query and key counts, one K/V head per launch, every head dim, mask or none.
+optional additive mask broadcastable to (B, H, Nq, Nk).  attend.py keeps the unmasked Nk == Nq call (the tuned kernels at head dim 64); a
+call with a mask -- masked self-attention included -- or with another key count comes here and runs osuf_xattn_fwd / osuf_xattn_bwd: the
+generic kernels of csrc/attn_generic.hpp, one K/V head per launch, every head dim; q, k, v may be column views of one row image.
   * check_shapes: what Attend.forward validates before anything is launched (pure, callable on CPU tensors).
   * xattn_fwd / xattn_bwd: the allocating wrappers, one C-ABI launch (plus osuf_attn_delta in the backward) each.
-  * CrossAttendFn / cross_attend: AttendFn's contract -- bf16-cast inputs, output in v.dtype, gradients in each input's dtype, a k / v with
+  * CrossAttendFn / cross_attend: Attend's contract -- bf16-cast inputs, output in v.dtype, gradients in each input's dtype, a k / v with
     one head gets its gradient summed over the query heads (by the dK/dV kernel itself), a floating-point mask that requires grad gets the
     dense bias gradient summed to its own shape.  Under no_grad the bare launches keep nothing.
 Rows whose every key is masked with -inf are NaN in the forward (as in SDPA) and therefore in the backward.
@@ -89,12 +89,12 @@ def xattn_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask4: Optional
 
 
 # ---------------------------------------------------------------------------------------------------------
-# Attend with Nk != Nq
+# Attend with a mask or with Nk != Nq
 # ---------------------------------------------------------------------------------------------------------
-def _rows(t: torch.Tensor) -> torch.Tensor:
-    """(B, h, N, D) -> contiguous bf16 rows (B, N, h * D)"""
-    B, h, N, D = t.shape
-    return t.permute(0, 2, 1, 3).reshape(B, N, h * D).to(torch.bfloat16).contiguous()
+def _rows(t: torch.Tensor, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """(B, h, N, D) -> rows (B, N, h * D): as they come (a copy unless h == 1) or, with a dtype, cast to it and contiguous"""
+    rows = t.permute(0, 2, 1, 3).reshape(t.shape[0], t.shape[2], -1)
+    return rows if dtype is None else rows.to(dtype).contiguous()
 
 
 def _heads(rows: torch.Tensor, B: int, N: int, D: int) -> torch.Tensor:
@@ -120,7 +120,7 @@ def cross_attend_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn
         qs = q if G == 1 else q[:, g:g + 1]
         ms = m4 if (G == 1 or m4 is None) else m4[:, g:g + 1]
         Hq = qs.shape[1]
-        qr, kr, vr = _rows(qs), _rows(k[:, g:g + 1]), _rows(v[:, g:g + 1])
+        qr, kr, vr = (_rows(t, torch.bfloat16) for t in (qs, k[:, g:g + 1], v[:, g:g + 1]))
         o, lse = xattn_fwd(qr, kr, vr, ms, B, Nq, Nk, Hq, D, torch.bfloat16, D ** -0.5)
         outs.append(o.view(B, Nq, Hq, D))
         parts.append((qr, kr, vr, o, lse))
@@ -147,7 +147,7 @@ class CrossAttendFn(torch.autograd.Function):
         saved = ctx.saved_tensors
         parts = [saved[5 * i:5 * i + 5] for i in range(ctx.n_parts)]
         m4 = saved[-1] if ctx.mask_meta is not None else None
-        do = _rows(go)                                       # the reference's out.to(dtype) hands SDPA a bf16 gradient
+        do = _rows(go, torch.bfloat16)                       # the reference's out.to(dtype) hands SDPA a bf16 gradient
         want_dbias = ctx.mask_meta is not None and ctx.mask_meta[2] and ctx.needs_input_grad[3]
         Hq = H if G == 1 else 1
         dq, dk, dv, db = [], [], [], []

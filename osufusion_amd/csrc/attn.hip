@@ -1870,6 +1870,36 @@ static inline int attn_ew_grid(long total_threads) {        // common.hpp's ew_g
 }
 // head dims served by the generic kernels of attn_generic.hpp (64 has the tuned kernels of this file): padded tile width, 0 = unsupported
 static int gen_dp(int head_dim) { return head_dim == 16 || head_dim == 32 ? 32 : head_dim == 128 ? 128 : 0; }
+// The one ladder over the generic kernels' tile width: f(std::integral_constant<int, DP>) for a head dim the caller has checked (64 runs as DP = 64).
+template <typename F> static void for_gen_dp(int head_dim, F f) {
+  const int dp = head_dim == D ? 64 : gen_dp(head_dim);
+  if (dp == 32) f(std::integral_constant<int, 32>{});
+  else if (dp == 64) f(std::integral_constant<int, 64>{});
+  else f(std::integral_constant<int, 128>{});
+}
+// The launches of the generic kernels, each with its grid and LDS bytes: 4 waves = 4 (head, 32-query block) pairs over K | V images of 64 rows
+// (forward, dQ); 4 waves = 128 keys over Q | dO images of 32 rows + 32 lse2 + 32 delta (dK/dV).  groups: gridDim.z of a GROUPS forward, else 1.
+template <bool MASKED, bool GROUPS> static void launch_gen_fwd(const AttnArgs& a, int head_dim, int groups, hipStream_t stream) {
+  const int nvb = ((a.N + 31) / 32) * a.H;
+  for_gen_dp(head_dim, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    if constexpr (DP != 64 || !GROUPS)                           // osuf_gqa_fwd's head dim 64 has the tuned kernel: no generic instantiation
+      hipLaunchKernelGGL((mqa_gen_fwd_kernel<DP, MASKED, GROUPS>), dim3((nvb + 3) / 4, a.B, groups), dim3(256), 2 * 64 * GenTile<DP>::RB, stream, a, head_dim);
+  });
+}
+template <bool MASKED> static void launch_gen_bwd_dq(const AttnArgs& a, int head_dim, hipStream_t stream) {
+  const int nvb = ((a.N + 31) / 32) * a.H;
+  for_gen_dp(head_dim, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<DP, MASKED>), dim3((nvb + 3) / 4, a.B), dim3(256), 2 * 64 * GenTile<DP>::RB, stream, a, head_dim);
+  });
+}
+template <bool MASKED> static void launch_gen_bwd_dkv(const AttnArgs& a, int head_dim, float* dbias, hipStream_t stream) {
+  for_gen_dp(head_dim, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<DP, MASKED>), dim3(((a.Nk + 127) / 128) * a.B), dim3(256), 2 * 32 * GenTile<DP>::RB + 256, stream, a, head_dim, dbias);
+  });
+}
 // argument checks and AttnArgs of the forward entry points
 static int fill_fwd_args(AttnArgs& a, const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
                          float* lse2, int B, int H, int N, int head_dim, float scale) {
@@ -1893,9 +1923,7 @@ static int mqa_fwd_impl(const void* q, long ldq, const void* k, long ldk, const 
   if (rope) { a.rcos = rope->cos; a.rsin = rope->sin; a.qmul = rope->qmul; a.qout = (bf16_t*)rope->qout; a.ldqo = rope->ldqo; }
   const int nvb = ((N + 31) / 32) * H;
   if (head_dim != D) {
-    const dim3 grid((nvb + 3) / 4, B);
-    if (gen_dp(head_dim) == 32) hipLaunchKernelGGL(mqa_gen_fwd_kernel<32>, grid, dim3(256), 2 * 64 * 64, stream, a, head_dim);
-    else hipLaunchKernelGGL(mqa_gen_fwd_kernel<128>, grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
+    launch_gen_fwd<false, false>(a, head_dim, 1, stream);
     return osuf_launch_status();
   }
   const bool whole = (N & 63) == 0 && getenv("OSUF_ATTN_FWD_NOWHOLE") == nullptr;
@@ -1929,9 +1957,7 @@ extern "C" int osuf_gqa_fwd(const void* q, long ldq, const void* k, long ldk, co
   if (head_dim % 8 || G > 65535) return OSUF_EINVAL;              // the groups' column offsets keep the 16-byte alignment; gridDim.z
   const int nvb = ((N + 31) / 32) * r;
   if (head_dim != D) {
-    const dim3 grid((nvb + 3) / 4, B, G);
-    if (gen_dp(head_dim) == 32) hipLaunchKernelGGL((mqa_gen_fwd_kernel<32, false, true>), grid, dim3(256), 2 * 64 * 64, stream, a, head_dim);
-    else hipLaunchKernelGGL((mqa_gen_fwd_kernel<128, false, true>), grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
+    launch_gen_fwd<false, true>(a, head_dim, G, stream);
     return osuf_launch_status();
   }
   const dim3 grid((nvb + 7) / 8, B, G);
@@ -1965,25 +1991,6 @@ extern "C" int osuf_mqa_fwd_rope(const void* q_raw, long ldq, const void* k, lon
   return mqa_fwd_impl(q_raw, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, H, N, head_dim, scale, true, stream, zero_dq, &r);
 }
 
-// Attend(q, k, v, attn_mask) (attention.py:77-99): the forward with an additive bf16 score bias, element strides over (b, h, q, key) with 0
-// for broadcast dimensions.  Inference path of the stand-alone Attend module; every head dim (64 included) runs the generic kernel.
-extern "C" int osuf_mqa_fwd_masked(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
-                                   float* lse2, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k, int B, int H, int N,
-                                   int head_dim, float scale, hipStream_t stream) {
-  AttnArgs a;
-  const int rc = fill_fwd_args(a, q, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, B, H, N, head_dim, scale);
-  if (rc) return rc;
-  if (!mask || scale == 0.f) return OSUF_EINVAL;
-  a.mask = (const bf16_t*)mask; a.mask_b = mask_b; a.mask_h = mask_h; a.mask_q = mask_q; a.mask_k = mask_k;
-  const int nvb = ((N + 31) / 32) * H;
-  const dim3 grid((nvb + 3) / 4, B);
-  const int dp = head_dim == D ? 64 : gen_dp(head_dim);
-  if (dp == 32) hipLaunchKernelGGL((mqa_gen_fwd_kernel<32, true>), grid, dim3(256), 2 * 64 * 64, stream, a, head_dim);
-  else if (dp == 64) hipLaunchKernelGGL((mqa_gen_fwd_kernel<64, true>), grid, dim3(256), 2 * 64 * 128, stream, a, head_dim);
-  else hipLaunchKernelGGL((mqa_gen_fwd_kernel<128, true>), grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
-  return osuf_launch_status();
-}
-
 static int fill_bwd_args(AttnArgs& a, const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
                          const float* lse2, const float* delta, int B, int H, int N, int head_dim, float scale) {
   if (head_dim != D && !gen_dp(head_dim)) return OSUF_EUNSUPPORTED;
@@ -1996,42 +2003,8 @@ static int fill_bwd_args(AttnArgs& a, const void* q, long ldq, const void* k, lo
   return OSUF_OK;
 }
 
-// The backward of osuf_mqa_fwd_masked (Attend with attn_mask): one K/V head, gradients of the ROTATED q / k (x scale) and of v, every head dim
-// (64 included) on the generic kernel pair with the bias restarting S.  dbias (may be NULL): dense fp32 [B][H][N][N], dL/d(bias).
-extern "C" int osuf_mqa_bwd_masked(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
-                                   const float* lse2, const float* delta, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k,
-                                   void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H, int N, int head_dim, float scale,
-                                   int out_dtype, float* dbias, hipStream_t stream) {
-  AttnArgs a;
-  int rc = fill_bwd_args(a, q, ldq, k, ldk, v, ldv, dout, lddo, lse2, delta, B, H, N, head_dim, scale);
-  if (rc) return rc;
-  if (!mask || !lse2 || !delta || scale == 0.f || lddq % 8 || lddk % 8 || !al16(dq) || !al16(dk) || !al16(dv) ||
-      (out_dtype != OSUF_DT_F32 && out_dtype != OSUF_DT_BF16) || (dbias && !al16(dbias)))
-    return OSUF_EINVAL;
-  a.mask = (const bf16_t*)mask; a.mask_b = mask_b; a.mask_h = mask_h; a.mask_q = mask_q; a.mask_k = mask_k;
-  a.dq = dq; a.lddq = lddq; a.dk = dk; a.dv = dv; a.lddk = lddk; a.g_bf16 = out_dtype == OSUF_DT_BF16;
-  const int nvb = ((N + 31) / 32) * H;
-  const dim3 grid((nvb + 3) / 4, B), ggrid(((N + 127) / 128) * B);
-  const int dp = head_dim == D ? 64 : gen_dp(head_dim);
-  if (dp == 32) {
-    hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<32, true>), grid, dim3(256), 2 * 64 * 64, stream, a, head_dim);
-    hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<32, true>), ggrid, dim3(256), 2 * 32 * 64 + 256, stream, a, head_dim, dbias);
-  } else if (dp == 64) {
-    hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<64, true>), grid, dim3(256), 2 * 64 * 128, stream, a, head_dim);
-    hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<64, true>), ggrid, dim3(256), 2 * 32 * 128 + 256, stream, a, head_dim, dbias);
-  } else {
-    hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<128, true>), grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
-    hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<128, true>), ggrid, dim3(256), 2 * 32 * 256 + 256, stream, a, head_dim, dbias);
-  }
-  return osuf_launch_status();
-}
-
-// Cross-attention (attention.py:94-99 with k / v of their own length): Nq query rows and Nk key rows per batch element, one K/V head, mask
-// (may be NULL) as osuf_mqa_fwd_masked over (batch, head, query, key).  Every head dim (64 included) runs the generic kernels.
-template <int DP, bool MASKED> static void launch_xattn_fwd(const AttnArgs& a, int head_dim, hipStream_t stream) {
-  const int nvb = ((a.N + 31) / 32) * a.H;
-  hipLaunchKernelGGL((mqa_gen_fwd_kernel<DP, MASKED>), dim3((nvb + 3) / 4, a.B), dim3(256), 2 * 64 * 2 * DP, stream, a, head_dim);
-}
+// Attend (attention.py:77-99): Nq query rows and Nk key rows per batch element, one K/V head, an additive bf16 score bias (mask, may be NULL)
+// with element strides over (batch, head, query, key), 0 for broadcast dimensions.  Every head dim (64 included) runs the generic kernels.
 extern "C" int osuf_xattn_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
                               float* lse2, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k, int B, int H, int Nq, int Nk,
                               int head_dim, float scale, hipStream_t stream) {
@@ -2041,26 +2014,20 @@ extern "C" int osuf_xattn_fwd(const void* q, long ldq, const void* k, long ldk, 
   if (Nk <= 0 || !lse2 || scale == 0.f) return OSUF_EINVAL;
   a.Nk = Nk;
   a.mask = (const bf16_t*)mask; a.mask_b = mask_b; a.mask_h = mask_h; a.mask_q = mask_q; a.mask_k = mask_k;
-  const int dp = head_dim == D ? 64 : gen_dp(head_dim);
-  if (mask) {
-    if (dp == 32) launch_xattn_fwd<32, true>(a, head_dim, stream);
-    else if (dp == 64) launch_xattn_fwd<64, true>(a, head_dim, stream);
-    else launch_xattn_fwd<128, true>(a, head_dim, stream);
-  } else {
-    if (dp == 32) launch_xattn_fwd<32, false>(a, head_dim, stream);
-    else if (dp == 64) launch_xattn_fwd<64, false>(a, head_dim, stream);
-    else launch_xattn_fwd<128, false>(a, head_dim, stream);
-  }
+  if (mask) launch_gen_fwd<true, false>(a, head_dim, 1, stream);
+  else launch_gen_fwd<false, false>(a, head_dim, 1, stream);
   return osuf_launch_status();
 }
-
-// The backward of osuf_xattn_fwd: lse2 / delta [B][H][Nq] (osuf_attn_delta with N = Nq), dq rows [B*Nq], dk / dv rows [B*Nk] (summed over
-// the H query heads), dbias (may be NULL; needs mask) dense fp32 [B][H][Nq][Nk].
-template <int DP, bool MASKED> static void launch_xattn_bwd(const AttnArgs& a, int head_dim, float* dbias, hipStream_t stream) {
-  const int nvb = ((a.N + 31) / 32) * a.H;
-  hipLaunchKernelGGL((mqa_gen_bwd_dq_kernel<DP, MASKED>), dim3((nvb + 3) / 4, a.B), dim3(256), 2 * 64 * 2 * DP, stream, a, head_dim);
-  hipLaunchKernelGGL((mqa_gen_bwd_dkv_kernel<DP, MASKED>), dim3(((a.Nk + 127) / 128) * a.B), dim3(256), 2 * 32 * 2 * DP + 256, stream, a, head_dim, dbias);
+// Masked self-attention: osuf_xattn_fwd with Nk = N and a mask that must be there.
+extern "C" int osuf_mqa_fwd_masked(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, int o_dtype,
+                                   float* lse2, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k, int B, int H, int N,
+                                   int head_dim, float scale, hipStream_t stream) {
+  if (!mask) return OSUF_EINVAL;
+  return osuf_xattn_fwd(q, ldq, k, ldk, v, ldv, o, ldo, o_dtype, lse2, mask, mask_b, mask_h, mask_q, mask_k, B, H, N, N, head_dim, scale, stream);
 }
+
+// The backward of osuf_xattn_fwd: gradients of the ROTATED q / k (x scale) and of v; lse2 / delta [B][H][Nq] (osuf_attn_delta with N = Nq),
+// dq rows [B*Nq], dk / dv rows [B*Nk] (summed over the H query heads), dbias (may be NULL; needs mask) dense fp32 [B][H][Nq][Nk], dL/d(bias).
 extern "C" int osuf_xattn_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
                               const float* lse2, const float* delta, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k,
                               void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H, int Nq, int Nk, int head_dim, float scale,
@@ -2074,17 +2041,23 @@ extern "C" int osuf_xattn_bwd(const void* q, long ldq, const void* k, long ldk, 
   a.Nk = Nk;
   a.mask = (const bf16_t*)mask; a.mask_b = mask_b; a.mask_h = mask_h; a.mask_q = mask_q; a.mask_k = mask_k;
   a.dq = dq; a.lddq = lddq; a.dk = dk; a.dv = dv; a.lddk = lddk; a.g_bf16 = out_dtype == OSUF_DT_BF16;
-  const int dp = head_dim == D ? 64 : gen_dp(head_dim);
   if (mask) {
-    if (dp == 32) launch_xattn_bwd<32, true>(a, head_dim, dbias, stream);
-    else if (dp == 64) launch_xattn_bwd<64, true>(a, head_dim, dbias, stream);
-    else launch_xattn_bwd<128, true>(a, head_dim, dbias, stream);
+    launch_gen_bwd_dq<true>(a, head_dim, stream);
+    launch_gen_bwd_dkv<true>(a, head_dim, dbias, stream);
   } else {
-    if (dp == 32) launch_xattn_bwd<32, false>(a, head_dim, nullptr, stream);
-    else if (dp == 64) launch_xattn_bwd<64, false>(a, head_dim, nullptr, stream);
-    else launch_xattn_bwd<128, false>(a, head_dim, nullptr, stream);
+    launch_gen_bwd_dq<false>(a, head_dim, stream);
+    launch_gen_bwd_dkv<false>(a, head_dim, nullptr, stream);
   }
   return osuf_launch_status();
+}
+// The backward of osuf_mqa_fwd_masked: osuf_xattn_bwd with Nk = N and a mask that must be there.
+extern "C" int osuf_mqa_bwd_masked(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* dout, long lddo,
+                                   const float* lse2, const float* delta, const void* mask, long mask_b, long mask_h, long mask_q, long mask_k,
+                                   void* dq, long lddq, void* dk, void* dv, long lddk, int B, int H, int N, int head_dim, float scale,
+                                   int out_dtype, float* dbias, hipStream_t stream) {
+  if (!mask) return OSUF_EINVAL;
+  return osuf_xattn_bwd(q, ldq, k, ldk, v, ldv, dout, lddo, lse2, delta, mask, mask_b, mask_h, mask_q, mask_k, dq, lddq, dk, dv, lddk, B, H, N, N,
+                        head_dim, scale, out_dtype, dbias, stream);
 }
 
 // delta[b][h][n] = sum_d dO * O   (o: bf16 or f32 storage of the forward output)
@@ -2122,9 +2095,7 @@ extern "C" int osuf_mqa_bwd_dq(const void* q, long ldq, const void* k, long ldk,
   const int nvb = ((N + 31) / 32) * H;
   if (head_dim != D) {                                            // generic head dims: gradient of the rotated q; the caller un-rotates (osuf_rope_bwd)
     if (rope_cos) return OSUF_EUNSUPPORTED;
-    const dim3 grid((nvb + 3) / 4, B);
-    if (gen_dp(head_dim) == 32) hipLaunchKernelGGL(mqa_gen_bwd_dq_kernel<32>, grid, dim3(256), 2 * 64 * 64, stream, a, head_dim);
-    else hipLaunchKernelGGL(mqa_gen_bwd_dq_kernel<128>, grid, dim3(256), 2 * 64 * 256, stream, a, head_dim);
+    launch_gen_bwd_dq<false>(a, head_dim, stream);
     return osuf_launch_status();
   }
   // the pipelined kernel (2 waves/SIMD, 256 VGPRs) wins once the key loop is long: +4.5 % at N=4096, +3 % at 2048, -2 % at <= 1024
@@ -2176,9 +2147,7 @@ extern "C" int osuf_mqa_bwd_dkv(const void* q, long ldq, const void* k, long ldk
   a.dk = dk; a.dv = dv; a.lddk = lddk; a.g_bf16 = out_dtype == OSUF_DT_BF16; a.rcos = rope_cos; a.rsin = rope_sin;
   if (head_dim != D) {                                            // generic head dims: gradients of the rotated k and of v, unsplit
     if (rope_cos) return OSUF_EUNSUPPORTED;
-    const dim3 ggrid(((N + 127) / 128) * B);
-    if (gen_dp(head_dim) == 32) hipLaunchKernelGGL(mqa_gen_bwd_dkv_kernel<32>, ggrid, dim3(256), 2 * 32 * 64 + 256, stream, a, head_dim, (float*)nullptr);
-    else hipLaunchKernelGGL(mqa_gen_bwd_dkv_kernel<128>, ggrid, dim3(256), 2 * 32 * 256 + 256, stream, a, head_dim, (float*)nullptr);
+    launch_gen_bwd_dkv<false>(a, head_dim, nullptr, stream);
     return osuf_launch_status();
   }
   const int b8 = (B + 7) / 8 * 8;

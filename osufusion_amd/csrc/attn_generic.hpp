@@ -71,6 +71,9 @@ __device__ __forceinline__ void gen_store_row(void* base, long elem_off, int is_
     }
 }
 
+// row of a 32x32 MFMA accumulator that register r of a lane in half lh (= lane >> 5) holds
+__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
 // ---- forward (attention.py:94-99 under unet.py:125-141): 4 waves = 4 (head, 32-query block) pairs share each 64-key K / V tile.
 // MASKED: Attend's attn_mask (attention.py:77-99) -- the reference casts it to bf16 and hands it to SDPA as an ADDITIVE bias of the
 // scaled scores (a bool mask therefore adds 1.0 / 0.0; that is the reference's behaviour and is kept), broadcast over (B, H, N, N).
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(256) void mqa_gen_fwd_kernel(AttnArgs a, int hd) {
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int key = j * 64 + kt * 32 + acc_row(r, lh);
           s[kt][r] = bf16_to_f32(mrow[(long)(key < a.Nk ? key : a.Nk - 1) * a.mask_k]) * inv_scale;
         }
     } else {
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(256) void mqa_gen_fwd_kernel(AttnArgs a, int hd) {
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int key = j * 64 + kt * 32 + acc_row(r, lh);
         if (key >= a.Nk) s[kt][r] = -INFINITY;
         mx = fmaxf(mx, s[kt][r]);
       }
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int key = j * 64 + kt * 32 + acc_row(r, lh);
           s[kt][r] = bf16_to_f32(mrow[(long)(key < a.Nk ? key : a.Nk - 1) * a.mask_k]) * inv_scale;
         }
     } else {
@@ -243,7 +246,7 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
       for (int r = 0; r < 16; ++r) {
         float p = fast_exp2(fmaf(s[kt][r], c, -L2));                  // keys past Nk: zero K rows -> their dS meets zero K rows below
         if constexpr (MASKED) {                                        // (a clamped bias could make p large there: drop it outright)
-          const int key = j * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int key = j * 64 + kt * 32 + acc_row(r, lh);
           p = key < a.Nk ? p : 0.f;
         }
         s[kt][r] = p * (dp[kt][r] - dl);
@@ -301,7 +304,7 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd
         const float inv_scale = 1.f / a.scale;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int qr = pb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int qr = pb * 32 + acc_row(r, lh);
           s[r] = bf16_to_f32(mcol[(long)(qr < a.N ? qr : a.N - 1) * a.mask_q]) * inv_scale;
         }
       } else {
@@ -318,7 +321,7 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd
       f32x16 ds;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int qi = (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int qi = acc_row(r, lh);
         const float p = fast_exp2(fmaf(s[r], c, -ls[qi]));
         s[r] = p;
         ds[r] = p * (dp[r] - ls[32 + qi]);
@@ -328,7 +331,7 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dkv_kernel(AttnArgs a, int hd
           float* drow = dbias + (((long)b * a.H + h) * a.N + pb * 32) * a.Nk + key;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int qi = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int qi = acc_row(r, lh);
             if (pb * 32 + qi < a.N) drow[(long)qi * a.Nk] = ds[r];
           }
         }

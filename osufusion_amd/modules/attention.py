@@ -37,7 +37,8 @@ class RotaryPositionEmbedding(nn.Module):
 
 class Attend(nn.Module):
     """attention.py:61-101: q, k, v -> bf16, softmax(q k^T / sqrt(d) + attn_mask.to(bf16)) v, back to the input dtype.  k / v carry 1 or
-    H heads and may be of another length than q (cross-attention: osufusion_amd/cross_attend.py).  Differentiable in q, k, v and a
+    H heads and may be of another length than q.  A call with a mask or with another key count runs the generic kernels
+    (osufusion_amd/cross_attend.py), the unmasked same-length call the tuned ones (osufusion_amd/attend.py).  Differentiable in q, k, v and a
     floating-point attn_mask (a k / v with one head gets the gradient summed over the query heads).  Rows whose every key is masked with
     -inf are NaN, as in SDPA."""
 

@@ -1,6 +1,7 @@
 """Training through the stand-alone Attend and RotaryPositionEmbedding modules (osufusion_amd/attend.py): their gradients against fp64
 autograd of the reference's formulas (attention.py:15-101) on the bf16-cast inputs, the bias gradient of a floating-point mask, K/V heads
-given repeated, a toy block end to end, and the masked backward under poisoned, canary-guarded memory."""
+given repeated, and a toy block end to end.  (The masked calls run cross_attend.py's generic path; their poisoned-memory cases are in
+tests/test_cross_attend_gpu.py.)"""
 import itertools
 
 import pytest
@@ -201,52 +202,3 @@ def test_toy_block_end_to_end():
         e = rell2(g, w)
         report(f"toy_block/{name}", rel_l2=e)
         assert e < 1e-2, (name, e)
-
-
-# ----------------------------------------------------------------------------------------------------------------------------------------
-# poisoned memory (tests/memguard.py): the masked kernels have no atomics, so every output is bit-identical across the three fills
-# ----------------------------------------------------------------------------------------------------------------------------------------
-def masked_pair(N, H, D, bias_shape, want_dbias):
-    def run(c):
-        from osufusion_amd import attend as At
-        from tests.test_poisoned_memory import rnd
-        scale = D ** -0.5
-        qkv = c.inp(rnd("qkv", (B, N, (H + 2) * D)), torch.bfloat16)
-        m = rnd("m", bias_shape)
-        m[..., N // 4:N // 4 + 7] = float("-inf")
-        mask4 = c.inp(m, torch.bfloat16).expand(B, H, N, N)
-        do = c.inp(rnd("do", (B, N, H * D)), torch.bfloat16)
-        o, lse = At.mqa_fwd_masked(qkv, mask4, B, N, H, D, torch.bfloat16, scale)
-        dqkv, dbias = At.mqa_bwd_masked(qkv, mask4, o, do, lse, B, N, H, D, scale, want_dbias)
-        c.eq("o", o), c.eq("lse", lse), c.eq("dq", dqkv[..., :H * D]), c.eq("dk", dqkv[..., H * D:(H + 1) * D]), c.eq("dv", dqkv[..., (H + 1) * D:])
-        if want_dbias:
-            c.eq("dbias", dbias)
-        else:
-            assert dbias is None
-        q = qkv[..., :H * D].view(B, N, H, D).permute(0, 2, 1, 3)
-        k, v = (qkv[..., s * D:(s + 1) * D].view(B, N, 1, D).permute(0, 2, 1, 3) for s in (H, H + 1))
-        go = do.view(B, N, H, D).permute(0, 2, 1, 3).float()
-        _, rq, rk, rv, rm = ref_grads(q, k, v, mask4, go)                  # rm: the gradient of the expanded (B, H, N, N) bias
-        rows = lambda t: t.permute(0, 2, 1, 3).reshape(B, N, -1).float()
-        c.close("dq", dqkv[..., :H * D], rows(rq), RL2, rell2)
-        c.close("dk", dqkv[..., H * D:(H + 1) * D], rows(rk), RL2, rell2)
-        c.close("dv", dqkv[..., (H + 1) * D:], rows(rv), RL2, rell2)
-        if want_dbias:
-            c.close("dbias", dbias, rm.float(), RL2, rell2)
-    return run
-
-
-# allocating function of osufusion_amd/attend.py -> its cases (tests/test_attend_cases.py requires one for every torch.empty site there)
-POISON_CASES = {
-    "mqa_fwd_masked": [("N200_D64_broadcast", masked_pair(200, 3, 64, (1, 1, 200, 200), False))],
-    "mqa_bwd_masked": [("N200_D64_broadcast", masked_pair(200, 3, 64, (1, 1, 200, 200), False)),
-                       ("N200_D64_dbias", masked_pair(200, 3, 64, (B, 3, 200, 200), True)),
-                       ("N136_D32_dbias", masked_pair(136, 2, 32, (B, 2, 136, 136), True)),
-                       ("N100_D128_dbias", masked_pair(100, 1, 128, (B, 1, 100, 100), True))],
-}
-
-
-@pytest.mark.parametrize("fn,case", [(k, c) for k, v in POISON_CASES.items() for c, _ in v])
-def test_masked_attention_on_poisoned_memory(fn, case):
-    from tests.test_poisoned_memory import run_case
-    run_case(dict(POISON_CASES[fn])[case])

@@ -4,7 +4,8 @@ The yardstick is tests/test_attend_autograd_gpu.py's, generalised to (Nq, Nk): f
 the bf16-cast inputs (the reference Attend's arithmetic, attention.py:84-101), with that file's bounds: output rel-L2 < 6e-3, gradients
 rel-L2 < 1e-2 and rel-max < 3e-2, everything finite.  Shapes: Nk = 77 (one full 64-key tile + a ragged 13-key one; one dK/dV workgroup with
 idle waves), Nk = 130 (a second dK/dV workgroup with 2 live keys), Nq = 33 (a ragged second 32-query block), Nk = 5 (less than a tile),
-Nk >> Nq and Nk << Nq (a swapped N / Nk in a batch stride or an index shows)."""
+Nk >> Nq and Nk << Nq (a swapped N / Nk in a batch stride or an index shows).  Masked self-attention rides the same path: its C entry points
+against osuf_xattn_*, its dispatch from attend(), and its poisoned-memory cases on column views of one q|k|v image are here too."""
 import itertools
 
 import pytest
@@ -130,7 +131,8 @@ def test_bool_and_integer_masks_get_no_gradient():
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------------
-# the generalisation changed nothing: Nk == Nq through the new entry points = the self-attention entry points, bit for bit
+# osuf_mqa_fwd_masked / osuf_mqa_bwd_masked forward to osuf_xattn_* with Nk = N: called directly (no Python wrapper is left for them), they
+# equal the generic path bit for bit
 # ----------------------------------------------------------------------------------------------------------------------------------------
 def _image(N, H, D):
     qkv = torch.randn(B, N, (H + 2) * D, device=DEV).to(torch.bfloat16)
@@ -139,22 +141,65 @@ def _image(N, H, D):
 
 @pytest.mark.parametrize("N,H,D", [(200, 3, 64), (136, 2, 32), (200, 1, 128), (136, 3, 16)])
 def test_same_length_equals_masked_self_attention(N, H, D):
-    from osufusion_amd import attend as At
     from osufusion_amd import cross_attend as Xa
+    from osufusion_amd import ops
     scale = D ** -0.5
     qkv, q, k, v = _image(N, H, D)
     m = torch.randn(B, H, N, N, device=DEV)
     m[..., N // 4:N // 4 + 7] = float("-inf")
     m4 = m.to(torch.bfloat16)
     do = torch.randn(B, N, H * D, device=DEV).to(torch.bfloat16)
-    o, lse = At.mqa_fwd_masked(qkv, m4, B, N, H, D, torch.bfloat16, scale)
-    dqkv, dbias = At.mqa_bwd_masked(qkv, m4, o, do, lse, B, N, H, D, scale, True)
+    # the self-attention side: the two C symbols on the [B][N][(H+2)D] image, outputs allocated here
+    W = (H + 2) * D
+    base, mstr, st = qkv.data_ptr(), m4.stride(), ops._stream()
+    o = torch.empty(B, N, H * D, dtype=torch.bfloat16, device=DEV)
+    lse, delta = (torch.empty(B, H, N, dtype=torch.float32, device=DEV) for _ in range(2))
+    dqkv = torch.empty(B, N, W, dtype=torch.float32, device=DEV)
+    dbias = torch.empty(B, H, N, N, dtype=torch.float32, device=DEV)
+    gb = dqkv.data_ptr()
+    ops.call("osuf_mqa_fwd_masked", base, W, base + 2 * H * D, W, base + 2 * (H + 1) * D, W, o.data_ptr(), H * D, ops.BF16, lse.data_ptr(),
+             m4.data_ptr(), *mstr, B, H, N, D, scale, st)
+    ops.call("osuf_attn_delta", do.data_ptr(), H * D, o.data_ptr(), H * D, ops.BF16, delta.data_ptr(), B, H, N, D, st)
+    ops.call("osuf_mqa_bwd_masked", base, W, base + 2 * H * D, W, base + 2 * (H + 1) * D, W, do.data_ptr(), H * D, lse.data_ptr(), delta.data_ptr(),
+             m4.data_ptr(), *mstr, gb, W, gb + 4 * H * D, gb + 4 * (H + 1) * D, W, B, H, N, D, scale, ops.F32, dbias.data_ptr(), st)
     xo, xlse = Xa.xattn_fwd(q, k, v, m4, B, N, N, H, D, torch.bfloat16, scale)
     assert torch.equal(xo, o) and torch.equal(xlse, lse)
     xdq, xdk, xdv, xdb = Xa.xattn_bwd(q, k, v, m4, xo, do, xlse, B, N, N, H, D, scale, True)
     assert torch.equal(xdq, dqkv[..., :H * D]) and torch.equal(xdk, dqkv[..., H * D:(H + 1) * D]) and torch.equal(xdv, dqkv[..., (H + 1) * D:])
     assert torch.equal(xdb, dbias)
     assert all(torch.isfinite(t).all() for t in (xo, xlse, xdq, xdk, xdv, xdb))
+
+
+def test_null_lse2_is_an_invalid_argument():
+    """lse2 = NULL: the kernel writes it unconditionally, so both forward entry points refuse the call before anything is launched."""
+    from osufusion_amd import ops
+    N, H, D = 32, 1, 32
+    qkv, q, k, v = _image(N, H, D)
+    qkv, q, k, v = qkv[:1], q[:1], k[:1], v[:1]
+    W = (H + 2) * D
+    m4 = torch.zeros(1, H, N, N, dtype=torch.bfloat16, device=DEV)
+    o = torch.empty(1, N, H * D, dtype=torch.bfloat16, device=DEV)
+    head = (q.data_ptr(), W, k.data_ptr(), W, v.data_ptr(), W, o.data_ptr(), H * D, ops.BF16, None, m4.data_ptr(), *m4.stride(), 1, H)
+    for name, lengths in (("osuf_mqa_fwd_masked", (N,)), ("osuf_xattn_fwd", (N, N))):
+        with pytest.raises(RuntimeError, match=name + " failed: invalid argument"):
+            ops.call(name, *head, *lengths, D, D ** -0.5, ops._stream())
+
+
+@pytest.mark.parametrize("grad_mask", [False, True])
+def test_masked_self_attention_dispatches_to_the_generic_path(grad_mask):
+    """attend() with a mask at Nk == Nq: CrossAttendFn under grad mode, and the very same launches under no_grad."""
+    from osufusion_amd import attend as At
+    from osufusion_amd.cross_attend import CrossAttendFn
+    N, H, D = 64, 2, 32
+    q, k, v = leaves(H, 1, N, N, D)
+    if grad_mask:
+        q, k, v = (t.detach() for t in (q, k, v))                              # the mask alone asks for a gradient
+    mask = make_mask("causal", H, N, N).requires_grad_(grad_mask)
+    out = At.attend(q, k, v, mask)
+    assert out.grad_fn is not None and type(out.grad_fn).__name__ == CrossAttendFn.__name__ + "Backward"
+    with torch.no_grad():
+        bare = At.attend(q, k, v, mask)
+    assert bare.grad_fn is None and torch.equal(out.detach(), bare)
 
 
 @pytest.mark.parametrize("N", [200, 136])
@@ -172,13 +217,19 @@ def test_same_length_unmasked_equals_generic_forward(N):
 # ----------------------------------------------------------------------------------------------------------------------------------------
 # poisoned memory (tests/memguard.py): the kernels have no atomics, so every output is bit-identical across the three fills
 # ----------------------------------------------------------------------------------------------------------------------------------------
-def cross_pair(Nq, Nk, H, D, bias_shape, want_dbias):
+def cross_pair(Nq, Nk, H, D, bias_shape, want_dbias, image=False):
+    """image: q, k, v are column views of one guarded [B][N][(H+2)D] q|k|v image (Nk == Nq; the row stride is not the row width)."""
     def run(c):
         from osufusion_amd import cross_attend as Xa
         scale = D ** -0.5
-        q = c.inp(rnd("q", (B, Nq, H * D)), torch.bfloat16)
-        k = c.inp(rnd("k", (B, Nk, D)), torch.bfloat16)
-        v = c.inp(rnd("v", (B, Nk, D)), torch.bfloat16)
+        if image:
+            assert Nk == Nq
+            qkv = c.inp(rnd("qkv", (B, Nq, (H + 2) * D)), torch.bfloat16)
+            q, k, v = qkv[..., :H * D], qkv[..., H * D:(H + 1) * D], qkv[..., (H + 1) * D:]
+        else:
+            q = c.inp(rnd("q", (B, Nq, H * D)), torch.bfloat16)
+            k = c.inp(rnd("k", (B, Nk, D)), torch.bfloat16)
+            v = c.inp(rnd("v", (B, Nk, D)), torch.bfloat16)
         do = c.inp(rnd("do", (B, Nq, H * D)), torch.bfloat16)
         mask4 = None
         if bias_shape is not None:
@@ -205,12 +256,34 @@ def cross_pair(Nq, Nk, H, D, bias_shape, want_dbias):
 
 
 # allocating function of osufusion_amd/cross_attend.py -> its cases (tests/test_cross_attend_cpu.py requires one for every torch.empty site)
+def masked_pair(N, H, D, bias_shape, want_dbias):
+    """Masked self-attention as Attend's callers lay it out: one q|k|v row image, Nk = Nq = N."""
+    return cross_pair(N, N, H, D, bias_shape, want_dbias, image=True)
+
+
+def attention_masked(c):
+    """A key-padding bias (B, 1, 1, N) of 0 / -1e4 on the q|k|v image: the forward alone."""
+    from osufusion_amd import cross_attend as Xa
+    N, H, D = 200, 2, 64
+    qkv = c.inp(rnd("qkv", (B, N, (H + 2) * D)), torch.bfloat16)
+    m = (rnd("m", (B, 1, 1, N)) > -1.0).to(torch.bfloat16)
+    mask4 = c.inp(torch.where(m > 0, 0.0, -1e4).to(torch.bfloat16)).expand(B, H, N, N)
+    o, lse = Xa.xattn_fwd(qkv[..., :H * D], qkv[..., H * D:(H + 1) * D], qkv[..., (H + 1) * D:], mask4, B, N, N, H, D, torch.bfloat16, D ** -0.5)
+    c.eq("o", o), c.eq("lse", lse)
+
+
 POISON_CASES = {
     "xattn_fwd": [("Nq200_Nk77_D64_broadcast", cross_pair(200, 77, 3, 64, (1, 1, 200, 77), False)),
-                  ("Nq64_Nk200_D128_unmasked", cross_pair(64, 200, 2, 128, None, False))],
+                  ("Nq64_Nk200_D128_unmasked", cross_pair(64, 200, 2, 128, None, False)),
+                  ("image_N200_D64_broadcast", masked_pair(200, 3, 64, (1, 1, 200, 200), False)),
+                  ("image_N200_D64_key_padding", attention_masked)],
     "xattn_bwd": [("Nq200_Nk77_D64_broadcast", cross_pair(200, 77, 3, 64, (1, 1, 200, 77), False)),
                   ("Nq33_Nk130_D32_dbias", cross_pair(33, 130, 2, 32, (B, 2, 33, 130), True)),
-                  ("Nq64_Nk200_D128_unmasked", cross_pair(64, 200, 2, 128, None, False))],
+                  ("Nq64_Nk200_D128_unmasked", cross_pair(64, 200, 2, 128, None, False)),
+                  ("image_N200_D64_broadcast", masked_pair(200, 3, 64, (1, 1, 200, 200), False)),
+                  ("image_N200_D64_dbias", masked_pair(200, 3, 64, (B, 3, 200, 200), True)),
+                  ("image_N136_D32_dbias", masked_pair(136, 2, 32, (B, 2, 136, 136), True)),
+                  ("image_N100_D128_dbias", masked_pair(100, 1, 128, (B, 1, 100, 100), True))],
 }
 
 

@@ -462,15 +462,6 @@ def attention(B, N, H, G=1, D=64, variant=None, qsplit=0, qs=False, rope=False, 
     return run
 
 
-def attention_masked(c):
-    from osufusion_amd import ops
-    B, N, H, D = 2, 200, 2, 64
-    qkv = c.inp(rnd("qkv", (B, N, (H + 2) * D)), torch.bfloat16)
-    m = (rnd("m", (B, 1, 1, N)) > -1.0).to(torch.bfloat16)
-    mask4 = c.inp(torch.where(m > 0, 0.0, -1e4).to(torch.bfloat16)).expand(B, H, N, N)
-    c.eq("o", ops.mqa_fwd_masked(qkv, mask4, B, N, H, D, torch.bfloat16, D ** -0.5))
-
-
 def rope_pair(c):
     from osufusion_amd import functional as Fn
     from osufusion_amd import ops
@@ -658,7 +649,6 @@ CASES = {
     "gca_bwd_apply": [("gc_f32", module_case("gc", F32, 5e-5)), ("gc_bf16", module_case("gc", BF, 2e-2))],
     "rope_cast": [("f32_ragged", rope_pair), ("qs", attention(2, 200, 3, qs=True))],
     "rope_bwd": [("f32_ragged", rope_pair), ("head_dim_32", attention(2, 136, 2, D=32, rope=True))],
-    "mqa_fwd_masked": [("N200", attention_masked)],
 }
 
 

@@ -403,18 +403,20 @@ def test_attend_with_mask_matches_reference_semantics(D, H, G):
 @pytest.mark.parametrize("D", [16, 32, 64, 128])
 @pytest.mark.parametrize("N", [64, 200, 1000])
 def test_masked_forward_op_random_bias(D, N):
-    """osuf_mqa_fwd_masked on its own: a dense random bf16 bias with a band of -inf key columns, every key tile (the second 32-key half of
+    """The masked forward on its own (osuf_xattn_fwd with Nk = N, on the column views of the q|k|v image): a dense random bf16 bias with a band of -inf key columns, every key tile (the second 32-key half of
     a 64-key tile included -- a first version of the kernel got exactly that half wrong) and a ragged last tile."""
+    from osufusion_amd import cross_attend as Xa
     torch.manual_seed(D + N)
     B, H = 2, 3
     qkv = torch.randn(B, N, (H + 2) * D, device=DEV).to(torch.bfloat16)
+    qc, kc, vc = qkv[..., :H * D], qkv[..., H * D:(H + 1) * D], qkv[..., (H + 1) * D:]
     x = qkv.float()
     q = x[..., :H * D].view(B, N, H, D).permute(0, 2, 1, 3)
     k, v = x[..., H * D:(H + 1) * D][:, None], x[..., (H + 1) * D:][:, None]
     bias = torch.randn(B, H, N, N, device=DEV).to(torch.bfloat16)
     bias[:, :, :, N // 2:N // 2 + 7] = float("-inf")
     want = (((q @ k.transpose(-1, -2)) * D ** -0.5 + bias.float()).softmax(-1) @ v).permute(0, 2, 1, 3).reshape(B, N, H * D)
-    got = ops.mqa_fwd_masked(qkv, bias, B, N, H, D, torch.bfloat16, D ** -0.5)
+    got = Xa.xattn_fwd(qc, kc, vc, bias, B, N, N, H, D, torch.bfloat16, D ** -0.5)[0]
     e = rell2(got, want)
     report(f"attend_mask/op/D{D}/N{N}", rel_l2=e)
     assert e < 4e-3
@@ -422,7 +424,7 @@ def test_masked_forward_op_random_bias(D, N):
     hot = torch.full((B, H, N, N), -1e4, device=DEV, dtype=torch.bfloat16)
     key = min(N - 1, 33)
     hot[..., key] = 0
-    got = ops.mqa_fwd_masked(qkv, hot, B, N, H, D, torch.float32, D ** -0.5)
+    got = Xa.xattn_fwd(qc, kc, vc, hot, B, N, N, H, D, torch.float32, D ** -0.5)[0]
     assert torch.equal(got.view(B, N, H, D), v[:, 0, key][:, None, None, :].expand(B, N, H, D))
 
 

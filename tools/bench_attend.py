@@ -1,10 +1,10 @@
-"""Timing of the stand-alone Attend module, forward + backward (osufusion_amd/attend.py), against torch's own SDPA on the same GPU.
+"""Timing of the stand-alone Attend module, forward + backward (osufusion_amd/attend.py, cross_attend.py), against torch's own SDPA on the same GPU.
 
     python tools/bench_attend.py [--out profiles/attend_fwd_bwd.json] [N ...]
 
 B = 2, H = 8, D = 64, one K/V head per query head, fp32 leaves as a model would hand them over.  Rows:
   * unmasked: ops.mqa_fwd + the tuned fused backward sweep;
-  * causal (N, N) float mask, no grad on it: the generic masked kernels (osuf_mqa_fwd_masked / osuf_mqa_bwd_masked), one launch set per head;
+  * causal (N, N) float mask, no grad on it: the generic kernels (cross_attend.py: osuf_xattn_fwd / osuf_xattn_bwd with Nk = N), one launch set per head;
   * the same with the mask requiring grad (dense fp32 dbias [B][H][N][N] stored, then summed to (N, N));
   * the masked backward kernels alone with a broadcast (1, 1, N, N) and a dense (B, H, N, N) bias: how much the per-lane bias gather costs.
 A timing tool, not a gate: medians of event-timed repetitions after warm-up."""
@@ -20,7 +20,7 @@ sys.path.insert(0, str(ROOT))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from osufusion_amd import attend as At  # noqa: E402
+from osufusion_amd import cross_attend as Xa  # noqa: E402
 from osufusion_amd.modules.attention import Attend  # noqa: E402
 
 B, H, D = 2, 8, 64
@@ -86,13 +86,14 @@ def main():
             print(json.dumps(rec), flush=True)
         # the masked backward kernels alone (one launch set over all H heads, one K/V head): broadcast vs dense bias
         qkv = torch.randn(B, N, (H + 2) * D, device=DEV).to(torch.bfloat16)
+        qc, kc, vc = qkv[..., :H * D], qkv[..., H * D:(H + 1) * D], qkv[..., (H + 1) * D:]      # column views of the q|k|v image
         do = torch.randn(B, N, H * D, device=DEV).to(torch.bfloat16)
         for name, m4 in (("bwd_kernels/bias(1,1,N,N)", causal.to(torch.bfloat16).expand(B, H, N, N)),
                          ("bwd_kernels/bias(B,H,N,N)", causal.to(torch.bfloat16).expand(B, H, N, N).contiguous())):
-            o, lse = At.mqa_fwd_masked(qkv, m4, B, N, H, D, torch.bfloat16, D ** -0.5)
+            o, lse = Xa.xattn_fwd(qc, kc, vc, m4, B, N, N, H, D, torch.bfloat16, D ** -0.5)
             rec = {"N": N, "case": name, "kv_heads": 1}
-            rec["ms"] = timeit(lambda: At.mqa_bwd_masked(qkv, m4, o, do, lse, B, N, H, D, D ** -0.5, False))
-            rec["ms_with_dbias"] = timeit(lambda: At.mqa_bwd_masked(qkv, m4, o, do, lse, B, N, H, D, D ** -0.5, True))
+            rec["ms"] = timeit(lambda: Xa.xattn_bwd(qc, kc, vc, m4, o, do, lse, B, N, N, H, D, D ** -0.5, False))
+            rec["ms_with_dbias"] = timeit(lambda: Xa.xattn_bwd(qc, kc, vc, m4, o, do, lse, B, N, N, H, D, D ** -0.5, True))
             rec["tflops_alg"] = round(4.0 * B * H * N * N * D * 2.0 / (rec["ms"] / 1e3) / 1e12, 2)
             rows.append(rec)
             print(json.dumps(rec), flush=True)

@@ -86,9 +86,9 @@ def main():
             except RuntimeError as e:                          # no SDPA backend for this case on this build
                 rec["sdpa_error"] = str(e).split("\n")[0][:200]
             # the backward launch pair alone (osuf_attn_delta + dQ + dK/dV), on the rows the module would keep
-            rq, rk, rv = Xa._rows(q.detach()), Xa._rows(k.detach()), Xa._rows(v.detach())
+            rq, rk, rv = (Xa._rows(t.detach(), torch.bfloat16) for t in (q, k, v))
             o, lse = Xa.xattn_fwd(rq, rk, rv, mask, B, Nq, Nk, H, D, torch.bfloat16, D ** -0.5)
-            do = Xa._rows(go)
+            do = Xa._rows(go, torch.bfloat16)
             rec["ours_bwd_kernels_ms"] = tm(lambda: Xa.xattn_bwd(rq, rk, rv, mask, o, do, lse, B, Nq, Nk, H, D, D ** -0.5, False))
             rec["ours_fwd_tflops_alg"] = round(flops_fwd / (rec["ours_fwd_ms"] / 1e3) / 1e12, 2)
             rec["ours_bwd_kernels_tflops_alg"] = round(2.0 * flops_fwd / (rec["ours_bwd_kernels_ms"] / 1e3) / 1e12, 2)
