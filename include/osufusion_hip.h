@@ -282,6 +282,17 @@ int osuf_add2d(int dtype, const void* a, long lda, const void* b, long ldb, void
 int osuf_axpby_rows(const float* x, const float* y, const float* ca, const float* cb, float* out, int B, long per_sample, hipStream_t stream);
 int osuf_ddim_step(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, float* out,
                    int B, long per_sample, hipStream_t stream);
+/* Continuous-time Gaussian diffusion (replaces: modules/scheduler.py:11-23, 83-93, 121-123 and the ancestral step a DDPM sampler
+ * composes from them).  osuf_ct_schedule: t[B], t_next[B] or NULL, kind 0 = linear / 1 = cosine log-SNR, evaluated in fp32 in the
+ * reference's order of operations -> out[B][3] = {log_snr, alpha, sigma} without t_next, else out[B][13] = those, {log_snr, alpha,
+ * sigma} at t_next, c = -expm1(log_snr - log_snr_next), posterior_variance, posterior_log_variance, 1 / max(alpha, 1e-8),
+ * alpha_next (1 - c) / alpha, alpha_next c, and the noise gain (t_next > 0 ? exp(0.5 posterior_log_variance) : 0).
+ * osuf_ct_step: one pass over (B, per_sample) fp32 with coef = the 13-column rows: eps = nullp ? nullp + (cond - nullp) cond_scale
+ * : cond; x0 = clamp((x - sigma eps) / max(alpha, 1e-8), -1, 1); out = alpha_next (x (1 - c) / alpha + c x0) + gain * noise
+ * (noise may be NULL; a zero gain never reads into the result). */
+int osuf_ct_schedule(const float* t, const float* t_next, int kind, float* out, int B, hipStream_t stream);
+int osuf_ct_step(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* noise,
+                 float* out, int B, long per_sample, hipStream_t stream);
 int osuf_mse(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum, int B, int Dch, int L,
              hipStream_t stream);
 int osuf_sqnorm(const float* g, long n, double* out, hipStream_t stream);

@@ -68,6 +68,8 @@ SIGNATURES = {
     "osuf_add2d": [I, P, L, P, L, P, L, I, I, P],
     "osuf_axpby_rows": [P, P, P, P, P, I, L, P],
     "osuf_ddim_step": [P, P, P, F, P, P, I, L, P],
+    "osuf_ct_schedule": [P, P, I, P, I, P],
+    "osuf_ct_step": [P, P, P, F, P, P, P, I, L, P],
     "osuf_mse": [P, P, P, P, P, I, I, I, P],
     "osuf_sqnorm": [P, L, P, P],
     "osuf_adamw": [P, P, P, P, L, F, F, F, F, F, I, P, P],

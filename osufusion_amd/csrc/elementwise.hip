@@ -99,6 +99,97 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const fl
   }
 }
 
+// ---- continuous-time Gaussian diffusion (scheduler.py): log-SNR schedule and the ancestral (DDPM) step ----------------------------
+// log_snr(t) in fp32, in the reference's order of operations (scheduler.py:11-23 as torch evaluates it on fp32 tensors: t**2 = t*t,
+// x**-2 = 1/(x*x), python scalars rounded to fp32).  The network is conditioned on this fp32 value, and it is not the fp64 one: the
+// cosine schedule cancels in cos(.)^-2 - 1 and takes cos of an fp32 argument at pi/2.  No contraction: 10*(t*t) + 1e-4 stays two roundings.
+// Every intermediate is an fp32 value; the transcendental functions (ct_cos, ct_log, ...) are correctly rounded fp32 functions, the fp64
+// routine rounded once.  A 1-ulp fp32 routine agrees with another libm's in most arguments only, and one ulp of log_snr = -33.9 is a
+// relative 2e-6 of alpha; the correctly rounded result is what a careful libm returns (B values per launch: the cost is nothing).
+#define CT_FN(name, fn) __device__ inline float name(float x) { return (float)fn((double)x); }
+CT_FN(ct_cos, cos) CT_FN(ct_log, log) CT_FN(ct_exp, exp) CT_FN(ct_expm1, expm1)
+#undef CT_FN
+
+__device__ inline float ct_log_snr(float t, int kind) {
+#pragma clang fp contract(off)
+  if (kind == 0) {                                       // linear: -log(expm1(1e-4 + 10 t^2))
+    const float u = 1e-4f + 10.f * (t * t);
+    return -ct_log(ct_expm1(u));
+  }
+  const float a = (t + 0.008f) / 1.008f * 3.14159265358979323846f * 0.5f;      // cosine: -log(max(cos(.)^-2 - 1, 1e-8))
+  const float c = ct_cos(a);
+  const float r = 1.f / (c * c) - 1.f;
+  return -ct_log(fmaxf(r, 1e-8f));
+}
+
+__device__ inline float ct_sigmoid(float x) { return 1.f / (1.f + ct_exp(-x)); }
+
+// One thread per sample.  Row of `cols` floats (OSUF_CT_COLS_T = 3 without t_next, OSUF_CT_COLS = 13 with it):
+//   0 log_snr  1 alpha  2 sigma | 3 log_snr_next  4 alpha_next  5 sigma_next  6 c = -expm1(log_snr - log_snr_next)
+//   7 posterior_variance = sigma_next^2 c  8 posterior_log_variance = log(max(var, 1e-20))            (scheduler.py:83-93)
+//   9 1 / max(alpha, 1e-8)  10 alpha_next (1 - c) / alpha  11 alpha_next c  12 noise gain = t_next > 0 ? exp(0.5 log_var) : 0
+__global__ __launch_bounds__(256) void ct_schedule_kernel(const float* t, const float* t_next, int kind, float* out, int B) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float ls = ct_log_snr(t[b], kind);
+  const float alpha = sqrtf(ct_sigmoid(ls)), sigma = sqrtf(ct_sigmoid(-ls));
+  float* o = out + (long)b * (t_next ? 13 : 3);
+  o[0] = ls; o[1] = alpha; o[2] = sigma;
+  if (!t_next) return;
+  const float tn = t_next[b];
+  const float lsn = ct_log_snr(tn, kind);
+  const float alpha_n = sqrtf(ct_sigmoid(lsn)), sigma_n = sqrtf(ct_sigmoid(-lsn));
+  const float c = -ct_expm1(ls - lsn);
+  const float var = (sigma_n * sigma_n) * c;
+  const float logvar = ct_log(fmaxf(var, 1e-20f));
+  o[3] = lsn; o[4] = alpha_n; o[5] = sigma_n; o[6] = c; o[7] = var; o[8] = logvar;
+  o[9] = 1.f / fmaxf(alpha, 1e-8f);
+  o[10] = alpha_n * ((1.f - c) / alpha);
+  o[11] = alpha_n * c;
+  o[12] = tn > 0.f ? ct_exp(0.5f * logvar) : 0.f;
+}
+
+// eps = null + (cond - null) cond_scale;  x0 = clamp((x - sigma eps) / max(alpha, 1e-8), -1, 1);  mean = alpha_next (x (1 - c) / alpha + c x0);
+// out = mean + gain * noise.  k = the sample's schedule row.  A zero gain (t_next == 0) or no noise buffer: the mean, whatever noise holds.
+__device__ inline float ct_step_one(float x, float cond, const float* nullp, const float* noise, long idx, float cond_scale, const float* k) {
+  float eps = cond;
+  if (nullp) { const float nu = nullp[idx]; eps = nu + (eps - nu) * cond_scale; }
+  float x0 = (x - k[2] * eps) * k[9];
+  x0 = fminf(fmaxf(x0, -1.f), 1.f);
+  const float mean = k[10] * x + k[11] * x0;
+  const float gain = k[12];
+  return (noise && gain != 0.f) ? mean + gain * noise[idx] : mean;
+}
+
+// VEC: x, cond and out are 16-byte aligned, four elements per lane over the flat (B * per_sample) range (a group may straddle two
+// samples when per_sample is no multiple of 4: the row is looked up per element there) and a scalar tail of total % 4 elements.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ct_step_kernel(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef,
+                                                      const float* noise, float* out, long per_sample, long total) {
+  if (!VEC) {
+    GRID_STRIDE(idx, total) out[idx] = ct_step_one(x[idx], cond[idx], nullp, noise, idx, cond_scale, coef + 13 * (idx / per_sample));
+    return;
+  }
+  const long groups = total >> 2;
+  GRID_STRIDE(g, groups) {
+    const long i0 = g << 2;
+    const long b0 = i0 / per_sample;
+    const long left = (b0 + 1) * per_sample - i0;          // elements of this group's first sample from i0 on (>= 1)
+    const f32x4 xv = reinterpret_cast<const f32x4*>(x)[g], cv = reinterpret_cast<const f32x4*>(cond)[g];
+    f32x4 ov;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const long b = e < left ? b0 : (i0 + e) / per_sample;
+      ov[e] = ct_step_one(xv[e], cv[e], nullp, noise, i0 + e, cond_scale, coef + 13 * b);
+    }
+    reinterpret_cast<f32x4*>(out)[g] = ov;
+  }
+  const long tail = (groups << 2) + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < (total & 3))
+    out[tail] = ct_step_one(x[tail], cond[tail], nullp, noise, tail, cond_scale, coef + 13 * (tail / per_sample));
+}
+
 // masked MSE: loss_sum += sum w*(pred-target)^2 (double), grad = 2*w*(pred-target)  (scaled by 1/count later)
 __global__ __launch_bounds__(256) void mse_kernel(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum,
                                                   int Dch, int L, long total) {
@@ -240,6 +331,23 @@ extern "C" int osuf_ddim_step(const float* x, const float* cond, const float* nu
   if (B <= 0 || per_sample <= 0) return OSUF_EINVAL;
   const long tot = (long)B * per_sample;
   hipLaunchKernelGGL(ddim_step_kernel, dim3(ew_grid(tot)), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, out, per_sample, tot);
+  return osuf_launch_status();
+}
+
+extern "C" int osuf_ct_schedule(const float* t, const float* t_next, int kind, float* out, int B, hipStream_t stream) {
+  if (B <= 0 || !t || !out || (kind != 0 && kind != 1)) return OSUF_EINVAL;
+  hipLaunchKernelGGL(ct_schedule_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, t, t_next, kind, out, B);
+  return osuf_launch_status();
+}
+
+extern "C" int osuf_ct_step(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* noise,
+                            float* out, int B, long per_sample, hipStream_t stream) {
+  if (B <= 0 || per_sample <= 0 || !x || !cond || !coef || !out) return OSUF_EINVAL;
+  const long tot = (long)B * per_sample;
+  if (al16(x) && al16(cond) && al16(out) && tot >= 4)
+    hipLaunchKernelGGL(ct_step_kernel<true>, dim3(ew_grid(tot / 4)), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, noise, out, per_sample, tot);
+  else
+    hipLaunchKernelGGL(ct_step_kernel<false>, dim3(ew_grid(tot)), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, noise, out, per_sample, tot);
   return osuf_launch_status();
 }
 

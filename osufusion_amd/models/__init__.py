@@ -1,2 +1,2 @@
 from . import diffusion, rectified_flow, transformer_diffusion  # noqa: F401
-from .transformer_diffusion import DiffusionOsuFusionDiT, RectifiedFlowOsuFusionDiT  # noqa: F401
+from .transformer_diffusion import ContinuousDiffusionOsuFusionDiT, DiffusionOsuFusionDiT, RectifiedFlowOsuFusionDiT  # noqa: F401

@@ -1,6 +1,7 @@
 """The DiT / MMDiT backbones behind the reference's ``OsuFusion`` interface: ``DiffusionOsuFusionDiT`` mirrors models/diffusion.OsuFusion and
 ``RectifiedFlowOsuFusionDiT`` models/rectified_flow.OsuFusion method for method (``forward`` = training loss, ``loss_with``, ``sample``,
-``set_full_bf16``).  The backbone is stored as ``self.unet``: the reference trainers call ``model.unet.set_gradient_checkpointing`` and write
+``set_full_bf16``).  ``ContinuousDiffusionOsuFusionDiT`` is the same interface on modules/scheduler.GaussianDiffusionContinuousTimes: the
+backbone's time input is the log-SNR, sampling is ancestral (DDPM), one osuf_ct_step per step.  The backbone is stored as ``self.unet``: the reference trainers call ``model.unet.set_gradient_checkpointing`` and write
 checkpoints with ``unet.``-prefixed keys, so train.py / data.py take these models as they are.
 
 ``sample`` is restructured like the UNet samplers: everything that does not depend on the step -- the audio's embedding rows and
@@ -18,6 +19,7 @@ from .. import ops
 from .. import runtime as rt
 from ..modules.dit import DiT
 from ..modules.mmdit import MMDiT
+from ..modules.scheduler import GaussianDiffusionContinuousTimes
 from .diffusion import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, DDIMSchedule, _MSEFn
 from .rectified_flow import cosmap
 
@@ -120,6 +122,59 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
         with self._dtype_ctx():
             x_noisy = self.scheduler.add_noise(x, noise, timesteps)
             pred = self.unet(x_noisy, a, timesteps, c, cond_drop_prob=p)
+        return _MSEFn.apply(pred, noise.float(), orig_len)
+
+
+class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
+    """Continuous-time Gaussian diffusion: noise prediction conditioned on log_snr(t) (scheduler.get_condition), t uniform in [0, 1]."""
+
+    def __init__(self, dim_h: int, backbone: str = "mmdit", cond_drop_prob: float = 0.5, noise_schedule: str = "cosine",
+                 sampling_timesteps: int = 35, **backbone_kwargs) -> None:
+        super().__init__(dim_h, backbone, cond_drop_prob, **backbone_kwargs)
+        self.scheduler = GaussianDiffusionContinuousTimes(noise_schedule=noise_schedule, timesteps=sampling_timesteps)
+        self.sampling_timesteps = sampling_timesteps
+        self.stop_after: Optional[int] = None
+
+    @torch.inference_mode()
+    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0) -> torch.Tensor:
+        """Ancestral sampling over scheduler.get_sampling_timesteps: per step one denoiser call at log_snr(t) (2B rows with guidance) and one
+        ops.ct_step (guidance, start prediction clamped to [-1, 1], posterior mean, noise).  Draws from the global generator, in this order:
+        the start iterate torch.randn((B, 6, n)) when x is None, then one torch.randn of the iterate's shape per step, in step order; the
+        last step (t_next == 0) adds no noise and draws none.  A plain loop that draws the same way from the same seed sees the same
+        noise.  Bit-reproducible for a given seed.  (Attribute `stop_after` as in DiffusionOsuFusionDiT.)"""
+        with ops.reproducible_mode(True), ops.one_launch_attention(True):
+            return self._sample(a, c, x, cond_scale, self.stop_after)
+
+    def _sample(self, a, c, x, cond_scale, stop_after):
+        x = self._start(a, x)
+        b, device = a.shape[0], a.device
+        cfg = cond_scale != 1.0
+        total = self.scheduler.timesteps
+        steps = total if stop_after is None else min(stop_after, total)
+        times = torch.linspace(1.0, 0.0, total + 1, device=device, dtype=torch.float32)        # get_sampling_timesteps' grid, every pair at once
+        coef = self.scheduler.coefficients(times[:-1].repeat_interleave(b), times[1:].repeat_interleave(b)).view(total, b, -1)
+        log_snr = coef[:, :, 0].repeat(1, 2 if cfg else 1).contiguous()
+        with self._dtype_ctx():
+            f = self._denoiser(a, c, cfg)
+            for i in range(steps):
+                pred = f(x, log_snr[i])
+                noise = torch.randn(x.shape, device=device) if i < total - 1 else None
+                x = ops.ct_step(x, pred[:b], pred[b:] if cfg else None, cond_scale, coef[i], noise)
+        return x
+
+    def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+        assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"
+        rt.require_gpu(x)
+        noise = torch.randn_like(x, device=x.device)
+        times = self.scheduler.sample_random_times(x.shape[0], x.device)
+        return self.loss_with(x, a, c, noise, times, orig_len)
+
+    def loss_with(self, x, a, c, noise, times, orig_len=None, cond_drop_prob: Optional[float] = None) -> torch.Tensor:
+        """forward() with the RNG draws passed in (parity tests, benchmarks)."""
+        p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
+        with self._dtype_ctx():
+            x_noisy, log_snr, _, _ = self.scheduler.q_sample(x, times.float(), noise)
+            pred = self.unet(x_noisy, a, log_snr.contiguous(), c, cond_drop_prob=p)
         return _MSEFn.apply(pred, noise.float(), orig_len)
 
 

@@ -1,1 +1,2 @@
-from . import attention, lora_layers, residual, unet, utils  # noqa: F401
+from . import attention, lora_layers, residual, scheduler, unet, utils  # noqa: F401
+from .scheduler import GaussianDiffusionContinuousTimes  # noqa: F401

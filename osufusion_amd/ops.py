@@ -686,6 +686,21 @@ def ddim_step(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Tensor],
     return out
 
 
+def ct_schedule(t: torch.Tensor, t_next: Optional[torch.Tensor] = None, kind: int = 0) -> torch.Tensor:
+    """The continuous-time log-SNR schedule (kind 0 linear, 1 cosine) at t (B,) -> fp32 (B, 3) = log_snr, alpha, sigma; with t_next (B,),
+    (B, 13): those, the three at t_next, c, the posterior variance and its clamped log, and osuf_ct_step's factors.  One launch, no host
+    sync.  The allocating wrapper lives in osufusion_amd/ct.py (its guarded-memory case in tests/test_scheduler_gpu.py)."""
+    from . import ct
+    return ct.ct_schedule(t, t_next, kind)
+
+
+def ct_step(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Tensor], cond_scale: float, coef: torch.Tensor,
+            noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One ancestral (DDPM) step with coef = ct_schedule(t, t_next, kind): guidance, start prediction, clamp, posterior mean, noise."""
+    from . import ct
+    return ct.ct_step(x, cond, null, cond_scale, coef, noise)
+
+
 def mse(pred: torch.Tensor, target: torch.Tensor, orig_len: Optional[torch.Tensor], want_grad: bool):
     B, Dc, Lx = pred.shape
     grad = torch.empty_like(pred) if want_grad else None
