@@ -244,7 +244,8 @@ int osuf_mqa_bwd_dkv(const void* q, long ldq, const void* k, long ldk, const voi
 /* Short sequences give the dK/dV kernel few 256-key workgroups (B=32, N=512: 64 on 256 CUs): with a 16-byte-aligned fp32 workspace
  * of this many bytes (0 = the shape does not need it) the query range is cut into 2 or 4 parts whose partial sums a finishing pass
  * adds in a fixed order (then scale, RoPE transpose, cast).  workspace NULL / too small: the unsplit kernel runs.
- * qsplit: 0 = the default split of the shape; 1..16 = force that many parts (the same value goes to osuf_mqa_bwd_dkv). */
+ * qsplit: 0 = the default split of the shape; 1..16 = force that many parts (the same value goes to osuf_mqa_bwd_dkv); a forced count is
+ * brought down to the parts that get at least one 32-query block (N = 33 has two blocks: at most 2 parts). */
 long osuf_mqa_bwd_dkv_workspace_bytes(int B, int N, int qsplit);
 
 /* The whole attention backward in ONE key-stationary sweep (S, dP and the exponentials are computed once per (query, key) pair

@@ -531,6 +531,17 @@ __device__ __forceinline__ void store_dkv(const AttnArgs& a, int part, int b, in
   }
 }
 
+// dS^T of a ragged last key tile (query-stationary kernels: accumulator rows = keys): a key beyond N has zero K / V rows, so its score is 0 and
+// its p = exp2(-lse2) -- finite garbage that meets a zero K row for an ordinary row, but inf for a row with lse2 < -128, and inf x 0 is NaN in dQ.
+// The padded keys' dS is therefore cleared outright (last tile only, a wave-uniform branch).
+__device__ __forceinline__ void zero_padded_keys(f32x16 (&ds)[2], int key0, int N, int lh) {
+#pragma unroll
+  for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (key0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh >= N) ds[kt][r] = 0.f;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // backward, dQ: query-stationary.  dQ^T[d][q] = sum_key K^T[d][key] * dS^T[key][q]
 // ------------------------------------------------------------------------------------------------------
@@ -576,6 +587,7 @@ __global__ __launch_bounds__(NW * 64) void mqa_bwd_dq_kernel(AttnArgs a) {
         float p = fast_exp2(fmaf(s[kt][r], c, -L2));
         s[kt][r] = p * (dp[kt][r] - dl);          // * scale folded into the final store
       }
+    if (j == ntiles - 1 && (a.N & 63) != 0) zero_padded_keys(s, j * 64, a.N, lh);
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) {
       const bf16x8 df = acc_to_frag(s[s4 >> 1], s4 & 1);
@@ -678,6 +690,7 @@ __global__ __launch_bounds__(512) void mqa_bwd_dq_pipe_kernel(AttnArgs a) {
       }                                                  // iteration, and code sinking would otherwise move all 32 exps behind the MFMAs)
       OSUF_FENCE;
     }
+    if (j == ntiles - 1 && (a.N & 63) != 0) zero_padded_keys(sc, j * 64, a.N, lh);
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) dfp[s4] = acc_to_frag(sc[s4 >> 1], s4 & 1);
     OSUF_FENCE;
@@ -997,8 +1010,11 @@ __device__ __forceinline__ int ds_img_off(int key, int qchunk) {     // 8-byte c
 // RAGGED = N is not a multiple of 32.  Whole-block shapes (every UNet level) take the lean form: no row clamps / selects, and
 // every global address of the loop is a wave-uniform 64-bit base (SGPRs, advanced by scalar adds) plus a loop-invariant 32-bit
 // lane offset -- the clamped per-lane 64-bit form cost ~50 of the loop's 134 VALU instructions.
-template <int DQ_MODE, bool RAGGED>
+// PADK = N is not a multiple of 256: the last key block has lanes without a key (zero K / V rows, score 0).  Their p = exp2(-lse2) overflows for a
+// row with lse2 < -128 and inf x (the zero K row of the dQ product) is NaN, so their dS is cleared; whole key blocks keep the loop without the select.
+template <int DQ_MODE, bool RAGGED, bool PADK = RAGGED>
 __global__ __launch_bounds__(512) void mqa_bwd_fused_kernel(AttnArgs a, float* dq32) {
+  static_assert(PADK || !RAGGED, "a ragged query count leaves a partial key block");
   extern __shared__ __attribute__((aligned(16))) char smem[];        // [2][Q 4K | dO 4K | lse 128 | delta 128] | K image 32K | [2] dS image 16K
   constexpr int NW = 8, kStage = 4096 + 4096 + 256;
   char* kimg = smem + 2 * kStage;
@@ -1152,6 +1168,7 @@ __global__ __launch_bounds__(512) void mqa_bwd_fused_kernel(AttnArgs a, float* d
         float p = fast_exp2(fmaf(s[r], c, -l4[e]));
         s[r] = p;
         ds[r] = p * (dp[r] - d4[e]);                // * scale folded into the finishing passes
+        if constexpr (PADK) ds[r] = kok ? ds[r] : 0.f;
       }
     }
     // dS rows of this wave's keys -> the transposing image (queries 8g + 4lh .. +3 = one 8-byte chunk)
@@ -2118,8 +2135,14 @@ static void launch_dkv_finish(const AttnArgs& a, hipStream_t stream) {
 
 // dk, dv: [B*N][lddk] in out_dtype; rope tables as for dq (applied to dk only)
 // query parts of the dK/dV kernel for this shape: short sequences give few 256-key workgroups (B=32, N=512: 64 on 256 CUs)
+// A forced part count is brought down to the parts that get a query block: KeyBlock deals ceil(nqb / parts) blocks to each part, and a part left
+// without one returns before it has written its partial sums, which the finishing pass would then add up unwritten (N = 33 with 4 parts)
+static int qsplit_parts(int nqb, int forced) {
+  const int per = (nqb + forced - 1) / forced;
+  return (nqb + per - 1) / per;
+}
 static int dkv_qsplit(int B, int N, int forced) {
-  if (forced > 0) return forced;
+  if (forced > 0) return qsplit_parts((N + 31) / 32, forced);
   const int blocks = ((N + 255) / 256) * ((B + 7) / 8 * 8);
   int sp = 1;
   while (sp < 4 && blocks * sp < 256 && ((N + 31) / 32) / (sp * 2) >= 4) sp *= 2;
@@ -2187,7 +2210,7 @@ static bool fused_use512(int B, int N, int dq_mode) {
   return (N % 512) == 0 && N >= 1024;
 }
 static int fused512_qsplit(int B, int N, int forced) {
-  if (forced > 0) return forced;
+  if (forced > 0) return qsplit_parts((N + 31) / 32, forced);
   const int blocks = ((N + 511) / 512) * ((B + 7) / 8 * 8);
   int sp = 1;
   while (sp < 8 && blocks * sp < 256 && (N / 32) / (sp * 2) >= 8) sp *= 2;
@@ -2281,15 +2304,18 @@ static int mqa_bwd_fused_impl(const void* q, long ldq, const void* k, long ldk, 
   } else if (use512) {
     launch_fused<mqa_bwd_fused512_kernel>(grid512, 256, lds512, stream, a, dq32);
   } else {
-    const bool ragged = (N % 32) != 0;
+    const bool ragged = (N % 32) != 0, padk = (N % 256) != 0;       // ragged query blocks; a partial last key block
     if (dq_mode != OSUF_DQ_SLABS) {
       if (ragged) launch_fused<mqa_bwd_fused_kernel<0, true>>(grid256, 512, lds256, stream, a, dq32);
+      else if (padk) launch_fused<mqa_bwd_fused_kernel<0, false, true>>(grid256, 512, lds256, stream, a, dq32);
       else launch_fused<mqa_bwd_fused_kernel<0, false>>(grid256, 512, lds256, stream, a, dq32);
     } else if (a.g_bf16) {
       if (ragged) launch_fused<mqa_bwd_fused_kernel<1, true>>(grid256, 512, lds256, stream, a, dq32);
+      else if (padk) launch_fused<mqa_bwd_fused_kernel<1, false, true>>(grid256, 512, lds256, stream, a, dq32);
       else launch_fused<mqa_bwd_fused_kernel<1, false>>(grid256, 512, lds256, stream, a, dq32);
     } else {
       if (ragged) launch_fused<mqa_bwd_fused_kernel<2, true>>(grid256, 512, lds256, stream, a, dq32);
+      else if (padk) launch_fused<mqa_bwd_fused_kernel<2, false, true>>(grid256, 512, lds256, stream, a, dq32);
       else launch_fused<mqa_bwd_fused_kernel<2, false>>(grid256, 512, lds256, stream, a, dq32);
     }
   }

@@ -244,11 +244,9 @@ __global__ __launch_bounds__(256) void mqa_gen_bwd_dq_kernel(AttnArgs a, int hd)
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float p = fast_exp2(fmaf(s[kt][r], c, -L2));                  // keys past Nk: zero K rows -> their dS meets zero K rows below
-        if constexpr (MASKED) {                                        // (a clamped bias could make p large there: drop it outright)
-          const int key = j * 64 + kt * 32 + acc_row(r, lh);
-          p = key < a.Nk ? p : 0.f;
-        }
+        float p = fast_exp2(fmaf(s[kt][r], c, -L2));                  // keys past Nk: their dS meets zero K rows below, but p = exp2(-lse2)
+        const int key = j * 64 + kt * 32 + acc_row(r, lh);             // (or of a clamped bias) is inf for a row with lse2 < -128 and
+        p = key < a.Nk ? p : 0.f;                                      // inf x 0 is NaN: drop it outright
         s[kt][r] = p * (dp[kt][r] - dl);
       }
 #pragma unroll

@@ -20,6 +20,7 @@ if torch.cuda.is_available():
 
 from oracle import diffusion_oracle as DO
 from oracle import unet_oracle as O
+from tests.attn_reference import bwd_cases
 from tests.test_hip_parity import DEV, _build_model, rell2, relmax, report
 
 
@@ -63,13 +64,9 @@ def test_every_attention_backward_kernel_vs_fp32_autograd(N):
     qkv, do, o_ref, g_ref = _attn_case(Bn, N, H)
     o, lse = ops.mqa_fwd(qkv, Bn, N, H, D, torch.bfloat16, D ** -0.5)
     assert rell2(o.float(), o_ref) < 5e-3                              # bf16 P and bf16 output rounding
-    cases = [("auto", ops.ATTN_AUTO, 0), ("plain", ops.ATTN_PLAIN, 0), ("pipe-unsplit", ops.ATTN_PIPE, 1), ("pipe-split2", ops.ATTN_PIPE, 2),
-             ("pipe-split4", ops.ATTN_PIPE, 4), ("fused", ops.ATTN_FUSED, 0), ("fused-split2", ops.ATTN_FUSED, 2),
-             ("fused-slabs", ops.ATTN_FUSED_SLABS, 0), ("fused256", ops.ATTN_FUSED256, 0)]
-    if N % 32 == 0:                                                    # round 3: the 4-wave, 512-keys-per-workgroup sweep (whole query blocks)
-        cases += [("fused512", ops.ATTN_FUSED512, 1), ("fused512-split2", ops.ATTN_FUSED512, 2), ("fused512-auto", ops.ATTN_FUSED512, 0)]
-    if N % 512 == 0:                                                   # round 4: the same sweep with its generated, hand-placed loop (whole 512-key blocks)
-        cases += [("fused512a", ops.ATTN_FUSED512A, 1), ("fused512a-split2", ops.ATTN_FUSED512A, 2), ("fused512a-auto", ops.ATTN_FUSED512A, 0)]
+    # the variant list is shared with tests/test_attn_exact_gpu.py: 9 kernels that take any N, the 4-wave 512-keys-per-workgroup sweep (round 3: whole
+    # query blocks) and the same sweep with its generated, hand-placed loop (round 4: whole 512-key blocks)
+    cases = bwd_cases(ops, N)
     outs = {}
     for name, variant, qsplit in cases:
         dqkv = ops.mqa_bwd(qkv, o, do, lse, Bn, N, H, D, D ** -0.5, variant=variant, qsplit=qsplit)
