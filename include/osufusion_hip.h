@@ -294,8 +294,36 @@ int osuf_ddim_step(const float* x, const float* cond, const float* nullp, float 
 int osuf_ct_schedule(const float* t, const float* t_next, int kind, float* out, int B, hipStream_t stream);
 int osuf_ct_step(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* noise,
                  float* out, int B, long per_sample, hipStream_t stream);
+/* Prediction objectives and dynamic thresholding (Imagen 2.3) on the same rows.  objective = what the network predicts: with p = the
+ * guided prediction (nullp ? nullp + (cond - nullp) cond_scale : cond) the unclamped start prediction x0 is (x - sigma p) / max(alpha, 1e-8)
+ * for OSUF_CT_OBJ_NOISE, p for OSUF_CT_OBJ_X_START and alpha x - sigma p for OSUF_CT_OBJ_V.
+ * osuf_ct_step_ex: osuf_ct_step with that x0 and an optional per-sample threshold, sample b's at s[b * s_ld] (s_ld = 3 reads column 2 of
+ * osuf_ct_x0_quantile's rows in place): x0 = clamp(x0, -s, s) / s, else the static clamp to [-1, 1]; the posterior mean and the noise as
+ * in osuf_ct_step, which is this call with OSUF_CT_OBJ_NOISE and s = NULL.
+ * osuf_ct_x0_quantile: per sample, the order statistics of |x0| over its per_sample values at ranks k_lo and min(k_lo + 1, per_sample - 1)
+ * (ascending, 0-based) and s = max(1, lo + (hi - lo) frac) -> out[B][3] = {lo, hi, s}.  The host passes k_lo = floor(q (per_sample - 1)) and
+ * frac = q (per_sample - 1) - k_lo (torch.quantile's linear interpolation).  lo and hi are exact (a radix select on the bit patterns of
+ * |x0|, x0 recomputed in every pass, nothing sorted or stored; -0.0 and subnormals in their order) and do not depend on scheduling: integer
+ * histogram counts only.  workspace: osuf_ct_x0_quantile_workspace_bytes(B) bytes, 16-byte aligned, zeroed by the call; inputs finite;
+ * per_sample <= 2^30, B <= 65535.  Three counting launches over (ceil(per_sample / 4096), B) workgroups and a B-workgroup finish.
+ * osuf_ct_qsample: x_noisy = alpha x0 + sigma noise and (target may be NULL) the objective's training target = noise, x0 or
+ * v = alpha noise - sigma x0, in one pass; sample b's alpha and sigma are sched[b * sched_ld + 1] and [+ 2] (osuf_ct_schedule's rows). */
+#define OSUF_CT_OBJ_NOISE 0
+#define OSUF_CT_OBJ_X_START 1
+#define OSUF_CT_OBJ_V 2
+int osuf_ct_step_ex(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* noise,
+                    int objective, const float* s, long s_ld, float* out, int B, long per_sample, hipStream_t stream);
+int osuf_ct_x0_quantile(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, int objective,
+                        long k_lo, float frac, float* out, void* workspace, int B, long per_sample, hipStream_t stream);
+long osuf_ct_x0_quantile_workspace_bytes(int B);
+int osuf_ct_qsample(const float* x0, const float* noise, const float* sched, int sched_ld, int objective, float* x_noisy, float* target,
+                    int B, long per_sample, hipStream_t stream);
 int osuf_mse(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum, int B, int Dch, int L,
              hipStream_t stream);
+/* osuf_mse with per-sample weights w[B] (min-SNR-gamma): loss_sum += sum_b w[b] sum_{d, l < len_b} (pred - target)^2 and
+ * grad = 2 w[b] mask (pred - target); the caller divides both by sum_b Dch len_b as for osuf_mse.  w of ones gives osuf_mse's bits. */
+int osuf_mse_w(const float* pred, const float* target, const int* orig_len, const float* w, float* grad, double* loss_sum, int B, int Dch,
+               int L, hipStream_t stream);
 int osuf_sqnorm(const float* g, long n, double* out, hipStream_t stream);
 int osuf_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps, float wd,
                int step, const float* gscale, hipStream_t stream);

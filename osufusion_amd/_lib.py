@@ -70,7 +70,12 @@ SIGNATURES = {
     "osuf_ddim_step": [P, P, P, F, P, P, I, L, P],
     "osuf_ct_schedule": [P, P, I, P, I, P],
     "osuf_ct_step": [P, P, P, F, P, P, P, I, L, P],
+    "osuf_ct_step_ex": [P, P, P, F, P, P, I, P, L, P, I, L, P],
+    "osuf_ct_x0_quantile": [P, P, P, F, P, I, L, F, P, P, I, L, P],
+    "osuf_ct_x0_quantile_workspace_bytes": [I],
+    "osuf_ct_qsample": [P, P, P, I, I, P, P, I, L, P],
     "osuf_mse": [P, P, P, P, P, I, I, I, P],
+    "osuf_mse_w": [P, P, P, P, P, P, I, I, I, P],
     "osuf_sqnorm": [P, L, P, P],
     "osuf_adamw": [P, P, P, P, L, F, F, F, F, F, I, P, P],
     "osuf_clip_coef": [P, F, F, P, P, P],

@@ -152,11 +152,26 @@ __global__ __launch_bounds__(256) void ct_schedule_kernel(const float* t, const 
 
 // eps = null + (cond - null) cond_scale;  x0 = clamp((x - sigma eps) / max(alpha, 1e-8), -1, 1);  mean = alpha_next (x (1 - c) / alpha + c x0);
 // out = mean + gain * noise.  k = the sample's schedule row.  A zero gain (t_next == 0) or no noise buffer: the mean, whatever noise holds.
-__device__ inline float ct_step_one(float x, float cond, const float* nullp, const float* noise, long idx, float cond_scale, const float* k) {
+// OBJ = what the network predicts (OSUF_CT_OBJ_*): the start prediction is (x - sigma p) / max(alpha, 1e-8) for noise, p itself for x_start and
+// alpha x - sigma p for v.  THR: the sample's dynamic threshold s (>= 1, osuf_ct_x0_quantile) replaces the static clamp: clamp(x0, -s, s) / s.
+#define OSUF_CT_OBJ_NOISE 0                                  // as in include/osufusion_hip.h
+#define OSUF_CT_OBJ_X_START 1
+#define OSUF_CT_OBJ_V 2
+template <int OBJ>
+__device__ inline float ct_start(float x, float p, const float* k) {
+  if (OBJ == 1) return p;
+  if (OBJ == 2) return k[1] * x - k[2] * p;
+  return (x - k[2] * p) * k[9];
+}
+
+template <int OBJ, bool THR>
+__device__ inline float ct_step_one(float x, float cond, const float* nullp, const float* noise, long idx, float cond_scale, const float* k,
+                                    const float* s) {
   float eps = cond;
   if (nullp) { const float nu = nullp[idx]; eps = nu + (eps - nu) * cond_scale; }
-  float x0 = (x - k[2] * eps) * k[9];
-  x0 = fminf(fmaxf(x0, -1.f), 1.f);
+  float x0 = ct_start<OBJ>(x, eps, k);
+  if (THR) { const float sv = *s; x0 = fminf(fmaxf(x0, -sv), sv) / sv; }
+  else x0 = fminf(fmaxf(x0, -1.f), 1.f);
   const float mean = k[10] * x + k[11] * x0;
   const float gain = k[12];
   return (noise && gain != 0.f) ? mean + gain * noise[idx] : mean;
@@ -164,11 +179,15 @@ __device__ inline float ct_step_one(float x, float cond, const float* nullp, con
 
 // VEC: x, cond and out are 16-byte aligned, four elements per lane over the flat (B * per_sample) range (a group may straddle two
 // samples when per_sample is no multiple of 4: the row is looked up per element there) and a scalar tail of total % 4 elements.
-template <bool VEC>
+// s (THR only): sample b's threshold is s[b * s_ld], so that column 2 of osuf_ct_x0_quantile's rows is read in place.
+template <bool VEC, int OBJ, bool THR>
 __global__ __launch_bounds__(256) void ct_step_kernel(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef,
-                                                      const float* noise, float* out, long per_sample, long total) {
+                                                      const float* noise, const float* s, long s_ld, float* out, long per_sample, long total) {
   if (!VEC) {
-    GRID_STRIDE(idx, total) out[idx] = ct_step_one(x[idx], cond[idx], nullp, noise, idx, cond_scale, coef + 13 * (idx / per_sample));
+    GRID_STRIDE(idx, total) {
+      const long b = idx / per_sample;
+      out[idx] = ct_step_one<OBJ, THR>(x[idx], cond[idx], nullp, noise, idx, cond_scale, coef + 13 * b, THR ? s + b * s_ld : nullptr);
+    }
     return;
   }
   const long groups = total >> 2;
@@ -181,23 +200,172 @@ __global__ __launch_bounds__(256) void ct_step_kernel(const float* x, const floa
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const long b = e < left ? b0 : (i0 + e) / per_sample;
-      ov[e] = ct_step_one(xv[e], cv[e], nullp, noise, i0 + e, cond_scale, coef + 13 * b);
+      ov[e] = ct_step_one<OBJ, THR>(xv[e], cv[e], nullp, noise, i0 + e, cond_scale, coef + 13 * b, THR ? s + b * s_ld : nullptr);
     }
     reinterpret_cast<f32x4*>(out)[g] = ov;
   }
   const long tail = (groups << 2) + threadIdx.x;
-  if (blockIdx.x == 0 && threadIdx.x < (total & 3))
-    out[tail] = ct_step_one(x[tail], cond[tail], nullp, noise, tail, cond_scale, coef + 13 * (tail / per_sample));
+  if (blockIdx.x == 0 && threadIdx.x < (total & 3)) {
+    const long b = tail / per_sample;
+    out[tail] = ct_step_one<OBJ, THR>(x[tail], cond[tail], nullp, noise, tail, cond_scale, coef + 13 * b, THR ? s + b * s_ld : nullptr);
+  }
+}
+
+// ---- dynamic thresholding (Imagen 2.3): per-sample order statistics of |x0| by an exact radix select ----------------------------------
+// Non-negative fp32 values order as their bit patterns, so the rank-k value of |x0| is found digit by digit over the 31 bits below the
+// sign (11 + 10 + 10), most significant first: histogram the digit of every element whose higher bits equal the prefix found so far, walk
+// the histogram to the bin that holds the rank, append the bin to the prefix.  No element is stored or moved: x0 is recomputed from
+// x / cond / nullp in every pass, by the same kernel (`pass` is a runtime argument, so every pass runs the same instructions and forms the same
+// bits).  Two ranks (k_lo, k_hi = k_lo + 1) are carried: while their prefixes agree they share one histogram, from the pass in which they part each
+// has its own.  A sample is spread over gridDim.x workgroups; each counts its slice in LDS (integer ds_add, no float atomics) and adds
+// its non-empty bins to the sample's histogram in the workspace with integer atomics, so the counts -- and with them the result -- do not
+// depend on which workgroup ran when.  The kernel boundary is the barrier between passes: pass p's workgroups each re-derive the prefix from
+// pass p - 1's finished histogram (2048 bins, one 8-bin strip per lane), and the finish kernel does it once more and writes lo, hi, s.
+// Workspace per sample (unsigned): hist[5][2048] = {pass 0; pass 1 lo, hi; pass 2 lo, hi}, then state[2][4] = {prefix_lo, k_lo, prefix_hi,
+// k_hi} on entering pass 1 and pass 2 (written by the sample's first workgroup of pass p, read by pass p + 1).  Zeroed per call.
+#define CTQ_BINS 2048
+#define CTQ_WS_PER_SAMPLE (5 * CTQ_BINS + 8)
+#define CTQ_CHUNK 4096                                       // elements per workgroup: 256 lanes x 4 x 4
+
+// The state on entering `pass` (1, 2, or 3 = finished) -> st[4] in LDS, from the state on entering pass - 1 and that pass's histogram(s).
+__device__ inline void ctq_advance(const unsigned* wsb, int pass, unsigned k_lo, unsigned k_hi, unsigned* st, unsigned* wave_tot) {
+  unsigned prefix[2] = {0u, 0u}, k[2] = {k_lo, k_hi};
+  if (pass > 1) {
+    const unsigned* prev = wsb + 5 * CTQ_BINS + (pass - 2) * 4;
+    prefix[0] = prev[0]; k[0] = prev[1]; prefix[1] = prev[2]; k[1] = prev[3];
+  }
+  const int slot_lo = pass == 1 ? 0 : 2 * pass - 3;           // pass - 1's histogram of the low rank: 0, 1, 3
+  const int slot[2] = {slot_lo, prefix[0] == prefix[1] ? slot_lo : slot_lo + 1};
+  const int bits = pass == 1 ? 11 : 10;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const uint4* h = reinterpret_cast<const uint4*>(wsb + slot[r] * CTQ_BINS + tid * 8);
+    const uint4 a = h[0], c = h[1];
+    const unsigned bin[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+    unsigned sum = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sum += bin[e];
+    unsigned incl = sum;                                      // inclusive scan over the wave, then over the four waves
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+    __syncthreads();                                          // wave_tot of the previous rank has been read
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    unsigned before = incl - sum;
+    for (int w = 0; w < wave; ++w) before += wave_tot[w];
+    if (k[r] >= before && k[r] - before < sum) {              // exactly one lane: the strip that holds the rank
+      unsigned left = k[r] - before;
+      int found = -1;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {                           // unrolled: bin[] stays in registers
+        if (found < 0) { if (left < bin[e]) found = e; else left -= bin[e]; }
+      }
+      st[2 * r] = (prefix[r] << bits) | (unsigned)(tid * 8 + found);
+      st[2 * r + 1] = left;
+    }
+  }
+  __syncthreads();
+}
+
+__device__ inline unsigned ctq_key(float x, float cond, float nu, bool guided, float cond_scale, const float* k, int objective) {
+  float p = cond;
+  if (guided) p = nu + (p - nu) * cond_scale;
+  const float x0 = objective == 1 ? ct_start<1>(x, p, k) : objective == 2 ? ct_start<2>(x, p, k) : ct_start<0>(x, p, k);
+  return __float_as_uint(x0) & 0x7fffffffu;                   // |x0|: -0.0 is 0, subnormals keep their order
+}
+
+__device__ inline void ctq_count(unsigned key, int pass, bool same, const unsigned* st, unsigned (*hist)[CTQ_BINS]) {
+  if (pass == 0) { atomicAdd(&hist[0][key >> 20], 1u); return; }
+  const unsigned pre = pass == 1 ? key >> 20 : key >> 10;
+  const unsigned d = (pass == 1 ? key >> 10 : key) & 1023u;
+  if (pre == st[0]) atomicAdd(&hist[0][d], 1u);
+  if (!same && pre == st[2]) atomicAdd(&hist[1][d], 1u);
+}
+
+// grid (G, B).  VEC: the sample's rows of x, cond and nullp are 16-byte aligned (per_sample % 4 == 0), four elements per lane.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ct_quantile_pass_kernel(const float* x, const float* cond, const float* nullp, float cond_scale,
+                                                               const float* coef, int objective, unsigned k_lo, unsigned k_hi, unsigned* ws,
+                                                               long per_sample, int pass) {
+  __shared__ unsigned hist[2][CTQ_BINS];
+  __shared__ unsigned st[4], wave_tot[4];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  unsigned* wsb = ws + (long)b * CTQ_WS_PER_SAMPLE;
+  if (pass > 0) {
+    ctq_advance(wsb, pass, k_lo, k_hi, st, wave_tot);
+    if (blockIdx.x == 0 && tid < 4) wsb[5 * CTQ_BINS + (pass - 1) * 4 + tid] = st[tid];
+  }
+  const bool same = pass == 0 || st[0] == st[2];
+  const int bins = pass == 0 ? CTQ_BINS : 1024;
+  for (int i = tid; i < bins; i += 256) { hist[0][i] = 0u; hist[1][i] = 0u; }
+  __syncthreads();
+  const float* k = coef + 13 * b;
+  const long base = (long)b * per_sample;
+  const bool guided = nullp != nullptr, need_x = objective != 1;
+  if (VEC) {
+    const long groups = per_sample >> 2;
+    for (long g = (long)blockIdx.x * 256 + tid; g < groups; g += (long)gridDim.x * 256) {
+      const long i = (base >> 2) + g;
+      const f32x4 cv = reinterpret_cast<const f32x4*>(cond)[i];
+      f32x4 xv = {0.f, 0.f, 0.f, 0.f}, nv = {0.f, 0.f, 0.f, 0.f};
+      if (need_x) xv = reinterpret_cast<const f32x4*>(x)[i];
+      if (guided) nv = reinterpret_cast<const f32x4*>(nullp)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ctq_count(ctq_key(xv[e], cv[e], nv[e], guided, cond_scale, k, objective), pass, same, st, hist);
+    }
+  } else {
+    for (long j = (long)blockIdx.x * 256 + tid; j < per_sample; j += (long)gridDim.x * 256) {
+      const long i = base + j;
+      ctq_count(ctq_key(need_x ? x[i] : 0.f, cond[i], guided ? nullp[i] : 0.f, guided, cond_scale, k, objective), pass, same, st, hist);
+    }
+  }
+  __syncthreads();
+  const int slot = pass == 0 ? 0 : 2 * pass - 1;
+  for (int i = tid; i < bins; i += 256) {
+    const unsigned h0 = hist[0][i];
+    if (h0) atomicAdd(wsb + slot * CTQ_BINS + i, h0);
+    if (!same) { const unsigned h1 = hist[1][i]; if (h1) atomicAdd(wsb + (slot + 1) * CTQ_BINS + i, h1); }
+  }
+}
+
+// grid (B).  out[b] = {lo, hi, s = max(1, lo + (hi - lo) frac)}: two fp32 roundings in the interpolation (no contraction), as a host
+// evaluates the same expression on the two values.
+__global__ __launch_bounds__(256) void ct_quantile_finish_kernel(const unsigned* ws, unsigned k_lo, unsigned k_hi, float frac, float* out) {
+#pragma clang fp contract(off)
+  __shared__ unsigned st[4], wave_tot[4];
+  const int b = blockIdx.x;
+  ctq_advance(ws + (long)b * CTQ_WS_PER_SAMPLE, 3, k_lo, k_hi, st, wave_tot);
+  if (threadIdx.x == 0) {
+    const float lo = __uint_as_float(st[0]), hi = __uint_as_float(st[2]);
+    out[3 * b] = lo; out[3 * b + 1] = hi;
+    out[3 * b + 2] = fmaxf(1.f, lo + (hi - lo) * frac);
+  }
+}
+
+// q_sample and the training target in one pass: x_noisy = alpha x0 + sigma noise; target = noise, x0, or v = alpha noise - sigma x0.
+// sched: the sample's schedule row (ld floats apart), alpha and sigma in columns 1 and 2.
+__global__ __launch_bounds__(256) void ct_qsample_kernel(const float* x0, const float* noise, const float* sched, int ld, int objective,
+                                                         float* x_noisy, float* target, long per_sample, long total) {
+  GRID_STRIDE(idx, total) {
+    const float* k = sched + (idx / per_sample) * ld;
+    const float a = k[1], s = k[2], xs = x0[idx], nz = noise[idx];
+    x_noisy[idx] = a * xs + s * nz;
+    if (target) target[idx] = objective == 1 ? xs : objective == 2 ? a * nz - s * xs : nz;
+  }
 }
 
 // masked MSE: loss_sum += sum w*(pred-target)^2 (double), grad = 2*w*(pred-target)  (scaled by 1/count later)
-__global__ __launch_bounds__(256) void mse_kernel(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum,
-                                                  int Dch, int L, long total) {
+// WEIGHTED: w is the length mask times the sample's loss weight wt[b] (min-SNR-gamma); a weight of one leaves every bit as it was.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void mse_kernel(const float* pred, const float* target, const int* orig_len, const float* wt, float* grad,
+                                                  double* loss_sum, int Dch, int L, long total) {
   float local = 0.f;
   GRID_STRIDE(idx, total) {
     const int n = (int)(idx % L);
     const long b = idx / ((long)Dch * L);
-    const float w = (!orig_len || n < orig_len[b]) ? 1.f : 0.f;
+    float w = (!orig_len || n < orig_len[b]) ? 1.f : 0.f;
+    if (WEIGHTED) w *= wt[b];
     const float d = pred[idx] - target[idx];
     local += w * d * d;
     if (grad) grad[idx] = 2.f * w * d;
@@ -340,14 +508,69 @@ extern "C" int osuf_ct_schedule(const float* t, const float* t_next, int kind, f
   return osuf_launch_status();
 }
 
+template <int OBJ, bool THR>
+static void ct_step_launch(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* noise,
+                           const float* s, long s_ld, float* out, long per_sample, long tot, hipStream_t stream) {
+  if (al16(x) && al16(cond) && al16(out) && tot >= 4)
+    hipLaunchKernelGGL((ct_step_kernel<true, OBJ, THR>), dim3(ew_grid(tot / 4)), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, noise, s,
+                       s_ld, out, per_sample, tot);
+  else
+    hipLaunchKernelGGL((ct_step_kernel<false, OBJ, THR>), dim3(ew_grid(tot)), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, noise, s,
+                       s_ld, out, per_sample, tot);
+}
+
+extern "C" int osuf_ct_step_ex(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* noise,
+                               int objective, const float* s, long s_ld, float* out, int B, long per_sample, hipStream_t stream) {
+  if (B <= 0 || per_sample <= 0 || !x || !cond || !coef || !out || objective < 0 || objective > 2 || (s && s_ld < 1)) return OSUF_EINVAL;
+  const long tot = (long)B * per_sample;
+#define OSUF_CT_STEP(OBJ)                                                                                                      \
+  do {                                                                                                                         \
+    if (s) ct_step_launch<OBJ, true>(x, cond, nullp, cond_scale, coef, noise, s, s_ld, out, per_sample, tot, stream);           \
+    else ct_step_launch<OBJ, false>(x, cond, nullp, cond_scale, coef, noise, nullptr, 0, out, per_sample, tot, stream);         \
+  } while (0)
+  if (objective == OSUF_CT_OBJ_NOISE) OSUF_CT_STEP(0);
+  else if (objective == OSUF_CT_OBJ_X_START) OSUF_CT_STEP(1);
+  else OSUF_CT_STEP(2);
+#undef OSUF_CT_STEP
+  return osuf_launch_status();
+}
+
 extern "C" int osuf_ct_step(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* noise,
                             float* out, int B, long per_sample, hipStream_t stream) {
-  if (B <= 0 || per_sample <= 0 || !x || !cond || !coef || !out) return OSUF_EINVAL;
+  return osuf_ct_step_ex(x, cond, nullp, cond_scale, coef, noise, OSUF_CT_OBJ_NOISE, nullptr, 0, out, B, per_sample, stream);
+}
+
+extern "C" long osuf_ct_x0_quantile_workspace_bytes(int B) { return B > 0 ? (long)B * CTQ_WS_PER_SAMPLE * (long)sizeof(unsigned) : 0; }
+
+extern "C" int osuf_ct_x0_quantile(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, int objective,
+                                   long k_lo, float frac, float* out, void* workspace, int B, long per_sample, hipStream_t stream) {
+  if (B <= 0 || B > 65535 || per_sample <= 0 || per_sample > (1L << 30) || !x || !cond || !coef || !out || !workspace || !al16(workspace) ||
+      objective < 0 || objective > 2 || k_lo < 0 || k_lo >= per_sample || !(frac >= 0.f && frac <= 1.f))
+    return OSUF_EINVAL;
+  const unsigned lo = (unsigned)k_lo, hi = (unsigned)(k_lo + 1 < per_sample ? k_lo + 1 : per_sample - 1);
+  unsigned* ws = (unsigned*)workspace;
+  hipError_t e = hipMemsetAsync(ws, 0, (size_t)osuf_ct_x0_quantile_workspace_bytes(B), stream);
+  if (e != hipSuccess) return (int)e;
+  // workgroups per sample: CTQ_CHUNK elements each, at most 2048 in the launch (256 CUs x 8), the rest by striding
+  long G = (per_sample + CTQ_CHUNK - 1) / CTQ_CHUNK;
+  const long cap = 2048 / B > 1 ? 2048 / B : 1;
+  if (G > cap) G = cap;
+  const bool vec = per_sample % 4 == 0 && al16(x) && al16(cond) && (!nullp || al16(nullp));
+  for (int pass = 0; pass < 3; ++pass) {
+    if (vec)
+      hipLaunchKernelGGL(ct_quantile_pass_kernel<true>, dim3((unsigned)G, B), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, objective, lo, hi, ws, per_sample, pass);
+    else
+      hipLaunchKernelGGL(ct_quantile_pass_kernel<false>, dim3((unsigned)G, B), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, objective, lo, hi, ws, per_sample, pass);
+  }
+  hipLaunchKernelGGL(ct_quantile_finish_kernel, dim3(B), dim3(256), 0, stream, ws, lo, hi, frac, out);
+  return osuf_launch_status();
+}
+
+extern "C" int osuf_ct_qsample(const float* x0, const float* noise, const float* sched, int sched_ld, int objective, float* x_noisy,
+                               float* target, int B, long per_sample, hipStream_t stream) {
+  if (B <= 0 || per_sample <= 0 || !x0 || !noise || !sched || sched_ld < 3 || !x_noisy || objective < 0 || objective > 2) return OSUF_EINVAL;
   const long tot = (long)B * per_sample;
-  if (al16(x) && al16(cond) && al16(out) && tot >= 4)
-    hipLaunchKernelGGL(ct_step_kernel<true>, dim3(ew_grid(tot / 4)), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, noise, out, per_sample, tot);
-  else
-    hipLaunchKernelGGL(ct_step_kernel<false>, dim3(ew_grid(tot)), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, noise, out, per_sample, tot);
+  hipLaunchKernelGGL(ct_qsample_kernel, dim3(ew_grid(tot)), dim3(256), 0, stream, x0, noise, sched, sched_ld, objective, x_noisy, target, per_sample, tot);
   return osuf_launch_status();
 }
 
@@ -355,7 +578,15 @@ extern "C" int osuf_mse(const float* pred, const float* target, const int* orig_
                         hipStream_t stream) {
   if (B <= 0 || Dch <= 0 || L <= 0) return OSUF_EINVAL;
   const long tot = (long)B * Dch * L;
-  hipLaunchKernelGGL(mse_kernel, dim3(ew_grid(tot)), dim3(256), 0, stream, pred, target, orig_len, grad, loss_sum, Dch, L, tot);
+  hipLaunchKernelGGL(mse_kernel<false>, dim3(ew_grid(tot)), dim3(256), 0, stream, pred, target, orig_len, nullptr, grad, loss_sum, Dch, L, tot);
+  return osuf_launch_status();
+}
+
+extern "C" int osuf_mse_w(const float* pred, const float* target, const int* orig_len, const float* w, float* grad, double* loss_sum, int B,
+                          int Dch, int L, hipStream_t stream) {
+  if (B <= 0 || Dch <= 0 || L <= 0 || !w) return OSUF_EINVAL;
+  const long tot = (long)B * Dch * L;
+  hipLaunchKernelGGL(mse_kernel<true>, dim3(ew_grid(tot)), dim3(256), 0, stream, pred, target, orig_len, w, grad, loss_sum, Dch, L, tot);
   return osuf_launch_status();
 }
 

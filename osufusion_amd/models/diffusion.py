@@ -55,11 +55,12 @@ class DDIMSchedule:
 
 
 class _MSEFn(torch.autograd.Function):
-    """F.mse_loss(pred, target, 'none') (* length mask).sum() / count   (diffusion.py:101-111) in one pass."""
+    """F.mse_loss(pred, target, 'none') (* length mask).sum() / count   (diffusion.py:101-111) in one pass.  weight (optional, per-sample
+    fp32 (B,), min-SNR-gamma): sum_b w_b sum_{d, l < len_b} (pred - target)^2 over the same count (osuf_mse_w); None is the unweighted loss."""
 
     @staticmethod
-    def forward(ctx, pred, target, orig_len):
-        acc, grad = ops.mse(pred.contiguous(), target.contiguous(), orig_len, pred.requires_grad)
+    def forward(ctx, pred, target, orig_len, weight=None):
+        acc, grad = ops.mse(pred.contiguous(), target.contiguous(), orig_len, pred.requires_grad, weight)
         B, Dc, L = pred.shape
         if orig_len is not None:
             count = orig_len.to(pred.device).clamp(max=L).sum().double() * Dc
@@ -71,7 +72,7 @@ class _MSEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         grad, count = ctx.saved_tensors
-        return grad * (g / count.float()), None, None
+        return grad * (g / count.float()), None, None, None      # (a trailing None for an omitted weight is dropped by autograd)
 
 
 class OsuFusion(nn.Module):

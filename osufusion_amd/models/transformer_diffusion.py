@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import ct, ops
 from .. import runtime as rt
 from ..modules.dit import DiT
 from ..modules.mmdit import MMDiT
@@ -126,14 +126,27 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
 
 
 class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
-    """Continuous-time Gaussian diffusion: noise prediction conditioned on log_snr(t) (scheduler.get_condition), t uniform in [0, 1]."""
+    """Continuous-time Gaussian diffusion: a noise (default), x_start or v prediction conditioned on log_snr(t) (scheduler.get_condition), t
+    uniform in [0, 1]."""
 
     def __init__(self, dim_h: int, backbone: str = "mmdit", cond_drop_prob: float = 0.5, noise_schedule: str = "cosine",
-                 sampling_timesteps: int = 35, **backbone_kwargs) -> None:
+                 sampling_timesteps: int = 35, pred_objective: str = "noise", dynamic_thresholding: bool = False,
+                 dynamic_thresholding_percentile: float = 0.95, min_snr_gamma: Optional[float] = None, **backbone_kwargs) -> None:
+        """pred_objective: what the backbone predicts, "noise" (the default), "x_start" or "v" = alpha noise - sigma x_0.
+        dynamic_thresholding: sample() clamps the start prediction to its per-sample `dynamic_thresholding_percentile` quantile of |x_0|
+        (at least 1) and rescales, instead of the static clamp to [-1, 1].  min_snr_gamma: min-SNR-gamma weighting of the training loss."""
+        if pred_objective not in ct.OBJECTIVES:
+            raise ValueError(f"Unknown prediction objective: {pred_objective!r} (one of {sorted(ct.OBJECTIVES)})")
+        if not 0.0 < dynamic_thresholding_percentile <= 1.0:
+            raise ValueError(f"dynamic_thresholding_percentile must be in (0, 1] (got {dynamic_thresholding_percentile})")
         super().__init__(dim_h, backbone, cond_drop_prob, **backbone_kwargs)
         self.scheduler = GaussianDiffusionContinuousTimes(noise_schedule=noise_schedule, timesteps=sampling_timesteps)
         self.sampling_timesteps = sampling_timesteps
         self.stop_after: Optional[int] = None
+        self.pred_objective = pred_objective
+        self.dynamic_thresholding = bool(dynamic_thresholding)
+        self.dynamic_thresholding_percentile = float(dynamic_thresholding_percentile)
+        self.min_snr_gamma = min_snr_gamma
 
     @torch.inference_mode()
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0) -> torch.Tensor:
@@ -141,7 +154,8 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         ops.ct_step (guidance, start prediction clamped to [-1, 1], posterior mean, noise).  Draws from the global generator, in this order:
         the start iterate torch.randn((B, 6, n)) when x is None, then one torch.randn of the iterate's shape per step, in step order; the
         last step (t_next == 0) adds no noise and draws none.  A plain loop that draws the same way from the same seed sees the same
-        noise.  Bit-reproducible for a given seed.  (Attribute `stop_after` as in DiffusionOsuFusionDiT.)"""
+        noise.  Bit-reproducible for a given seed.  (Attribute `stop_after` as in DiffusionOsuFusionDiT.)  With another pred_objective the
+        step is ops.ct_step_ex; with dynamic_thresholding one ops.ct_x0_quantile goes before it (two launches per step, no extra draw)."""
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
             return self._sample(a, c, x, cond_scale, self.stop_after)
 
@@ -154,12 +168,19 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         times = torch.linspace(1.0, 0.0, total + 1, device=device, dtype=torch.float32)        # get_sampling_timesteps' grid, every pair at once
         coef = self.scheduler.coefficients(times[:-1].repeat_interleave(b), times[1:].repeat_interleave(b)).view(total, b, -1)
         log_snr = coef[:, :, 0].repeat(1, 2 if cfg else 1).contiguous()
+        objective, thresholded = self.pred_objective, self.dynamic_thresholding
+        plain = objective == "noise" and not thresholded
         with self._dtype_ctx():
             f = self._denoiser(a, c, cfg)
             for i in range(steps):
                 pred = f(x, log_snr[i])
                 noise = torch.randn(x.shape, device=device) if i < total - 1 else None
-                x = ops.ct_step(x, pred[:b], pred[b:] if cfg else None, cond_scale, coef[i], noise)
+                cond, null = pred[:b], pred[b:] if cfg else None
+                if not plain:
+                    s = ops.ct_x0_quantile(x, cond, null, cond_scale, coef[i], objective, self.dynamic_thresholding_percentile)[:, 2] if thresholded else None
+                    x = ops.ct_step_ex(x, cond, null, cond_scale, coef[i], noise, objective, s)
+                else:
+                    x = ops.ct_step(x, cond, null, cond_scale, coef[i], noise)
         return x
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -173,9 +194,18 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         """forward() with the RNG draws passed in (parity tests, benchmarks)."""
         p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
         with self._dtype_ctx():
-            x_noisy, log_snr, _, _ = self.scheduler.q_sample(x, times.float(), noise)
+            if self.pred_objective == "noise":
+                x_noisy, log_snr, _, _ = self.scheduler.q_sample(x, times.float(), noise)
+                target = noise.float()
+            else:                                           # x_noisy and the x_start / v target in one pass
+                sched = self.scheduler.coefficients(times.float())
+                x_noisy, target = ops.ct_qsample(x.float().contiguous(), noise.float().contiguous(), sched, self.pred_objective)
+                log_snr = sched[:, ct.LOG_SNR]
             pred = self.unet(x_noisy, a, log_snr.contiguous(), c, cond_drop_prob=p)
-        return _MSEFn.apply(pred, noise.float(), orig_len)
+        weight = self.scheduler.loss_weight(log_snr, self.pred_objective, self.min_snr_gamma)
+        if weight is None:
+            return _MSEFn.apply(pred, target, orig_len)
+        return _MSEFn.apply(pred, target, orig_len, weight.float().contiguous())
 
 
 class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):

@@ -78,3 +78,36 @@ class GaussianDiffusionContinuousTimes(nn.Module):
         k = self.coefficients(t)
         inv_alpha = 1.0 / k[:, ct.ALPHA].clamp(min=1e-8)
         return ops.axpby_rows(x_t.float().contiguous(), noise.float().contiguous(), inv_alpha, -(k[:, ct.SIGMA] * inv_alpha))
+
+    # ---- v / x_start objectives, min-SNR-gamma, dynamic thresholding (imagen-pytorch's formulas; the reference has none of them) ----
+    def predict_start_from_v(self, x_t: torch.Tensor, t: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """x_0 = alpha x_t - sigma v."""
+        rt.require_gpu(x_t)
+        k = self.coefficients(t)
+        return ops.axpby_rows(x_t.float().contiguous(), v.float().contiguous(), k[:, ct.ALPHA].contiguous(), -k[:, ct.SIGMA])
+
+    def calculate_v(self, x_0: torch.Tensor, t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+        """v = alpha noise - sigma x_0."""
+        rt.require_gpu(x_0)
+        k = self.coefficients(t)
+        return ops.axpby_rows(noise.float().contiguous(), x_0.float().contiguous(), k[:, ct.ALPHA].contiguous(), -k[:, ct.SIGMA])
+
+    @staticmethod
+    def loss_weight(log_snr: torch.Tensor, objective: str = "noise", min_snr_gamma: Optional[float] = None) -> Optional[torch.Tensor]:
+        """Min-SNR-gamma weights of the per-sample MSE: with snr = exp(log_snr) and c = min(snr, gamma), c / snr for a noise prediction, c for
+        x_start, c / (snr + 1) for v; None (unweighted) when gamma is None.  Plain torch, any device."""
+        if objective not in ct.OBJECTIVES:
+            raise ValueError(f"Unknown prediction objective: {objective!r} (one of {sorted(ct.OBJECTIVES)})")
+        if min_snr_gamma is None:
+            return None
+        snr = log_snr.exp()
+        c = snr.clamp(max=min_snr_gamma)
+        return {"noise": c / snr, "x_start": c, "v": c / (snr + 1)}[objective]
+
+    @staticmethod
+    def dynamic_threshold(x_0: torch.Tensor, percentile: float = 0.95) -> torch.Tensor:
+        """Imagen 2.3 in plain torch (any device): s = max(1, the per-sample `percentile` quantile of |x_0|), x_0.clamp(-s, s) / s.  What
+        ops.ct_x0_quantile + ops.ct_step_ex do inside the sampler's step without forming x_0."""
+        s = torch.quantile(x_0.abs().reshape(x_0.shape[0], -1), percentile, dim=-1).clamp(min=1.0)
+        s = _pad_to(x_0, s)
+        return x_0.clamp(-s, s) / s

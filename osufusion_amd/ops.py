@@ -701,12 +701,39 @@ def ct_step(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Tensor], c
     return ct.ct_step(x, cond, null, cond_scale, coef, noise)
 
 
-def mse(pred: torch.Tensor, target: torch.Tensor, orig_len: Optional[torch.Tensor], want_grad: bool):
+def ct_step_ex(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Tensor], cond_scale: float, coef: torch.Tensor,
+               noise: Optional[torch.Tensor] = None, objective="noise", s: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ct_step for a "noise" / "x_start" / "v" prediction, with the per-sample dynamic threshold s (B,) in place of the clamp to [-1, 1]
+    when given.  objective "noise" and s None: ct_step, bit for bit."""
+    from . import ct
+    return ct.ct_step_ex(x, cond, null, cond_scale, coef, noise, objective, s)
+
+
+def ct_x0_quantile(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Tensor], cond_scale: float, coef: torch.Tensor,
+                   objective="noise", q: float = 0.95) -> torch.Tensor:
+    """Dynamic thresholding's per-sample quantile of |x0| (x0 = ct_step_ex's unclamped start prediction, never stored) by an exact radix
+    select -> (B, 3) fp32 = the two bracketing order statistics and s = max(1, their linear interpolation at q), torch.quantile's rule."""
+    from . import ct
+    return ct.ct_x0_quantile(x, cond, null, cond_scale, coef, objective, q)
+
+
+def ct_qsample(x_0: torch.Tensor, noise: torch.Tensor, sched: torch.Tensor, objective="noise", want_target: bool = True):
+    """-> (x_noisy = alpha x_0 + sigma noise, the objective's training target) in one pass; sched = ct_schedule's rows at the samples' times."""
+    from . import ct
+    return ct.ct_qsample(x_0, noise, sched, objective, want_target)
+
+
+def mse(pred: torch.Tensor, target: torch.Tensor, orig_len: Optional[torch.Tensor], want_grad: bool, weight: Optional[torch.Tensor] = None):
+    """weight: per-sample fp32 (B,) loss weights (osuf_mse_w); None is osuf_mse."""
     B, Dc, Lx = pred.shape
     grad = torch.empty_like(pred) if want_grad else None
     acc = zeros(1, torch.float64, pred.device)
     ol = orig_len.to(device=pred.device, dtype=torch.int32).contiguous() if orig_len is not None else None
-    call("osuf_mse", _p(pred), _p(target), _p(ol), _p(grad), _p(acc), B, Dc, Lx, _stream())
+    if weight is None:
+        call("osuf_mse", _p(pred), _p(target), _p(ol), _p(grad), _p(acc), B, Dc, Lx, _stream())
+    else:
+        assert weight.dtype == torch.float32 and weight.shape == (B,) and weight.is_contiguous() and weight.device == pred.device
+        call("osuf_mse_w", _p(pred), _p(target), _p(ol), _p(weight), _p(grad), _p(acc), B, Dc, Lx, _stream())
     return acc, grad
 
 
