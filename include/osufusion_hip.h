@@ -318,6 +318,32 @@ int osuf_ct_x0_quantile(const float* x, const float* cond, const float* nullp, f
 long osuf_ct_x0_quantile_workspace_bytes(int B);
 int osuf_ct_qsample(const float* x0, const float* noise, const float* sched, int sched_ld, int objective, float* x_noisy, float* target,
                     int B, long per_sample, hipStream_t stream);
+/* Solvers on the same log-SNR parameterisation (no counterpart in the reference, which samples ancestrally): DDIM(eta), eta in [0, 1]
+ * interpolating to the ancestral sampler, and DPM-Solver++(2M) in data prediction.  Both are
+ *   x_next = k_x x + k_0 x0 + k_p x0_prev + gain z,   x0 = osuf_ct_step_ex's clamped (or thresholded) start prediction.
+ * osuf_ct_solver_schedule: log_snr[steps + 1], a rising fp32 grid (equal neighbours are not checked for: 2M divides by their distance) ->
+ * every step's coefficients in one launch, one thread per step, fp32 without contraction as osuf_ct_schedule:
+ *   rows[steps][B][13]: step i's osuf_ct_schedule row at (log_snr[i], log_snr[i + 1]), REPLICATED for the B samples, so that rows + i * B * 13
+ *     is the coef of osuf_ct_x0_quantile, osuf_ct_step_ex and osuf_ct_solver_step as it stands.  Columns 0-5 and 9 by osuf_ct_schedule's
+ *     expressions; 6-8, 10, 11 the ancestral c, posterior variance and log-variance, and mean factors of that pair; 12 the ancestral noise
+ *     gain, zero on the last step (where osuf_ct_schedule has t_next = 0).
+ *   fac[steps][4] = k_x, k_0, k_p, gain of `sampler`, ONE per step (the grid is the batch's).  With alpha, sigma at log_snr[i], _n at
+ *     log_snr[i + 1], d = log_snr[i] - log_snr[i + 1], h = -d / 2:
+ *     OSUF_CT_SAMPLER_DDIM: gain = sigma_eta = eta sqrt(sigma_n^2 (-expm1(d))), k_eps = sigma_n sqrt((1 - eta^2) + eta^2 exp(d))
+ *       (= sqrt(sigma_n^2 - sigma_eta^2)), k_x = k_eps / sigma, k_0 = alpha_n - k_eps exp(log_snr[i] / 2), k_p = 0.
+ *     OSUF_CT_SAMPLER_DPMPP_2M (eta is not read past its range check): k_d = -alpha_n expm1(-h), k_x = sigma_n / sigma, gain = 0; step 0:
+ *       k_0 = k_d, k_p = 0; step i > 0, r = h_prev / h: k_0 = k_d (1 + 1 / (2r)), k_p = -k_d / (2r).
+ *   OSUF_EINVAL: steps or B < 1, a NULL pointer, eta outside [0, 1]; OSUF_EUNSUPPORTED: another sampler code.
+ * osuf_ct_solver_step: one pass over (B, per_sample) fp32: the guided prediction, x0 as in osuf_ct_step_ex (objective, s, s_ld as there),
+ * then x_next and x0 are both written: x0 is the next step's x0_prev, so a 2M step is one launch.  coef = the step's B rows, fac = its four
+ * factors.  x0_prev is read only when it is given and k_p != 0, noise only when it is given and gain != 0.  x_next and x0 must not overlap
+ * each other or an input.  16-byte aligned buffers take the four-wide path, anything else the scalar one. */
+#define OSUF_CT_SAMPLER_DDIM 0
+#define OSUF_CT_SAMPLER_DPMPP_2M 1
+int osuf_ct_solver_schedule(const float* log_snr, int steps, int sampler, float eta, float* rows, float* fac, int B, hipStream_t stream);
+int osuf_ct_solver_step(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* fac,
+                        const float* x0_prev, const float* noise, int objective, const float* s, long s_ld, float* x_next, float* x0, int B,
+                        long per_sample, hipStream_t stream);
 int osuf_mse(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum, int B, int Dch, int L,
              hipStream_t stream);
 /* osuf_mse with per-sample weights w[B] (min-SNR-gamma): loss_sum += sum_b w[b] sum_{d, l < len_b} (pred - target)^2 and

@@ -164,14 +164,23 @@ __device__ inline float ct_start(float x, float p, const float* k) {
   return (x - k[2] * p) * k[9];
 }
 
+// Classifier-free guidance: the prediction the step takes, from the conditional one and the null one.
+__device__ inline float ct_guide(float cond, float nu, float cond_scale) { return nu + (cond - nu) * cond_scale; }
+
+// The start prediction of the guided prediction p, clamped to [-1, 1] or (THR) to the sample's threshold and rescaled: what the ancestral step
+// and the solver step (below) both take as x0.
+template <int OBJ, bool THR>
+__device__ inline float ct_start_clamped(float x, float p, const float* k, const float* s) {
+  const float x0 = ct_start<OBJ>(x, p, k);
+  if (THR) { const float sv = *s; return fminf(fmaxf(x0, -sv), sv) / sv; }
+  return fminf(fmaxf(x0, -1.f), 1.f);
+}
+
 template <int OBJ, bool THR>
 __device__ inline float ct_step_one(float x, float cond, const float* nullp, const float* noise, long idx, float cond_scale, const float* k,
                                     const float* s) {
-  float eps = cond;
-  if (nullp) { const float nu = nullp[idx]; eps = nu + (eps - nu) * cond_scale; }
-  float x0 = ct_start<OBJ>(x, eps, k);
-  if (THR) { const float sv = *s; x0 = fminf(fmaxf(x0, -sv), sv) / sv; }
-  else x0 = fminf(fmaxf(x0, -1.f), 1.f);
+  const float eps = nullp ? ct_guide(cond, nullp[idx], cond_scale) : cond;
+  const float x0 = ct_start_clamped<OBJ, THR>(x, eps, k, s);
   const float mean = k[10] * x + k[11] * x0;
   const float gain = k[12];
   return (noise && gain != 0.f) ? mean + gain * noise[idx] : mean;
@@ -209,6 +218,119 @@ __global__ __launch_bounds__(256) void ct_step_kernel(const float* x, const floa
     const long b = tail / per_sample;
     out[tail] = ct_step_one<OBJ, THR>(x[tail], cond[tail], nullp, noise, tail, cond_scale, coef + 13 * b, THR ? s + b * s_ld : nullptr);
   }
+}
+
+// ---- solvers on a log-SNR grid: DDIM(eta) and DPM-Solver++(2M) in data prediction -------------------------------------------------------
+// Both are x_next = k_x x + k_0 x0 + k_p x0_prev + gain z, x0 the clamped start prediction (ct_start_clamped).  With lambda = log_snr / 2 and
+// d = ls - ls_next (< 0 on a rising grid), c = -expm1(d), h = -d / 2:
+//   DDIM(eta): sigma_eta = eta sqrt(sigma_n^2 / sigma^2 (1 - alpha^2 / alpha_n^2)) = eta sqrt(sigma_n^2 c)  (alpha^2 / sigma^2 = exp(ls): the
+//     posterior variance), k_eps = sqrt(sigma_n^2 - sigma_eta^2) = sigma_n sqrt((1 - eta^2) + eta^2 exp(d)); k_x = k_eps / sigma,
+//     k_0 = alpha_n - k_eps alpha / sigma with alpha / sigma = exp(ls / 2), gain = sigma_eta.  The right-hand forms are the ones evaluated:
+//     sums of positive terms, where the left-hand ones cancel (1 - alpha^2 / alpha_n^2 at small h, sigma_n^2 - sigma_eta^2 at eta = 1 and
+//     large h).  eta = 0: k_eps = sigma_n exactly.
+//   DPM-Solver++(2M): k_d = -alpha_n expm1(-h), k_x = sigma_n / sigma; first step k_0 = k_d, k_p = 0 (= DDIM(0)); later steps, r = h_prev / h:
+//     k_0 = k_d (1 + 1 / (2r)), k_p = -k_d / (2r).  gain = 0.
+// One thread per step i of the grid ls[0 .. S] (rising; equal neighbours divide by zero in r): the step's 13-column row, written B times
+// (rows[i][b][13], so that osuf_ct_x0_quantile and the step kernels index a step's rows by sample as they do osuf_ct_schedule's), and
+// fac[i][4] = k_x, k_0, k_p, gain, one per step.  Row columns 0-11 by ct_schedule_kernel's expressions on (ls[i], ls[i + 1]); column 12, the
+// ancestral gain, is zero on the last step (where ct_schedule_kernel has t_next = 0): a row is a valid osuf_ct_step_ex row too.
+#define OSUF_CT_SAMPLER_DDIM 0                               // as in include/osufusion_hip.h
+#define OSUF_CT_SAMPLER_DPMPP_2M 1
+__global__ __launch_bounds__(256) void ct_solver_schedule_kernel(const float* ls_grid, int S, int sampler, float eta, float* rows, float* fac,
+                                                                 int B) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S) return;
+  const float ls = ls_grid[i], lsn = ls_grid[i + 1];
+  const float alpha = sqrtf(ct_sigmoid(ls)), sigma = sqrtf(ct_sigmoid(-ls));
+  const float sig2_n = ct_sigmoid(-lsn);
+  const float alpha_n = sqrtf(ct_sigmoid(lsn)), sigma_n = sqrtf(sig2_n);
+  const float d = ls - lsn;
+  const float c = -ct_expm1(d);
+  const float var = (sigma_n * sigma_n) * c;
+  const float logvar = ct_log(fmaxf(var, 1e-20f));
+  const float row[13] = {ls, alpha, sigma, lsn, alpha_n, sigma_n, c, var, logvar, 1.f / fmaxf(alpha, 1e-8f), alpha_n * ((1.f - c) / alpha),
+                         alpha_n * c, i < S - 1 ? ct_exp(0.5f * logvar) : 0.f};
+  for (int b = 0; b < B; ++b) {
+    float* o = rows + ((long)i * B + b) * 13;
+    for (int j = 0; j < 13; ++j) o[j] = row[j];
+  }
+  float k_x, k_0, k_p = 0.f, gain = 0.f;
+  if (sampler == OSUF_CT_SAMPLER_DDIM) {
+    const float e2 = eta * eta;
+    gain = eta * sqrtf(fmaxf(sig2_n * c, 0.f));
+    const float exp_d = ct_exp(ls) * ct_exp(-lsn);         // not ct_exp(d): over a long step d's own rounding (2^-24 |d|) is the error of exp(d)
+    const float k_eps = sigma_n * sqrtf((1.f - e2) + e2 * exp_d);
+    k_x = k_eps / sigma;
+    k_0 = alpha_n - k_eps * ct_exp(0.5f * ls);
+  } else {
+    const float h = 0.5f * (lsn - ls);
+    const float k_d = -(alpha_n * ct_expm1(-h));
+    k_x = sigma_n / sigma;
+    k_0 = k_d;
+    if (i > 0) {
+      const float h_prev = 0.5f * (ls - ls_grid[i - 1]);
+      const float q = (0.5f * h) / h_prev;                 // 1 / (2r)
+      k_0 = k_d * (1.f + q);
+      k_p = -(k_d * q);
+    }
+  }
+  float* f = fac + 4 * (long)i;
+  f[0] = k_x; f[1] = k_0; f[2] = k_p; f[3] = gain;
+}
+
+// One element of the solver step.  p = the guided prediction; prev / z are read by the caller only when they enter (k_p != 0, gain != 0).
+template <int OBJ, bool THR>
+__device__ inline float ct_solver_one(float x, float p, const float* k, const float* s, const float* f, bool use_prev, float prev, bool use_noise,
+                                      float z, float* x0_out) {
+  const float x0 = ct_start_clamped<OBJ, THR>(x, p, k, s);
+  *x0_out = x0;
+  float out = f[0] * x + f[1] * x0;
+  if (use_prev) out += f[2] * prev;
+  if (use_noise) out += f[3] * z;
+  return out;
+}
+
+// ct_step_kernel's layout (VEC: every buffer that is given is 16-byte aligned; a group of four may straddle two samples; scalar tail) with two
+// outputs: x_next and the clamped x0, the next step's x0_prev.  fac = the step's four factors, the same for every sample.
+template <bool VEC, int OBJ, bool THR>
+__global__ __launch_bounds__(256) void ct_solver_step_kernel(const float* x, const float* cond, const float* nullp, float cond_scale,
+                                                             const float* coef, const float* fac, const float* x0_prev, const float* noise,
+                                                             const float* s, long s_ld, float* x_next, float* x0, long per_sample, long total) {
+  const float f[4] = {fac[0], fac[1], fac[2], fac[3]};
+  const bool use_prev = x0_prev && f[2] != 0.f, use_noise = noise && f[3] != 0.f;
+  auto scalar = [&](long idx) {
+    const long b = idx / per_sample;
+    const float p = nullp ? ct_guide(cond[idx], nullp[idx], cond_scale) : cond[idx];
+    x_next[idx] = ct_solver_one<OBJ, THR>(x[idx], p, coef + 13 * b, THR ? s + b * s_ld : nullptr, f, use_prev, use_prev ? x0_prev[idx] : 0.f,
+                                          use_noise, use_noise ? noise[idx] : 0.f, x0 + idx);
+  };
+  if (!VEC) {
+    GRID_STRIDE(idx, total) scalar(idx);
+    return;
+  }
+  const long groups = total >> 2;
+  GRID_STRIDE(g, groups) {
+    const long i0 = g << 2;
+    const long b0 = i0 / per_sample;
+    const long left = (b0 + 1) * per_sample - i0;          // elements of this group's first sample from i0 on (>= 1)
+    const f32x4 xv = reinterpret_cast<const f32x4*>(x)[g], cv = reinterpret_cast<const f32x4*>(cond)[g];
+    f32x4 nv = {0.f, 0.f, 0.f, 0.f}, pv = nv, zv = nv, ov, sv;
+    if (nullp) nv = reinterpret_cast<const f32x4*>(nullp)[g];
+    if (use_prev) pv = reinterpret_cast<const f32x4*>(x0_prev)[g];
+    if (use_noise) zv = reinterpret_cast<const f32x4*>(noise)[g];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const long b = e < left ? b0 : (i0 + e) / per_sample;
+      const float p = nullp ? ct_guide(cv[e], nv[e], cond_scale) : cv[e];
+      float x0e;
+      ov[e] = ct_solver_one<OBJ, THR>(xv[e], p, coef + 13 * b, THR ? s + b * s_ld : nullptr, f, use_prev, pv[e], use_noise, zv[e], &x0e);
+      sv[e] = x0e;
+    }
+    reinterpret_cast<f32x4*>(x_next)[g] = ov;
+    reinterpret_cast<f32x4*>(x0)[g] = sv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (total & 3)) scalar((groups << 2) + threadIdx.x);
 }
 
 // ---- dynamic thresholding (Imagen 2.3): per-sample order statistics of |x0| by an exact radix select ----------------------------------
@@ -538,6 +660,45 @@ extern "C" int osuf_ct_step_ex(const float* x, const float* cond, const float* n
 extern "C" int osuf_ct_step(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* noise,
                             float* out, int B, long per_sample, hipStream_t stream) {
   return osuf_ct_step_ex(x, cond, nullp, cond_scale, coef, noise, OSUF_CT_OBJ_NOISE, nullptr, 0, out, B, per_sample, stream);
+}
+
+extern "C" int osuf_ct_solver_schedule(const float* log_snr, int steps, int sampler, float eta, float* rows, float* fac, int B,
+                                       hipStream_t stream) {
+  if (steps <= 0 || B <= 0 || !log_snr || !rows || !fac || !(eta >= 0.f && eta <= 1.f)) return OSUF_EINVAL;
+  if (sampler != OSUF_CT_SAMPLER_DDIM && sampler != OSUF_CT_SAMPLER_DPMPP_2M) return OSUF_EUNSUPPORTED;
+  hipLaunchKernelGGL(ct_solver_schedule_kernel, dim3((steps + 255) / 256), dim3(256), 0, stream, log_snr, steps, sampler, eta, rows, fac, B);
+  return osuf_launch_status();
+}
+
+template <int OBJ, bool THR>
+static void ct_solver_step_launch(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* fac,
+                                  const float* x0_prev, const float* noise, const float* s, long s_ld, float* x_next, float* x0, long per_sample,
+                                  long tot, hipStream_t stream) {
+  if (al16(x) && al16(cond) && al16(nullp) && al16(x0_prev) && al16(noise) && al16(x_next) && al16(x0) && tot >= 4)      // NULL is aligned
+    hipLaunchKernelGGL((ct_solver_step_kernel<true, OBJ, THR>), dim3(ew_grid(tot / 4)), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, fac,
+                       x0_prev, noise, s, s_ld, x_next, x0, per_sample, tot);
+  else
+    hipLaunchKernelGGL((ct_solver_step_kernel<false, OBJ, THR>), dim3(ew_grid(tot)), dim3(256), 0, stream, x, cond, nullp, cond_scale, coef, fac,
+                       x0_prev, noise, s, s_ld, x_next, x0, per_sample, tot);
+}
+
+extern "C" int osuf_ct_solver_step(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* fac,
+                                   const float* x0_prev, const float* noise, int objective, const float* s, long s_ld, float* x_next, float* x0,
+                                   int B, long per_sample, hipStream_t stream) {
+  if (B <= 0 || per_sample <= 0 || !x || !cond || !coef || !fac || !x_next || !x0 || x_next == x0 || objective < 0 || objective > 2 ||
+      (s && s_ld < 1))
+    return OSUF_EINVAL;
+  const long tot = (long)B * per_sample;
+#define OSUF_CT_SOLVER_STEP(OBJ)                                                                                                            \
+  do {                                                                                                                                      \
+    if (s) ct_solver_step_launch<OBJ, true>(x, cond, nullp, cond_scale, coef, fac, x0_prev, noise, s, s_ld, x_next, x0, per_sample, tot, stream); \
+    else ct_solver_step_launch<OBJ, false>(x, cond, nullp, cond_scale, coef, fac, x0_prev, noise, nullptr, 0, x_next, x0, per_sample, tot, stream); \
+  } while (0)
+  if (objective == OSUF_CT_OBJ_NOISE) OSUF_CT_SOLVER_STEP(0);
+  else if (objective == OSUF_CT_OBJ_X_START) OSUF_CT_SOLVER_STEP(1);
+  else OSUF_CT_SOLVER_STEP(2);
+#undef OSUF_CT_SOLVER_STEP
+  return osuf_launch_status();
 }
 
 extern "C" long osuf_ct_x0_quantile_workspace_bytes(int B) { return B > 0 ? (long)B * CTQ_WS_PER_SAMPLE * (long)sizeof(unsigned) : 0; }

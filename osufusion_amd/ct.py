@@ -1,7 +1,9 @@
 """Continuous-time Gaussian diffusion on the device (osuf_ct_schedule, osuf_ct_step, csrc/elementwise.hip); reached as ops.ct_schedule /
 ops.ct_step.  The allocating wrappers live here, as osufusion_amd/gqa.py's does; their guarded-memory cases are in
 tests/test_scheduler_gpu.py.  Prediction objectives and dynamic thresholding (osuf_ct_step_ex, osuf_ct_x0_quantile, osuf_ct_qsample;
-ops.ct_step_ex / ops.ct_x0_quantile / ops.ct_qsample) follow, guarded in tests/test_ct_objectives_gpu.py."""
+ops.ct_step_ex / ops.ct_x0_quantile / ops.ct_qsample) follow, guarded in tests/test_ct_objectives_gpu.py; then the DDIM / DPM-Solver++(2M)
+solvers on a log-SNR grid (osuf_ct_solver_schedule, osuf_ct_solver_step; ops.ct_solver_schedule / ops.ct_solver_step), guarded in
+tests/test_ct_solver_gpu.py."""
 from __future__ import annotations
 
 import math
@@ -98,6 +100,53 @@ def ct_x0_quantile(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Ten
     ops.call("osuf_ct_x0_quantile", ops._p(x), ops._p(cond), ops._p(null), float(cond_scale), ops._p(coef), objective_code(objective), k_lo,
              frac, ops._p(out), ops._p(ws), B, n, ops._stream())
     return out
+
+
+# solvers on a log-SNR grid (include/osufusion_hip.h: OSUF_CT_SAMPLER_*); "ddpm" is the ancestral path and has no code here
+SAMPLERS = {"ddim": 0, "dpmpp_2m": 1}
+FAC_K_X, FAC_K_0, FAC_K_P, FAC_GAIN = range(4)
+
+
+def sampler_code(sampler) -> int:
+    if sampler in SAMPLERS:
+        return SAMPLERS[sampler]
+    if sampler in SAMPLERS.values() and not isinstance(sampler, bool):
+        return int(sampler)
+    raise ValueError(f"Unknown solver: {sampler!r} (one of {sorted(SAMPLERS)})")
+
+
+def ct_solver_schedule(log_snr: torch.Tensor, sampler="dpmpp_2m", eta: float = 0.0, batch: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """log_snr (S + 1,) fp32, rising -> (rows (S, batch, 13) fp32: step i's schedule row, once per sample, rows[i] being the coef of
+    ct_x0_quantile / ct_solver_step; fac (S, 4) fp32 = k_x, k_0, k_p, gain of x_next = k_x x + k_0 x0 + k_p x0_prev + gain z).  One launch, no
+    host sync."""
+    assert log_snr.dim() == 1 and log_snr.shape[0] >= 2, "the grid is S + 1 log-SNR values"
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta must be in [0, 1] (got {eta})")
+    code = sampler_code(sampler)
+    log_snr = log_snr.float().contiguous()
+    steps, batch = log_snr.shape[0] - 1, int(batch)
+    assert batch >= 1
+    rows = torch.empty((steps, batch, COLS), dtype=torch.float32, device=log_snr.device)
+    fac = torch.empty((steps, 4), dtype=torch.float32, device=log_snr.device)
+    ops.call("osuf_ct_solver_schedule", ops._p(log_snr), steps, code, float(eta), ops._p(rows), ops._p(fac), batch, ops._stream())
+    return rows, fac
+
+
+def ct_solver_step(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Tensor], cond_scale: float, coef: torch.Tensor, fac: torch.Tensor,
+                   x0_prev: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, objective="noise",
+                   s: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One DDIM / DPM-Solver++(2M) step over (B, ...) fp32 contiguous tensors -> (x_next, x0): coef (B, 13) and fac (4,) = rows[i] and fac[i]
+    of ct_solver_schedule; x0 is the clamped (s None) or thresholded start prediction, the x0_prev of the next 2M step.  x0_prev is read
+    only when fac's k_p is non-zero, noise only when its gain is."""
+    _step_args(x, cond, null, noise, coef)
+    assert x0_prev is None or (x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.shape == x.shape)
+    assert fac.dtype == torch.float32 and fac.is_contiguous() and fac.shape == (4,) and fac.device == x.device
+    assert s is None or (s.dtype == torch.float32 and s.shape == (x.shape[0],) and s.device == x.device and (s.stride(0) >= 1 or x.shape[0] == 1))
+    x_next, x0 = torch.empty_like(x), torch.empty_like(x)
+    ops.call("osuf_ct_solver_step", ops._p(x), ops._p(cond), ops._p(null), float(cond_scale), ops._p(coef), ops._p(fac), ops._p(x0_prev),
+             ops._p(noise), objective_code(objective), ops._p(s), max(s.stride(0), 1) if s is not None else 0, ops._p(x_next), ops._p(x0),
+             x.shape[0], x[0].numel(), ops._stream())
+    return x_next, x0
 
 
 def ct_qsample(x_0: torch.Tensor, noise: torch.Tensor, sched: torch.Tensor, objective="noise",

@@ -1,7 +1,8 @@
 """The DiT / MMDiT backbones behind the reference's ``OsuFusion`` interface: ``DiffusionOsuFusionDiT`` mirrors models/diffusion.OsuFusion and
 ``RectifiedFlowOsuFusionDiT`` models/rectified_flow.OsuFusion method for method (``forward`` = training loss, ``loss_with``, ``sample``,
 ``set_full_bf16``).  ``ContinuousDiffusionOsuFusionDiT`` is the same interface on modules/scheduler.GaussianDiffusionContinuousTimes: the
-backbone's time input is the log-SNR, sampling is ancestral (DDPM), one osuf_ct_step per step.  The backbone is stored as ``self.unet``: the reference trainers call ``model.unet.set_gradient_checkpointing`` and write
+backbone's time input is the log-SNR, sampling is ancestral (DDPM, the default), one osuf_ct_step per step, or DDIM / DPM-Solver++(2M) on a
+log-SNR grid, one osuf_ct_solver_step per step.  The backbone is stored as ``self.unet``: the reference trainers call ``model.unet.set_gradient_checkpointing`` and write
 checkpoints with ``unet.``-prefixed keys, so train.py / data.py take these models as they are.
 
 ``sample`` is restructured like the UNet samplers: everything that does not depend on the step -- the audio's embedding rows and
@@ -24,6 +25,7 @@ from .diffusion import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, DDIMSchedule, _MSEFn
 from .rectified_flow import cosmap
 
 BACKBONES = {"mmdit": MMDiT, "dit": DiT}
+SAMPLERS = ("ddpm", "ddim", "dpmpp_2m")                      # of ContinuousDiffusionOsuFusionDiT
 
 
 class _TransformerOsuFusion(nn.Module):
@@ -131,10 +133,20 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
 
     def __init__(self, dim_h: int, backbone: str = "mmdit", cond_drop_prob: float = 0.5, noise_schedule: str = "cosine",
                  sampling_timesteps: int = 35, pred_objective: str = "noise", dynamic_thresholding: bool = False,
-                 dynamic_thresholding_percentile: float = 0.95, min_snr_gamma: Optional[float] = None, **backbone_kwargs) -> None:
+                 dynamic_thresholding_percentile: float = 0.95, min_snr_gamma: Optional[float] = None, sampler: str = "ddpm",
+                 ddim_eta: float = 0.0, solver_spacing: str = "logsnr", solver_logsnr_min: float = -15.0, **backbone_kwargs) -> None:
         """pred_objective: what the backbone predicts, "noise" (the default), "x_start" or "v" = alpha noise - sigma x_0.
         dynamic_thresholding: sample() clamps the start prediction to its per-sample `dynamic_thresholding_percentile` quantile of |x_0|
-        (at least 1) and rescales, instead of the static clamp to [-1, 1].  min_snr_gamma: min-SNR-gamma weighting of the training loss."""
+        (at least 1) and rescales, instead of the static clamp to [-1, 1].  min_snr_gamma: min-SNR-gamma weighting of the training loss.
+        sampler: "ddpm" (the default: ancestral, over the time grid), "ddim" (deterministic at ddim_eta = 0, the ancestral variance at 1) or
+        "dpmpp_2m" (DPM-Solver++(2M), second order, deterministic); the last two run sampling_timesteps steps over
+        scheduler.solver_log_snr_grid(sampling_timesteps, solver_spacing, solver_logsnr_min).  Training does not depend on any of the four."""
+        if sampler not in SAMPLERS:
+            raise ValueError(f"Unknown sampler: {sampler!r} (one of {list(SAMPLERS)})")
+        if not 0.0 <= ddim_eta <= 1.0:
+            raise ValueError(f"ddim_eta must be in [0, 1] (got {ddim_eta})")
+        if solver_spacing not in ("logsnr", "time"):
+            raise ValueError(f"Unknown solver spacing: {solver_spacing!r} (one of ['logsnr', 'time'])")
         if pred_objective not in ct.OBJECTIVES:
             raise ValueError(f"Unknown prediction objective: {pred_objective!r} (one of {sorted(ct.OBJECTIVES)})")
         if not 0.0 < dynamic_thresholding_percentile <= 1.0:
@@ -147,17 +159,52 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         self.dynamic_thresholding = bool(dynamic_thresholding)
         self.dynamic_thresholding_percentile = float(dynamic_thresholding_percentile)
         self.min_snr_gamma = min_snr_gamma
+        self.sampler = sampler
+        self.ddim_eta = float(ddim_eta)
+        self.solver_spacing = solver_spacing
+        self.solver_logsnr_min = float(solver_logsnr_min)
 
     @torch.inference_mode()
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0) -> torch.Tensor:
-        """Ancestral sampling over scheduler.get_sampling_timesteps: per step one denoiser call at log_snr(t) (2B rows with guidance) and one
+        """sampler = "ddpm": ancestral sampling over scheduler.get_sampling_timesteps: per step one denoiser call at log_snr(t) (2B rows with guidance) and one
         ops.ct_step (guidance, start prediction clamped to [-1, 1], posterior mean, noise).  Draws from the global generator, in this order:
         the start iterate torch.randn((B, 6, n)) when x is None, then one torch.randn of the iterate's shape per step, in step order; the
         last step (t_next == 0) adds no noise and draws none.  A plain loop that draws the same way from the same seed sees the same
         noise.  Bit-reproducible for a given seed.  (Attribute `stop_after` as in DiffusionOsuFusionDiT.)  With another pred_objective the
-        step is ops.ct_step_ex; with dynamic_thresholding one ops.ct_x0_quantile goes before it (two launches per step, no extra draw)."""
+        step is ops.ct_step_ex; with dynamic_thresholding one ops.ct_x0_quantile goes before it (two launches per step, no extra draw).
+
+        sampler = "ddim" / "dpmpp_2m": one ops.ct_solver_schedule per call, then per step one denoiser call at the grid's log_snr, one
+        ops.ct_x0_quantile only with dynamic_thresholding, and one ops.ct_solver_step, which also returns the clamped start prediction that
+        the next 2M step takes as x0_prev.  Draws from the global generator, in this order: the start iterate torch.randn((B, 6, n)) when x is
+        None; then, for "ddim" with ddim_eta > 0 only, one torch.randn of the iterate's shape per step, in step order, the last step
+        included (its gain is eta times the ancestral one, not zero: the grid ends at log_snr(0), not at infinity).  "dpmpp_2m" and "ddim" at
+        ddim_eta = 0 draw nothing after the start iterate.  Bit-reproducible; `stop_after` as above."""
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
+            if self.sampler != "ddpm":
+                return self._sample_solver(a, c, x, cond_scale, self.stop_after)
             return self._sample(a, c, x, cond_scale, self.stop_after)
+
+    def _sample_solver(self, a, c, x, cond_scale, stop_after):
+        x = self._start(a, x)
+        b, device = a.shape[0], a.device
+        cfg = cond_scale != 1.0
+        total = self.scheduler.timesteps
+        steps = total if stop_after is None else min(stop_after, total)
+        grid = self.scheduler.solver_log_snr_grid(total, self.solver_spacing, self.solver_logsnr_min, device=device)
+        coef, fac = self.scheduler.solver_coefficients(grid, self.sampler, self.ddim_eta, batch=b)
+        log_snr = grid[:-1, None].repeat(1, 2 * b if cfg else b)
+        objective, q = self.pred_objective, self.dynamic_thresholding_percentile
+        draws = self.sampler == "ddim" and self.ddim_eta > 0.0
+        x0_prev = None
+        with self._dtype_ctx():
+            f = self._denoiser(a, c, cfg)
+            for i in range(steps):
+                pred = f(x, log_snr[i])
+                noise = torch.randn(x.shape, device=device) if draws else None
+                cond, null = pred[:b], pred[b:] if cfg else None
+                s = ops.ct_x0_quantile(x, cond, null, cond_scale, coef[i], objective, q)[:, 2] if self.dynamic_thresholding else None
+                x, x0_prev = ops.ct_solver_step(x, cond, null, cond_scale, coef[i], fac[i], x0_prev, noise, objective, s)
+        return x
 
     def _sample(self, a, c, x, cond_scale, stop_after):
         x = self._start(a, x)

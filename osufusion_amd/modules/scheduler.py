@@ -27,6 +27,7 @@ class GaussianDiffusionContinuousTimes(nn.Module):
         self.noise_schedule = noise_schedule
         self.kind = ct.KINDS[noise_schedule]
         self.timesteps = timesteps
+        self._log_snr_ends: Optional[Tuple[float, float]] = None    # (log_snr(1), log_snr(0)) as the kernel gives them, for solver_log_snr_grid
 
     def coefficients(self, t: torch.Tensor, t_next: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The schedule rows of ops.ct_schedule at t (and t_next), (B, 3) or (B, 13) fp32: what a sampler hands to ops.ct_step."""
@@ -52,6 +53,31 @@ class GaussianDiffusionContinuousTimes(nn.Module):
         times = times[None, :].expand(batch_size, -1)
         times = torch.stack((times[:, :-1], times[:, 1:]), dim=0)
         return times.unbind(dim=-1)
+
+    # ---- DDIM / DPM-Solver++(2M) on a log-SNR grid (the reference samples ancestrally only) ----
+    def solver_log_snr_grid(self, steps: int, spacing: str = "logsnr", logsnr_min: float = -15.0,
+                            device: Union[torch.device, str] = "cuda") -> torch.Tensor:
+        """The solvers' grid, (steps + 1,) fp32 log-SNR values rising from noise to data.  "time": the kernel's log_snr at
+        linspace(1, 0, steps + 1), the ancestral sampler's grid.  "logsnr": torch.linspace from max(log_snr(1), logsnr_min) to log_snr(0),
+        the two ends from osuf_ct_schedule -- the backbone is conditioned on log_snr, so no inverse of the schedule is needed.  At the default
+        logsnr_min = -15 alpha is 5.5e-4: a standard-normal start iterate is the marginal there to within that."""
+        if spacing not in ("logsnr", "time"):
+            raise ValueError(f"Unknown solver spacing: {spacing!r} (one of ['logsnr', 'time'])")
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1 (got {steps})")
+        if spacing == "time":
+            return self.log_snr(torch.linspace(1.0, 0.0, steps + 1, device=device, dtype=torch.float32))
+        if self._log_snr_ends is None:                                              # two constants of the schedule: read back once
+            self._log_snr_ends = tuple(self.log_snr(torch.tensor([1.0, 0.0], device=device, dtype=torch.float32)).tolist())
+        lo, hi = self._log_snr_ends
+        return torch.linspace(max(lo, float(logsnr_min)), hi, steps + 1, device=device, dtype=torch.float32)
+
+    def solver_coefficients(self, grid: torch.Tensor, sampler: str = "dpmpp_2m", eta: float = 0.0,
+                            batch: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """ops.ct_solver_schedule on a grid of solver_log_snr_grid: (rows (S, batch, 13), fac (S, 4)), what a sampler hands to
+        ops.ct_x0_quantile and ops.ct_solver_step step by step."""
+        rt.require_gpu(grid)
+        return ops.ct_solver_schedule(grid, sampler, eta, batch)
 
     def q_posterior(self, x_0: torch.Tensor, x_t: torch.Tensor, t: torch.Tensor,
                     t_next: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

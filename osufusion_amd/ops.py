@@ -717,6 +717,23 @@ def ct_x0_quantile(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Ten
     return ct.ct_x0_quantile(x, cond, null, cond_scale, coef, objective, q)
 
 
+def ct_solver_schedule(log_snr: torch.Tensor, sampler="dpmpp_2m", eta: float = 0.0, batch: int = 1):
+    """A rising fp32 log-SNR grid (S + 1,) -> (rows (S, batch, 13), fac (S, 4)): every step's schedule row (once per sample) and the four
+    factors k_x, k_0, k_p, gain of the "ddim" (eta in [0, 1]) or "dpmpp_2m" update, in one launch.  The allocating wrapper lives in
+    osufusion_amd/ct.py (its guarded-memory cases in tests/test_ct_solver_gpu.py)."""
+    from . import ct
+    return ct.ct_solver_schedule(log_snr, sampler, eta, batch)
+
+
+def ct_solver_step(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Tensor], cond_scale: float, coef: torch.Tensor, fac: torch.Tensor,
+                   x0_prev: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, objective="noise",
+                   s: Optional[torch.Tensor] = None):
+    """One solver step -> (x_next = k_x x + k_0 x0 + k_p x0_prev + gain noise, x0): guidance, start prediction, clamp or threshold as
+    ct_step_ex; coef / fac = rows[i] / fac[i] of ct_solver_schedule.  One launch, two outputs."""
+    from . import ct
+    return ct.ct_solver_step(x, cond, null, cond_scale, coef, fac, x0_prev, noise, objective, s)
+
+
 def ct_qsample(x_0: torch.Tensor, noise: torch.Tensor, sched: torch.Tensor, objective="noise", want_target: bool = True):
     """-> (x_noisy = alpha x_0 + sigma noise, the objective's training target) in one pass; sched = ct_schedule's rows at the samples' times."""
     from . import ct
