@@ -344,6 +344,22 @@ int osuf_ct_solver_schedule(const float* log_snr, int steps, int sampler, float 
 int osuf_ct_solver_step(const float* x, const float* cond, const float* nullp, float cond_scale, const float* coef, const float* fac,
                         const float* x0_prev, const float* noise, int objective, const float* s, long s_ld, float* x_next, float* x0, int B,
                         long per_sample, hipStream_t stream);
+/* Masked generation by replacement conditioning (no counterpart in the reference): the known region of an iterate is overwritten by the
+ * known signal noised to the iterate's own level, in one pass over (B, Dch, L) fp32 contiguous x, known, noise, out.
+ *   mask: fp32 in [0, 1] (not checked), one row of L per sample, broadcast over the Dch channels; sample b's row starts at mask + b * mask_ld,
+ *     mask_ld = 0 is one row shared by all samples.
+ *   levels: a = coef[b * coef_ld + col_a], s = coef[b * coef_ld + col_s], so that rows of osuf_ct_schedule (alpha, sigma in columns 1, 2; the
+ *     pair at t_next in 4, 5), of osuf_ct_solver_schedule (rows + i * B * 13) and the 4-column rows of osuf_ddim_step are read in place.
+ *   tgt = a known + s noise in fp32 without contraction: two products and one sum, three roundings.  noise = NULL: tgt = a known, no noise
+ *     is read.  coef = NULL: tgt = known bit for bit, neither coef nor noise is read.
+ *   out = x where m == 0 and tgt where m == 1, both bit for bit (selects, not arithmetic: known and noise may hold anything, NaN included,
+ *     where m == 0, x anything where m == 1, and -0.0 survives); otherwise out = x + m (tgt - x), three roundings, no contraction.
+ * out == x (in place) is allowed, no other overlap.  One launch over (chunks of Dch * L, B) workgroups, plain vector stores, no allocation,
+ * no host sync, graph-capturable.  The four-wide path is taken when L % 4 == 0 and x, known, noise (when read), mask and out are 16-byte
+ * aligned (with mask_ld % 4 == 0, so that every mask row is); anything else takes the scalar path.
+ * OSUF_EINVAL: a NULL x, known, mask or out; B, Dch or L < 1; mask_ld < 0; with coef given, coef_ld < 1 or a negative column. */
+int osuf_inpaint_blend(const float* x, const float* known, const float* noise, const float* mask, long mask_ld, const float* coef, int coef_ld,
+                       int col_a, int col_s, float* out, int B, int Dch, int L, hipStream_t stream);
 int osuf_mse(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum, int B, int Dch, int L,
              hipStream_t stream);
 /* osuf_mse with per-sample weights w[B] (min-SNR-gamma): loss_sum += sum_b w[b] sum_{d, l < len_b} (pred - target)^2 and

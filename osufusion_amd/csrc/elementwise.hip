@@ -477,6 +477,62 @@ __global__ __launch_bounds__(256) void ct_qsample_kernel(const float* x0, const 
   }
 }
 
+// ---- masked generation: put the known region back at the iterate's noise level (replacement conditioning) ---------------------------------
+// tgt = a known + s noise (two products, one sum, no contraction; a known without noise; known itself without levels), then a select at
+// both ends of the mask: m == 0 keeps x, m == 1 takes tgt, anything between is x + m (tgt - x).  The ends being selects, not arithmetic,
+// whatever lies under the other end (NaN included) never reaches the result and -0.0 survives.
+__device__ inline float inpaint_one(float x, float known, float z, float m, float a, float s, bool levels, bool noisy) {
+#pragma clang fp contract(off)
+  if (m == 0.f) return x;
+  float tgt = known;
+  if (levels) {
+    tgt = a * known;
+    if (noisy) {
+      const float sz = s * z;
+      tgt = tgt + sz;
+    }
+  }
+  if (m == 1.f) return tgt;
+  const float d = tgt - x;
+  const float md = m * d;
+  return x + md;
+}
+
+// grid (chunks of Dch * L, samples); sample b's mask row is mask + b * mask_ld (0: one row for all), broadcast over the Dch channels; its
+// levels are coef[b * coef_ld + col_a] and [+ col_s].  VEC: L % 4 == 0 and every buffer (each mask row too) 16-byte aligned, so a group of
+// four lies within one row of L; out == x is fine (every lane reads its own elements before it writes them).
+template <bool VEC>
+__global__ __launch_bounds__(256) void inpaint_blend_kernel(const float* x, const float* known, const float* noise, const float* mask, long mask_ld,
+                                                            const float* coef, int coef_ld, int col_a, int col_s, float* out, int B, int L,
+                                                            long per_sample) {
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const float a = coef ? coef[(long)b * coef_ld + col_a] : 1.f;
+    const float s = (coef && noise) ? coef[(long)b * coef_ld + col_s] : 0.f;
+    const float* mrow = mask + b * mask_ld;
+    const long base = b * per_sample;
+    const bool levels = coef != nullptr, noisy = noise != nullptr;
+    if (VEC) {
+      const long groups = per_sample >> 2;
+      GRID_STRIDE(g, groups) {
+        const long i0 = g << 2;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + base + i0), kv = *reinterpret_cast<const f32x4*>(known + base + i0);
+        const f32x4 mv = *reinterpret_cast<const f32x4*>(mrow + i0 % L);
+        f32x4 zv = {0.f, 0.f, 0.f, 0.f};
+        if (levels && noisy) zv = *reinterpret_cast<const f32x4*>(noise + base + i0);
+        f32x4 ov;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ov[e] = inpaint_one(xv[e], kv[e], zv[e], mv[e], a, s, levels, noisy);
+        *reinterpret_cast<f32x4*>(out + base + i0) = ov;
+      }
+    } else {
+      GRID_STRIDE(i, per_sample) {
+        const float z = (levels && noisy) ? noise[base + i] : 0.f;
+        out[base + i] = inpaint_one(x[base + i], known[base + i], z, mrow[i % L], a, s, levels, noisy);
+      }
+    }
+  }
+}
+
 // masked MSE: loss_sum += sum w*(pred-target)^2 (double), grad = 2*w*(pred-target)  (scaled by 1/count later)
 // WEIGHTED: w is the length mask times the sample's loss weight wt[b] (min-SNR-gamma); a weight of one leaves every bit as it was.
 template <bool WEIGHTED>
@@ -732,6 +788,22 @@ extern "C" int osuf_ct_qsample(const float* x0, const float* noise, const float*
   if (B <= 0 || per_sample <= 0 || !x0 || !noise || !sched || sched_ld < 3 || !x_noisy || objective < 0 || objective > 2) return OSUF_EINVAL;
   const long tot = (long)B * per_sample;
   hipLaunchKernelGGL(ct_qsample_kernel, dim3(ew_grid(tot)), dim3(256), 0, stream, x0, noise, sched, sched_ld, objective, x_noisy, target, per_sample, tot);
+  return osuf_launch_status();
+}
+
+extern "C" int osuf_inpaint_blend(const float* x, const float* known, const float* noise, const float* mask, long mask_ld, const float* coef,
+                                  int coef_ld, int col_a, int col_s, float* out, int B, int Dch, int L, hipStream_t stream) {
+  if (!x || !known || !mask || !out || B < 1 || Dch < 1 || L < 1 || mask_ld < 0) return OSUF_EINVAL;
+  if (coef && (coef_ld < 1 || col_a < 0 || col_s < 0)) return OSUF_EINVAL;
+  const long per_sample = (long)Dch * L;
+  const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
+  const bool vec = (L & 3) == 0 && (mask_ld & 3) == 0 && al16(x) && al16(known) && al16(mask) && al16(out) && (!noise || !coef || al16(noise));
+  if (vec)
+    hipLaunchKernelGGL(inpaint_blend_kernel<true>, dim3(ew_grid(per_sample / 4), gy), dim3(256), 0, stream, x, known, noise, mask, mask_ld, coef,
+                       coef_ld, col_a, col_s, out, B, L, per_sample);
+  else
+    hipLaunchKernelGGL(inpaint_blend_kernel<false>, dim3(ew_grid(per_sample), gy), dim3(256), 0, stream, x, known, noise, mask, mask_ld, coef,
+                       coef_ld, col_a, col_s, out, B, L, per_sample);
   return osuf_launch_status();
 }
 

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F  # noqa: N812
 
-from .. import ops
+from .. import inpaint, ops
 from .. import runtime as rt
 from ..modules.unet import UNet
 
@@ -109,11 +109,26 @@ class OsuFusion(nn.Module):
         """diffusion.py:59-77.  Same outputs, restructured: the audio code is computed once (it does not depend on t or x),
         the conditional and null branches of classifier-free guidance run as one batch of 2B, and the guidance combine is
         fused into the DDIM-step kernel.  (Attribute `stop_after`, None by default and absent from the reference: return the
-        iterate after that many of the sampling_timesteps steps -- lets tests check single steps of a long schedule.)"""
+        iterate after that many of the sampling_timesteps steps -- lets tests check single steps of a long schedule.)  The signature is
+        the reference's (tests/test_host_logic.py holds it there); masked generation is `sample_masked`."""
         with ops.reproducible_mode(self.reproducible_sampling):
             return self._sample(a, c, x, cond_scale, self.stop_after)
 
-    def _sample(self, a, c, x, cond_scale, stop_after):
+    @torch.inference_mode()
+    def sample_masked(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
+                      known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """sample() with the keywords the transformer models' sample() takes (the reference's signature of sample() is kept as it is).
+        known (B, 6, n) and known_mask ((n,), (B, n) or (B, 1, n); 1 / True = keep), both or neither: masked generation by replacement
+        conditioning (osufusion_amd/inpaint.py).  The iterate handed to the UNet has its known region at its own level: one
+        ops.inpaint_blend of the start iterate at columns (1, 0) of the first coefficient row, one after every step at columns (2, 3) of the
+        step's row, and after the final step of a full run the exact blend, so that the result holds `known` bit for bit where the mask is
+        1.  The noise is one fixed tensor, a clone of the start iterate: nothing new is drawn.  Under use_hip_graph the blend is launched
+        eagerly after each replay.  With both None: no extra launch, the bits of the unmasked sampler."""
+        masked = inpaint.check_pair(known, known_mask)
+        with ops.reproducible_mode(self.reproducible_sampling):
+            return self._sample(a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None)
+
+    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None):
         (b, _, n), device = a.shape, a.device
         rt.require_gpu(a)
         if x is None:
@@ -141,6 +156,10 @@ class OsuFusion(nn.Module):
             coef_table = torch.tensor([[self.scheduler.step_coefficients(t)] * b for t in steps], dtype=torch.float32, device=device)
             t_table = torch.tensor([[t] * nb for t in steps], dtype=torch.int64, device=device)
             x_buf, t_buf, coef_buf = x.clone(), t_table[0].clone(), coef_table[0].clone()
+            total = self.sampling_timesteps
+            blender = inpaint.Blender(*keep_region, x_buf, fresh=False) if keep_region is not None else None
+            if blender is not None and len(steps) > 0:
+                blender.level(x_buf, coef_table[0], 1, 0, out=x_buf)
 
             def one_step() -> None:                      # reads x_buf / t_buf / coef_buf, writes x_buf (static buffers)
                 xin = torch.cat([x_buf, x_buf], 0) if cfg else x_buf
@@ -155,15 +174,20 @@ class OsuFusion(nn.Module):
                     coef_buf.copy_(coef_table[i])
                 if graph is not None:
                     graph.replay()
-                    continue
-                one_step()                               # eager (also warms pack caches / RoPE tables before a capture)
-                if self.use_hip_graph and i == 0 and len(steps) > 1:
-                    torch.cuda.synchronize()
-                    graph = torch.cuda.CUDAGraph()
-                    keep_x = x_buf.clone()
-                    with torch.cuda.graph(graph):        # capture records the launches only; x_buf is restored below
-                        one_step()
-                    x_buf.copy_(keep_x)
+                else:
+                    one_step()                           # eager (also warms pack caches / RoPE tables before a capture)
+                    if self.use_hip_graph and i == 0 and len(steps) > 1:
+                        torch.cuda.synchronize()
+                        graph = torch.cuda.CUDAGraph()
+                        keep_x = x_buf.clone()
+                        with torch.cuda.graph(graph):    # capture records the launches only; x_buf is restored below
+                            one_step()
+                        x_buf.copy_(keep_x)
+                if blender is not None:                  # outside the captured step: eager and replay issue the same sequence
+                    if i == total - 1:
+                        blender.exact(x_buf, out=x_buf)
+                    else:
+                        blender.level(x_buf, coef_table[i], 2, 3, out=x_buf)
             x = x_buf
         return x
 

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F  # noqa: N812
 
-from .. import ops
+from .. import inpaint, ops
 from .. import runtime as rt
 from ..modules.unet import UNet
 from .diffusion import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, _MSEFn
@@ -21,6 +21,37 @@ from .diffusion import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, _MSEFn
 def cosmap(t: torch.Tensor) -> torch.Tensor:
     """rectified_flow.py:15-16."""
     return 1.0 - (1.0 / (torch.tan(math.pi / 2 * t) + 1))
+
+
+def flow_levels(times, b: int, device) -> torch.Tensor:
+    """The levels a masked midpoint loop over `times` blends at, fp32 (1 + 2 (S - 1), b, 2) = (t, 1 - t) per sample: row 0 the start
+    (times[0]), then per interval its midpoint t0 + dt / 2 and its end t1.  Built once per call; t and 1 - t are python floats rounded to fp32."""
+    ts = [times[0]]
+    for t0, t1 in zip(times[:-1], times[1:]):
+        ts += [t0 + 0.5 * (t1 - t0), t1]
+    return torch.tensor([[[t, 1.0 - t]] * b for t in ts], dtype=torch.float32, device=device)
+
+
+def midpoint_loop(f, x: torch.Tensor, times, ones: torch.Tensor, keep_region=None) -> torch.Tensor:
+    """The fixed-grid midpoint loop of both flow samplers over f(t, y) -> the guided flow.  keep_region = (known, known_mask): every state
+    handed to f is blended at its own time, the end of the last interval exactly; None issues the unmasked loop's launches and nothing else."""
+    blender = None
+    if keep_region is not None:
+        blender = inpaint.Blender(*keep_region, x, fresh=False)
+        levels = flow_levels(times, x.shape[0], x.device)
+        x = blender.level(x, levels[0], 0, 1)
+    last = len(times) - 2
+    for j, (t0, t1) in enumerate(zip(times[:-1], times[1:])):
+        dt = t1 - t0
+        k1 = f(t0, x)
+        mid = ops.axpby_rows(x, k1, ones, ones * (0.5 * dt))
+        if blender is not None:
+            mid = blender.level(mid, levels[1 + 2 * j], 0, 1)
+        k2 = f(t0 + 0.5 * dt, mid)
+        x = ops.axpby_rows(x, k2, ones, ones * dt)
+        if blender is not None:
+            x = blender.exact(x) if j == last else blender.level(x, levels[2 + 2 * j], 0, 1)
+    return x
 
 
 class OsuFusion(nn.Module):
@@ -47,11 +78,25 @@ class OsuFusion(nn.Module):
     @torch.inference_mode()
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0) -> torch.Tensor:
         """rectified_flow.py:57-79.  Same restructuring as the DDIM sampler: audio code computed once, conditional + null
-        branches as one batch of 2B; 2 * (S - 1) UNet evaluations.  Bit-reproducible (ops.reproducible_mode), as the DDIM sampler."""
+        branches as one batch of 2B; 2 * (S - 1) UNet evaluations.  Bit-reproducible (ops.reproducible_mode), as the DDIM sampler.  The
+        signature is the reference's (tests/test_host_logic.py holds it there); masked generation is `sample_masked`."""
         with ops.reproducible_mode(True):
             return self._sample(a, c, x, cond_scale)
 
-    def _sample(self, a, c, x, cond_scale):
+    @torch.inference_mode()
+    def sample_masked(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0,
+                      known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """sample() with the keywords the transformer models' sample() takes (the reference's signature of sample() is kept as it is).
+        known (B, 6, n) and known_mask ((n,), (B, n) or (B, 1, n); 1 / True = keep), both or neither: masked generation (flow_levels,
+        osufusion_amd/inpaint.py).  The iterate at ODE time t is t x_0 + (1 - t) noise -- the sampler's own state, not the cosmap position of
+        training -- so every state handed to the UNet is blended at (t, 1 - t): the start iterate at (0, 1), the midpoint state at
+        t0 + dt / 2, the end of an interval at t1, and the end of the last interval by the exact blend (`known` bit for bit where the mask is
+        1).  The noise is one fixed tensor, a clone of the start iterate: nothing new is drawn.  With both None: the unmasked sampler's bits."""
+        masked = inpaint.check_pair(known, known_mask)
+        with ops.reproducible_mode(True):
+            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None)
+
+    def _sample(self, a, c, x, cond_scale, keep_region=None):
         (b, _, n), device = a.shape, a.device
         rt.require_gpu(a)
         if x is None:
@@ -82,11 +127,7 @@ class OsuFusion(nn.Module):
                 return out
 
             times = torch.linspace(0.0, 1.0, self.sample_timesteps).tolist()
-            for t0, t1 in zip(times[:-1], times[1:]):
-                dt = t1 - t0
-                k1 = f(t0, x)
-                k2 = f(t0 + 0.5 * dt, ops.axpby_rows(x, k1, ones, ones * (0.5 * dt)))
-                x = ops.axpby_rows(x, k2, ones, ones * dt)
+            x = midpoint_loop(f, x, times, ones, keep_region)
         return x
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -8,21 +8,22 @@ checkpoints with ``unet.``-prefixed keys, so train.py / data.py take these model
 ``sample`` is restructured like the UNet samplers: everything that does not depend on the step -- the audio's embedding rows and
 where(keep, mlp_cond(c), null_cond) + mlp_a(feature_extractor_a(stat_pool(a))) -- is computed once per call, the conditional and null
 branches of classifier-free guidance run as one batch of 2B, the guidance combine rides the DDIM-step kernel, and the attention forward of
-every block is one launch over all K/V groups (ops.one_launch_attention -> osuf_gqa_fwd).  Not here: hipGraph capture of the step, LoRA
-on these backbones.
+every block is one launch over all K/V groups (ops.one_launch_attention -> osuf_gqa_fwd).  Every ``sample`` takes ``known`` / ``known_mask``:
+masked generation by replacement conditioning, one ops.inpaint_blend per iterate handed to the denoiser (osufusion_amd/inpaint.py), with
+RePaint resampling on the ancestral sampler.  Not here: hipGraph capture of the step, LoRA on these backbones.
 """
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
-from .. import ct, ops
+from .. import ct, inpaint, ops
 from .. import runtime as rt
 from ..modules.dit import DiT
 from ..modules.mmdit import MMDiT
 from ..modules.scheduler import GaussianDiffusionContinuousTimes
 from .diffusion import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, DDIMSchedule, _MSEFn
-from .rectified_flow import cosmap
+from .rectified_flow import cosmap, midpoint_loop
 
 BACKBONES = {"mmdit": MMDiT, "dit": DiT}
 SAMPLERS = ("ddpm", "ddim", "dpmpp_2m")                      # of ContinuousDiffusionOsuFusionDiT
@@ -87,13 +88,20 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
         self.stop_after: Optional[int] = None
 
     @torch.inference_mode()
-    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0) -> torch.Tensor:
+    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
+               known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """diffusion.py:59-77 on the transformer backbones.  Bit-reproducible.  (Attribute `stop_after`, None by default: return the iterate
-        after that many of the sampling_timesteps steps, as models/diffusion.OsuFusion.)"""
-        with ops.reproducible_mode(True), ops.one_launch_attention(True):
-            return self._sample(a, c, x, cond_scale, self.stop_after)
+        after that many of the sampling_timesteps steps, as models/diffusion.OsuFusion.)
 
-    def _sample(self, a, c, x, cond_scale, stop_after):
+        known (B, 6, n) and known_mask ((n,), (B, n) or (B, 1, n); 1 / True = keep), both or neither: masked generation as in
+        models/diffusion.OsuFusion.sample_masked -- the start iterate blended at columns (1, 0) of the first coefficient row, every step's result at
+        columns (2, 3) of its row, the final step of a full run exactly; one fixed noise tensor (a clone of the start iterate), no new draw.
+        With both None: no extra launch, the unmasked sampler's bits."""
+        masked = inpaint.check_pair(known, known_mask)
+        with ops.reproducible_mode(True), ops.one_launch_attention(True):
+            return self._sample(a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None)
+
+    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None):
         x_buf = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
@@ -106,9 +114,14 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
             f = self._denoiser(a, c, cfg)
             coef_table = torch.tensor([[self.scheduler.step_coefficients(t)] * b for t in steps], dtype=torch.float32, device=device)
             t_table = torch.tensor([[t] * nb for t in steps], dtype=torch.int64, device=device)
+            blender = inpaint.Blender(*keep_region, x_buf, fresh=False) if keep_region is not None else None
+            if blender is not None and len(steps) > 0:
+                x_buf = blender.level(x_buf, coef_table[0], 1, 0)
             for i in range(len(steps)):
                 pred = f(x_buf, t_table[i])
                 x_buf = ops.ddim_step(x_buf, pred[:b], pred[b:] if cfg else None, cond_scale, coef_table[i])
+                if blender is not None:
+                    x_buf = blender.exact(x_buf) if i == self.sampling_timesteps - 1 else blender.level(x_buf, coef_table[i], 2, 3)
         return x_buf
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -165,7 +178,8 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         self.solver_logsnr_min = float(solver_logsnr_min)
 
     @torch.inference_mode()
-    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0) -> torch.Tensor:
+    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
+               known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None, resample: int = 1) -> torch.Tensor:
         """sampler = "ddpm": ancestral sampling over scheduler.get_sampling_timesteps: per step one denoiser call at log_snr(t) (2B rows with guidance) and one
         ops.ct_step (guidance, start prediction clamped to [-1, 1], posterior mean, noise).  Draws from the global generator, in this order:
         the start iterate torch.randn((B, 6, n)) when x is None, then one torch.randn of the iterate's shape per step, in step order; the
@@ -178,13 +192,36 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         the next 2M step takes as x0_prev.  Draws from the global generator, in this order: the start iterate torch.randn((B, 6, n)) when x is
         None; then, for "ddim" with ddim_eta > 0 only, one torch.randn of the iterate's shape per step, in step order, the last step
         included (its gain is eta times the ancestral one, not zero: the grid ends at log_snr(0), not at infinity).  "dpmpp_2m" and "ddim" at
-        ddim_eta = 0 draw nothing after the start iterate.  Bit-reproducible; `stop_after` as above."""
+        ddim_eta = 0 draw nothing after the start iterate.  Bit-reproducible; `stop_after` as above.
+
+        known (B, 6, n) and known_mask ((n,), (B, n) or (B, 1, n); 1 / True = keep), both or neither: masked generation by replacement
+        conditioning (osufusion_amd/inpaint.py).  Every iterate handed to the denoiser has its known region at its own level,
+        alpha known + sigma noise: one ops.inpaint_blend of the start iterate at columns (1, 2) of the first schedule row, one after every step
+        at columns (4, 5) of the step's row, and after the final step of a full run the exact blend (`known` bit for bit where the mask is 1;
+        a run cut short by `stop_after` ends on a level blend).  "dpmpp_2m" and "ddim" at ddim_eta = 0 take one fixed noise tensor, a clone of
+        the start iterate, and draw nothing new; the x0_prev of a 2M step stays as the step kernel wrote it.  "ddpm" and "ddim" with
+        ddim_eta > 0 draw a fresh torch.randn of the iterate's shape per level blend, which extends the order above: the start iterate, then
+        the start blend's noise; then per step the step's own noise (where it draws one) and after it the noise of that step's level blend.
+        The exact blend draws nothing.  With both None: no extra launch, no extra draw, the bits of the unmasked sampler.
+
+        resample = r > 1 (RePaint's resampling; "ddpm" with a known region only): every step but the final one of a full run is taken r
+        times.  After pass u < r - 1 (the step, then its level blend) the whole iterate goes back one level by the exact forward transition
+        x = k_r x + k_g z through ops.axpby_rows, z a fresh torch.randn, the last draw of that pass, with per sample
+        k_r = alpha / alpha_next and k_g = sigma sqrt(c) (columns 1, 4 and 2, 6 of the step's row; sigma^2 - k_r^2 sigma_next^2 = sigma^2 c, so
+        nothing cancels), computed in fp32 torch once per call.  r (S - 1) + 1 denoiser calls for S steps."""
+        masked = inpaint.check_pair(known, known_mask)
+        resample = int(resample)
+        if resample < 1:
+            raise ValueError(f"resample must be >= 1 (got {resample})")
+        if resample > 1 and (self.sampler != "ddpm" or not masked):
+            raise ValueError('resample > 1 needs sampler == "ddpm" and a known region (known, known_mask)')
+        keep_region = (known, known_mask) if masked else None
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
             if self.sampler != "ddpm":
-                return self._sample_solver(a, c, x, cond_scale, self.stop_after)
-            return self._sample(a, c, x, cond_scale, self.stop_after)
+                return self._sample_solver(a, c, x, cond_scale, self.stop_after, keep_region)
+            return self._sample(a, c, x, cond_scale, self.stop_after, keep_region, resample)
 
-    def _sample_solver(self, a, c, x, cond_scale, stop_after):
+    def _sample_solver(self, a, c, x, cond_scale, stop_after, keep_region=None):
         x = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
@@ -196,6 +233,9 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         objective, q = self.pred_objective, self.dynamic_thresholding_percentile
         draws = self.sampler == "ddim" and self.ddim_eta > 0.0
         x0_prev = None
+        blender = inpaint.Blender(*keep_region, x, fresh=draws) if keep_region is not None else None
+        if blender is not None and steps > 0:
+            x = blender.level(x, coef[0], ct.ALPHA, ct.SIGMA)
         with self._dtype_ctx():
             f = self._denoiser(a, c, cfg)
             for i in range(steps):
@@ -204,9 +244,11 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
                 cond, null = pred[:b], pred[b:] if cfg else None
                 s = ops.ct_x0_quantile(x, cond, null, cond_scale, coef[i], objective, q)[:, 2] if self.dynamic_thresholding else None
                 x, x0_prev = ops.ct_solver_step(x, cond, null, cond_scale, coef[i], fac[i], x0_prev, noise, objective, s)
+                if blender is not None:
+                    x = blender.exact(x) if i == total - 1 else blender.level(x, coef[i], ct.ALPHA_NEXT, ct.SIGMA_NEXT)
         return x
 
-    def _sample(self, a, c, x, cond_scale, stop_after):
+    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None, resample=1):
         x = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
@@ -217,17 +259,29 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         log_snr = coef[:, :, 0].repeat(1, 2 if cfg else 1).contiguous()
         objective, thresholded = self.pred_objective, self.dynamic_thresholding
         plain = objective == "noise" and not thresholded
+        blender = inpaint.Blender(*keep_region, x, fresh=True) if keep_region is not None else None
+        if blender is not None and steps > 0:
+            x = blender.level(x, coef[0], ct.ALPHA, ct.SIGMA)
+        if resample > 1:                                    # the forward transition from a step's level back to the level it left
+            k_r = (coef[:, :, ct.ALPHA] / coef[:, :, ct.ALPHA_NEXT]).contiguous()
+            k_g = (coef[:, :, ct.SIGMA] * torch.sqrt(coef[:, :, ct.C])).contiguous()
         with self._dtype_ctx():
             f = self._denoiser(a, c, cfg)
             for i in range(steps):
-                pred = f(x, log_snr[i])
-                noise = torch.randn(x.shape, device=device) if i < total - 1 else None
-                cond, null = pred[:b], pred[b:] if cfg else None
-                if not plain:
-                    s = ops.ct_x0_quantile(x, cond, null, cond_scale, coef[i], objective, self.dynamic_thresholding_percentile)[:, 2] if thresholded else None
-                    x = ops.ct_step_ex(x, cond, null, cond_scale, coef[i], noise, objective, s)
-                else:
-                    x = ops.ct_step(x, cond, null, cond_scale, coef[i], noise)
+                passes = resample if i < total - 1 else 1
+                for u in range(passes):
+                    pred = f(x, log_snr[i])
+                    noise = torch.randn(x.shape, device=device) if i < total - 1 else None
+                    cond, null = pred[:b], pred[b:] if cfg else None
+                    if not plain:
+                        s = ops.ct_x0_quantile(x, cond, null, cond_scale, coef[i], objective, self.dynamic_thresholding_percentile)[:, 2] if thresholded else None
+                        x = ops.ct_step_ex(x, cond, null, cond_scale, coef[i], noise, objective, s)
+                    else:
+                        x = ops.ct_step(x, cond, null, cond_scale, coef[i], noise)
+                    if blender is not None:
+                        x = blender.exact(x) if i == total - 1 else blender.level(x, coef[i], ct.ALPHA_NEXT, ct.SIGMA_NEXT)
+                    if u < passes - 1:
+                        x = ops.axpby_rows(x, torch.randn(x.shape, device=device), k_r[i], k_g[i])
         return x
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -262,12 +316,16 @@ class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
         self.sample_timesteps = sampling_timesteps
 
     @torch.inference_mode()
-    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0) -> torch.Tensor:
-        """rectified_flow.py:57-79 on the transformer backbones: the fixed-grid midpoint loop, 2 * (S - 1) evaluations.  Bit-reproducible."""
+    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0,
+               known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rectified_flow.py:57-79 on the transformer backbones: the fixed-grid midpoint loop, 2 * (S - 1) evaluations.  Bit-reproducible.
+        known / known_mask (both or neither): masked generation as in models/rectified_flow.OsuFusion.sample_masked -- every state handed to the
+        backbone blended at (t, 1 - t), the end of the last interval exactly, one fixed noise tensor, no new draw."""
+        masked = inpaint.check_pair(known, known_mask)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
-            return self._sample(a, c, x, cond_scale)
+            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None)
 
-    def _sample(self, a, c, x, cond_scale):
+    def _sample(self, a, c, x, cond_scale, keep_region=None):
         x = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
@@ -282,11 +340,7 @@ class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
                 return out
 
             times = torch.linspace(0.0, 1.0, self.sample_timesteps).tolist()
-            for t0, t1 in zip(times[:-1], times[1:]):
-                dt = t1 - t0
-                k1 = f(t0, x)
-                k2 = f(t0 + 0.5 * dt, ops.axpby_rows(x, k1, ones, ones * (0.5 * dt)))
-                x = ops.axpby_rows(x, k2, ones, ones * dt)
+            x = midpoint_loop(f, x, times, ones, keep_region)
         return x
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:

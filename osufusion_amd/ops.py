@@ -740,6 +740,15 @@ def ct_qsample(x_0: torch.Tensor, noise: torch.Tensor, sched: torch.Tensor, obje
     return ct.ct_qsample(x_0, noise, sched, objective, want_target)
 
 
+def inpaint_blend(x: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, coef: Optional[torch.Tensor] = None, col_a: int = 0, col_s: int = 1,
+                  noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Masked generation's one pass: the region where mask == 1 becomes coef[b, col_a] known + coef[b, col_s] noise (known itself with coef
+    None), the region where mask == 0 stays x, both bit for bit; a soft mask interpolates.  The allocating wrapper lives in
+    osufusion_amd/inpaint.py (its guarded-memory cases in tests/test_inpaint_gpu.py)."""
+    from . import inpaint
+    return inpaint.inpaint_blend(x, known, mask, coef, col_a, col_s, noise, out)
+
+
 def mse(pred: torch.Tensor, target: torch.Tensor, orig_len: Optional[torch.Tensor], want_grad: bool, weight: Optional[torch.Tensor] = None):
     """weight: per-sample fp32 (B,) loss weights (osuf_mse_w); None is osuf_mse."""
     B, Dc, Lx = pred.shape
