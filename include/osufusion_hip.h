@@ -360,6 +360,23 @@ int osuf_ct_solver_step(const float* x, const float* cond, const float* nullp, f
  * OSUF_EINVAL: a NULL x, known, mask or out; B, Dch or L < 1; mask_ld < 0; with coef given, coef_ld < 1 or a negative column. */
 int osuf_inpaint_blend(const float* x, const float* known, const float* noise, const float* mask, long mask_ld, const float* coef, int coef_ld,
                        int col_a, int col_s, float* out, int B, int Dch, int L, hipStream_t stream);
+/* Windowed sampling (osufusion_amd/windowed.py): a sequence of n >= window frames is cut into W = ceil((n - window) / stride) + 1 windows
+ * of exactly `window` frames, 1 <= stride <= window; window j starts at s_j = min(j * stride, n - window), so only the last start is
+ * clamped and the last window may overlap its predecessor by more than window - stride.
+ *   osuf_window_gather: src fp32 (R, D, n) -> out fp32 (R * W, D, window), out[r * W + j, d, i] = src[r, d, s_j + i], a copy of bits.
+ *   osuf_window_fuse: pred fp32 (R * W, D, window), weight fp32 (window), every weight > 0 (not checked) -> out fp32 (R, D, n), a tapered,
+ *     normalised overlap-add.  For frame l let J(l) be the windows that cover it, in ascending j.  One window: out = pred[r * W + j, d, l - s_j]
+ *     bit for bit (a select: -0.0 and NaN payloads survive, no multiply or divide).  More: num = sum_J w[l - s_j] pred[...] and
+ *     den = sum_J w[l - s_j], both in fp32 in ascending j starting from the first term, every product rounded before its add (no
+ *     contraction), out = num / den, one IEEE division.  A NaN in window j reaches exactly the frames that window covers.
+ * Both are one launch over (chunks of a row, rows) workgroups; every output element is written by one lane: no atomics, deterministic,
+ * no allocation, no host sync, graph-capturable.  out must not overlap the input.  The four-wide path is taken when n, window and stride
+ * are multiples of 4 (then every start is) and every buffer is 16-byte aligned; anything else takes the scalar path.
+ * OSUF_EINVAL, nothing launched: a NULL pointer; R, W, D, n or window < 1; stride < 1 or > window; n < window; W not the count above;
+ * R * W beyond an int. */
+int osuf_window_gather(const float* src, float* out, int R, int W, int D, int n, int window, int stride, hipStream_t stream);
+int osuf_window_fuse(const float* pred, const float* weight, float* out, int R, int W, int D, int n, int window, int stride,
+                     hipStream_t stream);
 int osuf_mse(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum, int B, int Dch, int L,
              hipStream_t stream);
 /* osuf_mse with per-sample weights w[B] (min-SNR-gamma): loss_sum += sum_b w[b] sum_{d, l < len_b} (pred - target)^2 and

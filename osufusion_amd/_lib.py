@@ -77,6 +77,8 @@ SIGNATURES = {
     "osuf_ct_solver_schedule": [P, I, I, F, P, P, I, P],
     "osuf_ct_solver_step": [P, P, P, F, P, P, P, P, I, P, L, P, P, I, L, P],
     "osuf_inpaint_blend": [P, P, P, P, L, P, I, I, I, P, I, I, I, P],
+    "osuf_window_gather": [P, P, I, I, I, I, I, I, P],
+    "osuf_window_fuse": [P, P, P, I, I, I, I, I, I, P],
     "osuf_mse": [P, P, P, P, P, I, I, I, P],
     "osuf_mse_w": [P, P, P, P, P, P, I, I, I, P],
     "osuf_sqnorm": [P, L, P, P],

@@ -533,6 +533,104 @@ __global__ __launch_bounds__(256) void inpaint_blend_kernel(const float* x, cons
   }
 }
 
+// ---- windowed sampling: cut a song into overlapping windows of the trained length, fuse the window predictions back ----------------------------
+// W windows of `window` frames over n >= window frames: window j < W - 1 starts at j * stride, the last one at n - window (clamped: it is
+// (W - 1) * stride only when the windows fit exactly), with W = ceil((n - window) / stride) + 1, so (W - 2) * stride < n - window and the
+// last window is never one of the regular ones.  Both kernels take that W from a host that has checked it.
+__device__ __forceinline__ int window_start(int j, int W, int n, int window, int stride) { return j < W - 1 ? j * stride : n - window; }
+
+// grid (chunks of D * window, window rows); out[r * W + j, d, i] = src[r, d, s_j + i].  VEC: n, window and stride multiples of 4 and both
+// buffers 16-byte aligned, so that every start and every row is; a group of four lies within one row of `window`.
+template <bool VEC>
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* src, float* out, int RW, int W, int D, int n, int window, int stride) {
+  const long per_row = (long)D * window;
+  for (int rw = blockIdx.y; rw < RW; rw += gridDim.y) {
+    const int r = rw / W, j = rw - r * W;
+    const float* from = src + (long)r * D * n + window_start(j, W, n, window, stride);
+    float* to = out + rw * per_row;
+    if (VEC) {
+      GRID_STRIDE(g, per_row >> 2) {
+        const long i0 = g << 2;
+        const long d = i0 / window;
+        *reinterpret_cast<f32x4*>(to + i0) = *reinterpret_cast<const f32x4*>(from + d * n + (i0 - d * window));
+      }
+    } else {
+      GRID_STRIDE(i, per_row) {
+        const long d = i / window;
+        to[i] = from[d * n + (i - d * window)];
+      }
+    }
+  }
+}
+
+// The windows that cover frame l, in ascending j: the regular ones j_lo .. j_hi (j * stride <= l < j * stride + window, j <= W - 2; none
+// when j_hi < j_lo) and then the last one when l >= n - window.
+struct WindowCover { int j_lo, j_hi; bool last; };
+__device__ __forceinline__ WindowCover window_cover(int l, int W, int n, int window, int stride) {
+  WindowCover c;
+  c.j_lo = l >= window ? (l - window) / stride + 1 : 0;
+  c.j_hi = min(l / stride, W - 2);
+  c.last = l >= n - window;
+  return c;
+}
+
+// One frame (T = float) or four frames that every window covers alike (T = f32x4) of row `p` = pred + (r * W * D + d) * window, whose
+// window j lies at p + j * D * window.  One window: its value, bit for bit.  More: sum_j w p / sum_j w in ascending j, every product
+// rounded before its add, one division.
+template <typename T>
+__device__ __forceinline__ T window_fuse_one(const float* p, const float* weight, long jstep, int l, int W, int n, int window, int stride) {
+#pragma clang fp contract(off)
+  const WindowCover c = window_cover(l, W, n, window, stride);
+  const int regular = c.j_hi >= c.j_lo ? c.j_hi - c.j_lo + 1 : 0;
+  const int s_last = n - window;
+  if (regular + (c.last ? 1 : 0) == 1) {
+    const int j = c.last ? W - 1 : c.j_lo;
+    return *reinterpret_cast<const T*>(p + j * jstep + (l - (c.last ? s_last : j * stride)));
+  }
+  // two windows or more: at least one is regular, and the sums start from it (not from zero: 0 + -0.0 would lose the sign)
+  T den = *reinterpret_cast<const T*>(weight + (l - c.j_lo * stride));
+  T num = den * *reinterpret_cast<const T*>(p + c.j_lo * jstep + (l - c.j_lo * stride));
+  for (int j = c.j_lo + 1; j <= c.j_hi; ++j) {
+    const int i = l - j * stride;
+    const T w = *reinterpret_cast<const T*>(weight + i);
+    const T wp = w * *reinterpret_cast<const T*>(p + j * jstep + i);
+    num = num + wp;
+    den = den + w;
+  }
+  if (c.last) {
+    const int i = l - s_last;
+    const T w = *reinterpret_cast<const T*>(weight + i);
+    const T wp = w * *reinterpret_cast<const T*>(p + (W - 1) * jstep + i);
+    num = num + wp;
+    den = den + w;
+  }
+  return num / den;
+}
+
+// grid (chunks of D * n, R); every output element is written by one lane: no atomics, the same bits on every run.  VEC as in the gather,
+// with `weight` aligned too: window boundaries are multiples of 4, so the four frames of a group have the same windows.
+template <bool VEC>
+__global__ __launch_bounds__(256) void window_fuse_kernel(const float* pred, const float* weight, float* out, int R, int W, int D, int n, int window,
+                                                          int stride) {
+  const long per_row = (long)D * n, jstep = (long)D * window;
+  for (int r = blockIdx.y; r < R; r += gridDim.y) {
+    const float* prow = pred + (long)r * W * jstep;
+    float* orow = out + r * per_row;
+    if (VEC) {
+      GRID_STRIDE(g, per_row >> 2) {
+        const long i0 = g << 2;
+        const long d = i0 / n;
+        *reinterpret_cast<f32x4*>(orow + i0) = window_fuse_one<f32x4>(prow + d * window, weight, jstep, (int)(i0 - d * n), W, n, window, stride);
+      }
+    } else {
+      GRID_STRIDE(i, per_row) {
+        const long d = i / n;
+        orow[i] = window_fuse_one<float>(prow + d * window, weight, jstep, (int)(i - d * n), W, n, window, stride);
+      }
+    }
+  }
+}
+
 // masked MSE: loss_sum += sum w*(pred-target)^2 (double), grad = 2*w*(pred-target)  (scaled by 1/count later)
 // WEIGHTED: w is the length mask times the sample's loss weight wt[b] (min-SNR-gamma); a weight of one leaves every bit as it was.
 template <bool WEIGHTED>
@@ -804,6 +902,38 @@ extern "C" int osuf_inpaint_blend(const float* x, const float* known, const floa
   else
     hipLaunchKernelGGL(inpaint_blend_kernel<false>, dim3(ew_grid(per_sample), gy), dim3(256), 0, stream, x, known, noise, mask, mask_ld, coef,
                        coef_ld, col_a, col_s, out, B, L, per_sample);
+  return osuf_launch_status();
+}
+
+// the layout both window entry points accept: n >= window >= stride >= 1 and W the window count of that layout (R * W within an int)
+static inline bool bad_windows(int R, int W, int D, int n, int window, int stride) {
+  if (R < 1 || W < 1 || D < 1 || n < 1 || window < 1 || stride < 1 || stride > window || n < window) return true;
+  return (long)W != ((long)n - window + stride - 1) / stride + 1 || (long)R * W > 0x7fffffffL;
+}
+
+extern "C" int osuf_window_gather(const float* src, float* out, int R, int W, int D, int n, int window, int stride, hipStream_t stream) {
+  if (!src || !out || bad_windows(R, W, D, n, window, stride)) return OSUF_EINVAL;
+  const int RW = R * W;
+  const long per_row = (long)D * window;
+  const unsigned gy = (unsigned)(RW < 65535 ? RW : 65535);
+  const bool vec = ((n | window | stride) & 3) == 0 && al16(src) && al16(out);
+  if (vec)
+    hipLaunchKernelGGL(window_gather_kernel<true>, dim3(ew_grid(per_row / 4), gy), dim3(256), 0, stream, src, out, RW, W, D, n, window, stride);
+  else
+    hipLaunchKernelGGL(window_gather_kernel<false>, dim3(ew_grid(per_row), gy), dim3(256), 0, stream, src, out, RW, W, D, n, window, stride);
+  return osuf_launch_status();
+}
+
+extern "C" int osuf_window_fuse(const float* pred, const float* weight, float* out, int R, int W, int D, int n, int window, int stride,
+                                hipStream_t stream) {
+  if (!pred || !weight || !out || bad_windows(R, W, D, n, window, stride)) return OSUF_EINVAL;
+  const long per_row = (long)D * n;
+  const unsigned gy = (unsigned)(R < 65535 ? R : 65535);
+  const bool vec = ((n | window | stride) & 3) == 0 && al16(pred) && al16(weight) && al16(out);
+  if (vec)
+    hipLaunchKernelGGL(window_fuse_kernel<true>, dim3(ew_grid(per_row / 4), gy), dim3(256), 0, stream, pred, weight, out, R, W, D, n, window, stride);
+  else
+    hipLaunchKernelGGL(window_fuse_kernel<false>, dim3(ew_grid(per_row), gy), dim3(256), 0, stream, pred, weight, out, R, W, D, n, window, stride);
   return osuf_launch_status();
 }
 

@@ -10,14 +10,16 @@ where(keep, mlp_cond(c), null_cond) + mlp_a(feature_extractor_a(stat_pool(a))) -
 branches of classifier-free guidance run as one batch of 2B, the guidance combine rides the DDIM-step kernel, and the attention forward of
 every block is one launch over all K/V groups (ops.one_launch_attention -> osuf_gqa_fwd).  Every ``sample`` takes ``known`` / ``known_mask``:
 masked generation by replacement conditioning, one ops.inpaint_blend per iterate handed to the denoiser (osufusion_amd/inpaint.py), with
-RePaint resampling on the ancestral sampler.  Not here: hipGraph capture of the step, LoRA on these backbones.
+RePaint resampling on the ancestral sampler, and ``window`` / ``window_stride`` / ``window_taper`` / ``window_batch``: songs longer than the
+trained context by fused-window denoising (osufusion_amd/windowed.py), one gather and one fuse around a batched backbone call per step.
+Not here: hipGraph capture of the step, LoRA on these backbones.
 """
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
-from .. import ct, inpaint, ops
+from .. import ct, inpaint, ops, windowed
 from .. import runtime as rt
 from ..modules.dit import DiT
 from ..modules.mmdit import MMDiT
@@ -31,6 +33,24 @@ SAMPLERS = ("ddpm", "ddim", "dpmpp_2m")                      # of ContinuousDiff
 
 class _TransformerOsuFusion(nn.Module):
     """What the two variants share: the backbone as `unet`, the compute-dtype switch and the step-independent part of a sample call."""
+
+    WINDOW_DOC = """The window keywords of every sample() here: windowed sampling (fused-window denoising, MultiDiffusion), for songs longer than the
+    trained context.
+      window: the window length in frames, usually the trained attn_context_len.  None (the default): the whole sequence goes to the
+        backbone at once, with the launches and the bits sample() had before these keywords.  A sequence of n <= window frames is
+        sampled that way too.  For n > window every denoiser call becomes: ops.window_gather of the iterate into W windows of exactly
+        `window` frames (windowed.window_starts; only the last start is clamped), the backbone on the b W windows as one batch, and
+        ops.window_fuse of the window predictions into one full-length prediction.  The step kernels, thresholding and the
+        known / known_mask blends work on the full-length tensors as before; the draws keep their shapes and their order.
+      window_stride: frames between window starts, in [1, window]; default window * 3 // 4 rounded down to a multiple of the backbone's
+        patch size (MMDiT's patch_size; a DiT counts as 1).
+      window_taper: "trapezoid" (the default; linear ramps over the window - window_stride overlapping frames) or "flat" (a plain mean).
+      window_batch: at most this many window rows per backbone call (None: all b W at once); bounds the activation memory.  Results under
+        different window_batch values are not promised to be bit-equal: the GEMM dispatch may depend on the row count.
+    ValueError: window < 1; a stride outside [1, window]; an unknown taper; window_batch < 1; window, the stride or (when n > window) n not
+    a multiple of the patch size; any of the other three given while window is None.
+    Out of scope: the two UNet models (their loop is written inline around the hipGraph capture and has no denoiser closure), hipGraph
+    capture of a windowed step, and any claim about map quality (no trained weights were at hand)."""
 
     def __init__(self, dim_h: int, backbone: str, cond_drop_prob: float, **backbone_kwargs) -> None:
         super().__init__()
@@ -70,6 +90,52 @@ class _TransformerOsuFusion(nn.Module):
             return net.denoise_rows(net.encode_x(xin, a_rows, dtype), cvec, n).contiguous()
         return f
 
+    def _windowed_denoiser(self, a: torch.Tensor, c: torch.Tensor, cfg: bool, window: int, stride: int, taper: str = "trapezoid",
+                           window_batch: Optional[int] = None):
+        """-> f(x (b, 6, n) fp32, t (nb,)) = the prediction (nb, 6, n) with _denoiser's contract (conditional rows first), by fused-window
+        denoising (osufusion_amd/windowed.py), n >= window.  Once, here: the audio cut into its W windows, a_w (b W, 96, window), the
+        conditioning repeated per window, and one inner _denoiser per chunk of at most window_batch of the b W window rows (None: one
+        chunk), so the audio rows and the static conditioning vector are still computed once per call; the statistics pooling sees the
+        window, as it does in training on sub-sequences.  Per step: one ops.window_gather of the iterate, one inner call per chunk with the
+        step's t repeated per window, the halves of its [cond; null] result written into one (2, b W, 6, window) buffer (a single chunk's
+        result is that buffer already), one ops.window_fuse over R = nb rows."""
+        b, n = a.shape[0], a.shape[-1]
+        W = len(windowed.window_starts(n, window, stride))
+        rows, g = b * W, 2 if cfg else 1
+        a_w = ops.window_gather(a.float().contiguous(), window, stride)
+        c_w = c.repeat_interleave(W, 0)
+        step = rows if window_batch is None else min(int(window_batch), rows)
+        chunks = [(lo, min(lo + step, rows)) for lo in range(0, rows, step)]
+        inner = [self._denoiser(a_w[lo:hi], c_w[lo:hi], cfg) for lo, hi in chunks]
+        weight = windowed.window_weight(window, stride, taper).to(a.device)
+
+        def f(x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+            x_w = ops.window_gather(x, window, stride)
+            t_w = t.view(g, b).repeat_interleave(W, 1)
+            if len(chunks) == 1:
+                pred = inner[0](x_w, t_w.reshape(-1))
+            else:
+                pred = torch.empty((g, rows, x.shape[1], window), dtype=torch.float32, device=x.device)
+                for (lo, hi), den in zip(chunks, inner):
+                    pred[:, lo:hi] = den(x_w[lo:hi], t_w[:, lo:hi].reshape(-1)).view(g, hi - lo, x.shape[1], window)
+            return ops.window_fuse(pred.view(g * rows, x.shape[1], window), weight, n, stride)
+        return f
+
+    def _make_denoiser(self, a: torch.Tensor, c: torch.Tensor, cfg: bool, wp: Optional[windowed.WindowPlan] = None):
+        """The closure every sampling loop calls: _denoiser over the whole sequence when no window is asked for or the sequence fits into
+        one, else _windowed_denoiser."""
+        if wp is None or a.shape[-1] <= wp.window:
+            return self._denoiser(a, c, cfg)
+        return self._windowed_denoiser(a, c, cfg, wp.window, wp.stride, wp.taper, wp.batch)
+
+    def _window_plan(self, a: torch.Tensor, window, window_stride, window_taper, window_batch) -> Optional[windowed.WindowPlan]:
+        """The window keywords of sample() checked against the backbone's patch size (a DiT counts as 1) and the length of `a`."""
+        p = getattr(self.unet, "patch_size", 1)
+        wp = windowed.plan(window, window_stride, window_taper, window_batch, p)
+        if wp is not None:
+            windowed.check_length(a.shape[-1], wp, p)
+        return wp
+
     def _start(self, a: torch.Tensor, x: Optional[torch.Tensor]) -> torch.Tensor:
         rt.require_gpu(a)
         if x is None:
@@ -89,19 +155,24 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
 
     @torch.inference_mode()
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
-               known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+               known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
+               window: Optional[int] = None, window_stride: Optional[int] = None, window_taper: str = "trapezoid",
+               window_batch: Optional[int] = None) -> torch.Tensor:
         """diffusion.py:59-77 on the transformer backbones.  Bit-reproducible.  (Attribute `stop_after`, None by default: return the iterate
         after that many of the sampling_timesteps steps, as models/diffusion.OsuFusion.)
 
         known (B, 6, n) and known_mask ((n,), (B, n) or (B, 1, n); 1 / True = keep), both or neither: masked generation as in
         models/diffusion.OsuFusion.sample_masked -- the start iterate blended at columns (1, 0) of the first coefficient row, every step's result at
         columns (2, 3) of its row, the final step of a full run exactly; one fixed noise tensor (a clone of the start iterate), no new draw.
-        With both None: no extra launch, the unmasked sampler's bits."""
-        masked = inpaint.check_pair(known, known_mask)
-        with ops.reproducible_mode(True), ops.one_launch_attention(True):
-            return self._sample(a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None)
+        With both None: no extra launch, the unmasked sampler's bits.
 
-    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None):
+        window, window_stride, window_taper, window_batch: windowed sampling, see _TransformerOsuFusion.WINDOW_DOC."""
+        masked = inpaint.check_pair(known, known_mask)
+        wp = self._window_plan(a, window, window_stride, window_taper, window_batch)
+        with ops.reproducible_mode(True), ops.one_launch_attention(True):
+            return self._sample(a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None, wp)
+
+    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None, wp=None):
         x_buf = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
@@ -111,7 +182,7 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
             steps = steps[:stop_after]
         nb = 2 * b if cfg else b
         with self._dtype_ctx():
-            f = self._denoiser(a, c, cfg)
+            f = self._make_denoiser(a, c, cfg, wp)
             coef_table = torch.tensor([[self.scheduler.step_coefficients(t)] * b for t in steps], dtype=torch.float32, device=device)
             t_table = torch.tensor([[t] * nb for t in steps], dtype=torch.int64, device=device)
             blender = inpaint.Blender(*keep_region, x_buf, fresh=False) if keep_region is not None else None
@@ -179,7 +250,9 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
 
     @torch.inference_mode()
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
-               known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None, resample: int = 1) -> torch.Tensor:
+               known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None, resample: int = 1,
+               window: Optional[int] = None, window_stride: Optional[int] = None, window_taper: str = "trapezoid",
+               window_batch: Optional[int] = None) -> torch.Tensor:
         """sampler = "ddpm": ancestral sampling over scheduler.get_sampling_timesteps: per step one denoiser call at log_snr(t) (2B rows with guidance) and one
         ops.ct_step (guidance, start prediction clamped to [-1, 1], posterior mean, noise).  Draws from the global generator, in this order:
         the start iterate torch.randn((B, 6, n)) when x is None, then one torch.randn of the iterate's shape per step, in step order; the
@@ -208,7 +281,10 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         times.  After pass u < r - 1 (the step, then its level blend) the whole iterate goes back one level by the exact forward transition
         x = k_r x + k_g z through ops.axpby_rows, z a fresh torch.randn, the last draw of that pass, with per sample
         k_r = alpha / alpha_next and k_g = sigma sqrt(c) (columns 1, 4 and 2, 6 of the step's row; sigma^2 - k_r^2 sigma_next^2 = sigma^2 c, so
-        nothing cancels), computed in fp32 torch once per call.  r (S - 1) + 1 denoiser calls for S steps."""
+        nothing cancels), computed in fp32 torch once per call.  r (S - 1) + 1 denoiser calls for S steps.
+
+        window, window_stride, window_taper, window_batch: windowed sampling, see _TransformerOsuFusion.WINDOW_DOC; the draws above are of
+        the full-length iterate's shape and keep their order."""
         masked = inpaint.check_pair(known, known_mask)
         resample = int(resample)
         if resample < 1:
@@ -216,12 +292,13 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         if resample > 1 and (self.sampler != "ddpm" or not masked):
             raise ValueError('resample > 1 needs sampler == "ddpm" and a known region (known, known_mask)')
         keep_region = (known, known_mask) if masked else None
+        wp = self._window_plan(a, window, window_stride, window_taper, window_batch)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
             if self.sampler != "ddpm":
-                return self._sample_solver(a, c, x, cond_scale, self.stop_after, keep_region)
-            return self._sample(a, c, x, cond_scale, self.stop_after, keep_region, resample)
+                return self._sample_solver(a, c, x, cond_scale, self.stop_after, keep_region, wp)
+            return self._sample(a, c, x, cond_scale, self.stop_after, keep_region, resample, wp)
 
-    def _sample_solver(self, a, c, x, cond_scale, stop_after, keep_region=None):
+    def _sample_solver(self, a, c, x, cond_scale, stop_after, keep_region=None, wp=None):
         x = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
@@ -237,7 +314,7 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         if blender is not None and steps > 0:
             x = blender.level(x, coef[0], ct.ALPHA, ct.SIGMA)
         with self._dtype_ctx():
-            f = self._denoiser(a, c, cfg)
+            f = self._make_denoiser(a, c, cfg, wp)
             for i in range(steps):
                 pred = f(x, log_snr[i])
                 noise = torch.randn(x.shape, device=device) if draws else None
@@ -248,7 +325,7 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
                     x = blender.exact(x) if i == total - 1 else blender.level(x, coef[i], ct.ALPHA_NEXT, ct.SIGMA_NEXT)
         return x
 
-    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None, resample=1):
+    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None, resample=1, wp=None):
         x = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
@@ -266,7 +343,7 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
             k_r = (coef[:, :, ct.ALPHA] / coef[:, :, ct.ALPHA_NEXT]).contiguous()
             k_g = (coef[:, :, ct.SIGMA] * torch.sqrt(coef[:, :, ct.C])).contiguous()
         with self._dtype_ctx():
-            f = self._denoiser(a, c, cfg)
+            f = self._make_denoiser(a, c, cfg, wp)
             for i in range(steps):
                 passes = resample if i < total - 1 else 1
                 for u in range(passes):
@@ -317,21 +394,26 @@ class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
 
     @torch.inference_mode()
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0,
-               known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+               known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
+               window: Optional[int] = None, window_stride: Optional[int] = None, window_taper: str = "trapezoid",
+               window_batch: Optional[int] = None) -> torch.Tensor:
         """rectified_flow.py:57-79 on the transformer backbones: the fixed-grid midpoint loop, 2 * (S - 1) evaluations.  Bit-reproducible.
         known / known_mask (both or neither): masked generation as in models/rectified_flow.OsuFusion.sample_masked -- every state handed to the
-        backbone blended at (t, 1 - t), the end of the last interval exactly, one fixed noise tensor, no new draw."""
-        masked = inpaint.check_pair(known, known_mask)
-        with ops.reproducible_mode(True), ops.one_launch_attention(True):
-            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None)
+        backbone blended at (t, 1 - t), the end of the last interval exactly, one fixed noise tensor, no new draw.
 
-    def _sample(self, a, c, x, cond_scale, keep_region=None):
+        window, window_stride, window_taper, window_batch: windowed sampling, see _TransformerOsuFusion.WINDOW_DOC."""
+        masked = inpaint.check_pair(known, known_mask)
+        wp = self._window_plan(a, window, window_stride, window_taper, window_batch)
+        with ops.reproducible_mode(True), ops.one_launch_attention(True):
+            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None, wp)
+
+    def _sample(self, a, c, x, cond_scale, keep_region=None, wp=None):
         x = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
         ones = torch.ones(b, dtype=torch.float32, device=device)
         with self._dtype_ctx():
-            den = self._denoiser(a, c, cfg)
+            den = self._make_denoiser(a, c, cfg, wp)
 
             def f(t: float, y: torch.Tensor) -> torch.Tensor:
                 out = den(y, torch.full((2 * b if cfg else b,), t, dtype=torch.float32, device=device))

@@ -749,6 +749,20 @@ def inpaint_blend(x: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, coef
     return inpaint.inpaint_blend(x, known, mask, coef, col_a, col_s, noise, out)
 
 
+def window_gather(src: torch.Tensor, window: int, stride: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Windowed sampling's cut: src (R, D, n) -> (R * W, D, window), the overlapping windows of windowed.window_starts(n, window, stride), a
+    copy of bits.  The allocating wrapper lives in osufusion_amd/windowed.py (its guarded-memory cases in tests/test_windowed_gpu.py)."""
+    from . import windowed
+    return windowed.window_gather(src, window, stride, out)
+
+
+def window_fuse(pred: torch.Tensor, weight: torch.Tensor, n: int, stride: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Windowed sampling's fuse: pred (R * W, D, window) -> (R, D, n), the weighted mean of the windows that cover each frame (the
+    window's own bits where there is one), deterministic.  See osufusion_amd/windowed.py."""
+    from . import windowed
+    return windowed.window_fuse(pred, weight, n, stride, out)
+
+
 def mse(pred: torch.Tensor, target: torch.Tensor, orig_len: Optional[torch.Tensor], want_grad: bool, weight: Optional[torch.Tensor] = None):
     """weight: per-sample fp32 (B,) loss weights (osuf_mse_w); None is osuf_mse."""
     B, Dc, Lx = pred.shape
