@@ -271,7 +271,7 @@ int osuf_mqa_bwd_fused_qs(const void* q, long ldq, const void* k, long ldk, cons
                           float* workspace, long workspace_bytes, int qsplit, int dq_mode, hipStream_t stream);
 long osuf_mqa_bwd_fused_workspace_bytes(int B, int H, int N, int out_dtype, int qsplit, int dq_mode);
 
-/* ---- layout / scheduler / optimizer (elementwise.hip) ----------------------------------------------------------
+/* ---- layout / scheduler / optimizer (elementwise.hip; the samplers' kernels: sampling.hip) -----------------------
  * replaces: the (B,C,L) <-> (B,L,C) rearranges (modules/unet.py:180,183) at the model boundary, torch.cat (unet.py:500,
  *           507,510), DDIMScheduler.add_noise / .step (models/diffusion.py:96,75; diffusers 0.29.2), the CFG combine
  *           (unet.py:465), F.mse_loss + mask (diffusion.py:101-111), get_total_norm / clip_grad_norm_ / AdamW.step

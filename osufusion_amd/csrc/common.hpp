@@ -187,6 +187,9 @@ static inline int ew_grid(long total_threads) {
   if (blocks < 1) blocks = 1;
   return (int)blocks;
 }
+// the loop of such a kernel (256 lanes per block): idx over [0, total), whatever the grid
+#define GRID_STRIDE(idx, total) \
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < (total); idx += (long)gridDim.x * blockDim.x)
 static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline bool bad_c(int C) { return C <= 0 || (C & 7) || C > 2048; }
 

@@ -1,4 +1,4 @@
-"""Continuous-time Gaussian diffusion on the device (osuf_ct_schedule, osuf_ct_step, csrc/elementwise.hip); reached as ops.ct_schedule /
+"""Continuous-time Gaussian diffusion on the device (osuf_ct_schedule, osuf_ct_step, csrc/sampling.hip); reached as ops.ct_schedule /
 ops.ct_step.  The allocating wrappers live here, as osufusion_amd/gqa.py's does; their guarded-memory cases are in
 tests/test_scheduler_gpu.py.  Prediction objectives and dynamic thresholding (osuf_ct_step_ex, osuf_ct_x0_quantile, osuf_ct_qsample;
 ops.ct_step_ex / ops.ct_x0_quantile / ops.ct_qsample) follow, guarded in tests/test_ct_objectives_gpu.py; then the DDIM / DPM-Solver++(2M)

@@ -1,8 +1,8 @@
-"""Masked generation: keep the known parts of a beatmap while a sampler draws the rest (osuf_inpaint_blend, csrc/elementwise.hip; reached as
+"""Masked generation: keep the known parts of a beatmap while a sampler draws the rest (osuf_inpaint_blend, csrc/sampling.hip; reached as
 ops.inpaint_blend).  The method is replacement conditioning: before an iterate goes to the denoiser its known region is overwritten by the
 known signal noised to the iterate's own level, a known + s noise -- fresh noise per blend in the stochastic samplers (RePaint), one
 fixed tensor in the deterministic ones, whose known region then follows the trajectory the sampler itself would take for that x_0.  The
-allocating wrapper and the mask helpers live here, as ct.py's do; `Blender` is what the five sampling loops of osufusion_amd/models share.
+allocating wrapper and the mask helpers live here, as ct.py's do; `Blender` is what the sampling loops of osufusion_amd/models share.
 The guarded-memory cases are in tests/test_inpaint_gpu.py."""
 from __future__ import annotations
 

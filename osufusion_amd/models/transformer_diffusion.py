@@ -12,9 +12,12 @@ every block is one launch over all K/V groups (ops.one_launch_attention -> osuf_
 masked generation by replacement conditioning, one ops.inpaint_blend per iterate handed to the denoiser (osufusion_amd/inpaint.py), with
 RePaint resampling on the ancestral sampler, and ``window`` / ``window_stride`` / ``window_taper`` / ``window_batch``: songs longer than the
 trained context by fused-window denoising (osufusion_amd/windowed.py), one gather and one fuse around a batched backbone call per step.
+The three diffusion samplers (discrete DDIM, ancestral, DDIM / 2M solver) share one loop, _TransformerOsuFusion._run; each describes its
+steps to it with a _Steps record.  The flow sampler's loop is models/rectified_flow.midpoint_loop.
 Not here: hipGraph capture of the step, LoRA on these backbones.
 """
-from typing import Optional
+from dataclasses import dataclass
+from typing import Callable, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -143,6 +146,50 @@ class _TransformerOsuFusion(nn.Module):
         rt.require_gpu(x)
         return x.float().contiguous()
 
+    def _run(self, describe, a, c, x, cond_scale, stop_after, keep_region=None, wp=None):
+        """The sampling loop of the diffusion samplers; describe(b, cfg, cond_scale, device) -> the sampler's _Steps.  Draws, in this order:
+        the start iterate (x None), the start blend's noise; then per pass of a step its own noise, its level blend's noise, the resample
+        draw -- each only where the sampler has one.  Per pass: the denoiser, the step, the blend of the known region, the resample."""
+        x = self._start(a, x)
+        b, device = a.shape[0], a.device
+        cfg = cond_scale != 1.0
+        sp = describe(b, cfg, cond_scale, device)
+        total = sp.coef.shape[0]
+        steps = total if stop_after is None else min(stop_after, total)
+        blender = inpaint.Blender(*keep_region, x, fresh=sp.fresh) if keep_region is not None else None
+        if blender is not None and steps > 0:
+            x = blender.level(x, sp.coef[0], *sp.start_cols)
+        state = None
+        with self._dtype_ctx():
+            f = self._make_denoiser(a, c, cfg, wp)
+            for i in range(steps):
+                passes = sp.resample if i < sp.last else 1
+                for u in range(passes):
+                    pred = f(x, sp.t_in[i])
+                    noise = torch.randn(x.shape, device=device) if i < sp.draw_steps else None
+                    x, state = sp.step(i, x, pred[:b], pred[b:] if cfg else None, noise, state)
+                    if blender is not None:
+                        x = blender.exact(x) if i == sp.last else blender.level(x, sp.coef[i], *sp.step_cols)
+                    if u < passes - 1:
+                        x = ops.axpby_rows(x, torch.randn(x.shape, device=device), sp.k_r[i], sp.k_g[i])
+        return x
+
+
+@dataclass
+class _Steps:
+    """What a sampler tells _TransformerOsuFusion._run.  S = the steps of a full run."""
+    coef: torch.Tensor                  # (S, b, cols): step i's coefficient rows, also the levels of the blends
+    t_in: torch.Tensor                  # (S, nb): step i's time input of the denoiser
+    step: Callable                      # step(i, x, cond, null, noise, state) -> (x, state); state is None on the first call
+    draw_steps: int                     # steps i < draw_steps draw a torch.randn of the iterate's shape for `noise`, the others get None
+    fresh: bool                         # the level blends draw fresh noise (else: one fixed tensor, a clone of the start iterate)
+    start_cols: Tuple[int, int]         # columns (a, s) of coef[0] for the level blend of the start iterate
+    step_cols: Tuple[int, int]          # columns (a, s) of coef[i] for the level blend after step i
+    last: int                           # the step that ends a full run: the exact blend instead of a level blend, and no resampling
+    resample: int = 1                   # the ancestral sampler's RePaint passes per step, with the factors of the way back one level:
+    k_r: Optional[torch.Tensor] = None  # (S, b) x = k_r x + k_g z
+    k_g: Optional[torch.Tensor] = None
+
 
 class DiffusionOsuFusionDiT(_TransformerOsuFusion):
     def __init__(self, dim_h: int, backbone: str = "mmdit", cond_drop_prob: float = 0.5, train_timesteps: int = 1000,
@@ -170,30 +217,17 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
         masked = inpaint.check_pair(known, known_mask)
         wp = self._window_plan(a, window, window_stride, window_taper, window_batch)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
-            return self._sample(a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None, wp)
+            return self._run(self._ddim, a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None, wp)
 
-    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None, wp=None):
-        x_buf = self._start(a, x)
-        b, device = a.shape[0], a.device
-        cfg = cond_scale != 1.0
+    def _ddim(self, b, cfg, cond_scale, device) -> _Steps:
         self.scheduler.set_timesteps(self.sampling_timesteps)
         steps = self.scheduler.timesteps.tolist()
-        if stop_after is not None:
-            steps = steps[:stop_after]
-        nb = 2 * b if cfg else b
-        with self._dtype_ctx():
-            f = self._make_denoiser(a, c, cfg, wp)
-            coef_table = torch.tensor([[self.scheduler.step_coefficients(t)] * b for t in steps], dtype=torch.float32, device=device)
-            t_table = torch.tensor([[t] * nb for t in steps], dtype=torch.int64, device=device)
-            blender = inpaint.Blender(*keep_region, x_buf, fresh=False) if keep_region is not None else None
-            if blender is not None and len(steps) > 0:
-                x_buf = blender.level(x_buf, coef_table[0], 1, 0)
-            for i in range(len(steps)):
-                pred = f(x_buf, t_table[i])
-                x_buf = ops.ddim_step(x_buf, pred[:b], pred[b:] if cfg else None, cond_scale, coef_table[i])
-                if blender is not None:
-                    x_buf = blender.exact(x_buf) if i == self.sampling_timesteps - 1 else blender.level(x_buf, coef_table[i], 2, 3)
-        return x_buf
+        coef = torch.tensor([[self.scheduler.step_coefficients(t)] * b for t in steps], dtype=torch.float32, device=device)
+        t_in = torch.tensor([[t] * (2 * b if cfg else b) for t in steps], dtype=torch.int64, device=device)
+
+        def step(i, x, cond, null, noise, state):
+            return ops.ddim_step(x, cond, null, cond_scale, coef[i]), None
+        return _Steps(coef, t_in, step, draw_steps=0, fresh=False, start_cols=(1, 0), step_cols=(2, 3), last=self.sampling_timesteps - 1)
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"
@@ -294,72 +328,46 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         keep_region = (known, known_mask) if masked else None
         wp = self._window_plan(a, window, window_stride, window_taper, window_batch)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
-            if self.sampler != "ddpm":
-                return self._sample_solver(a, c, x, cond_scale, self.stop_after, keep_region, wp)
-            return self._sample(a, c, x, cond_scale, self.stop_after, keep_region, resample, wp)
+            describe = self._solver if self.sampler != "ddpm" else lambda *args: self._ancestral(*args, resample)
+            return self._run(describe, a, c, x, cond_scale, self.stop_after, keep_region, wp)
 
-    def _sample_solver(self, a, c, x, cond_scale, stop_after, keep_region=None, wp=None):
-        x = self._start(a, x)
-        b, device = a.shape[0], a.device
-        cfg = cond_scale != 1.0
+    def _threshold(self, x, cond, null, cond_scale, row) -> Optional[torch.Tensor]:
+        """The per-sample dynamic threshold of a step, one ops.ct_x0_quantile; None (the static clamp) without dynamic_thresholding."""
+        if not self.dynamic_thresholding:
+            return None
+        return ops.ct_x0_quantile(x, cond, null, cond_scale, row, self.pred_objective, self.dynamic_thresholding_percentile)[:, 2]
+
+    def _solver(self, b, cfg, cond_scale, device) -> _Steps:
         total = self.scheduler.timesteps
-        steps = total if stop_after is None else min(stop_after, total)
         grid = self.scheduler.solver_log_snr_grid(total, self.solver_spacing, self.solver_logsnr_min, device=device)
         coef, fac = self.scheduler.solver_coefficients(grid, self.sampler, self.ddim_eta, batch=b)
         log_snr = grid[:-1, None].repeat(1, 2 * b if cfg else b)
-        objective, q = self.pred_objective, self.dynamic_thresholding_percentile
         draws = self.sampler == "ddim" and self.ddim_eta > 0.0
-        x0_prev = None
-        blender = inpaint.Blender(*keep_region, x, fresh=draws) if keep_region is not None else None
-        if blender is not None and steps > 0:
-            x = blender.level(x, coef[0], ct.ALPHA, ct.SIGMA)
-        with self._dtype_ctx():
-            f = self._make_denoiser(a, c, cfg, wp)
-            for i in range(steps):
-                pred = f(x, log_snr[i])
-                noise = torch.randn(x.shape, device=device) if draws else None
-                cond, null = pred[:b], pred[b:] if cfg else None
-                s = ops.ct_x0_quantile(x, cond, null, cond_scale, coef[i], objective, q)[:, 2] if self.dynamic_thresholding else None
-                x, x0_prev = ops.ct_solver_step(x, cond, null, cond_scale, coef[i], fac[i], x0_prev, noise, objective, s)
-                if blender is not None:
-                    x = blender.exact(x) if i == total - 1 else blender.level(x, coef[i], ct.ALPHA_NEXT, ct.SIGMA_NEXT)
-        return x
 
-    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None, resample=1, wp=None):
-        x = self._start(a, x)
-        b, device = a.shape[0], a.device
-        cfg = cond_scale != 1.0
+        def step(i, x, cond, null, noise, x0_prev):        # the state: the clamped start prediction, the next 2M step's x0_prev
+            s = self._threshold(x, cond, null, cond_scale, coef[i])
+            return ops.ct_solver_step(x, cond, null, cond_scale, coef[i], fac[i], x0_prev, noise, self.pred_objective, s)
+        return _Steps(coef, log_snr, step, draw_steps=total if draws else 0, fresh=draws, start_cols=(ct.ALPHA, ct.SIGMA),
+                      step_cols=(ct.ALPHA_NEXT, ct.SIGMA_NEXT), last=total - 1)
+
+    def _ancestral(self, b, cfg, cond_scale, device, resample=1) -> _Steps:
         total = self.scheduler.timesteps
-        steps = total if stop_after is None else min(stop_after, total)
         times = torch.linspace(1.0, 0.0, total + 1, device=device, dtype=torch.float32)        # get_sampling_timesteps' grid, every pair at once
         coef = self.scheduler.coefficients(times[:-1].repeat_interleave(b), times[1:].repeat_interleave(b)).view(total, b, -1)
         log_snr = coef[:, :, 0].repeat(1, 2 if cfg else 1).contiguous()
-        objective, thresholded = self.pred_objective, self.dynamic_thresholding
-        plain = objective == "noise" and not thresholded
-        blender = inpaint.Blender(*keep_region, x, fresh=True) if keep_region is not None else None
-        if blender is not None and steps > 0:
-            x = blender.level(x, coef[0], ct.ALPHA, ct.SIGMA)
+        plain = self.pred_objective == "noise" and not self.dynamic_thresholding
+        k_r = k_g = None
         if resample > 1:                                    # the forward transition from a step's level back to the level it left
             k_r = (coef[:, :, ct.ALPHA] / coef[:, :, ct.ALPHA_NEXT]).contiguous()
             k_g = (coef[:, :, ct.SIGMA] * torch.sqrt(coef[:, :, ct.C])).contiguous()
-        with self._dtype_ctx():
-            f = self._make_denoiser(a, c, cfg, wp)
-            for i in range(steps):
-                passes = resample if i < total - 1 else 1
-                for u in range(passes):
-                    pred = f(x, log_snr[i])
-                    noise = torch.randn(x.shape, device=device) if i < total - 1 else None
-                    cond, null = pred[:b], pred[b:] if cfg else None
-                    if not plain:
-                        s = ops.ct_x0_quantile(x, cond, null, cond_scale, coef[i], objective, self.dynamic_thresholding_percentile)[:, 2] if thresholded else None
-                        x = ops.ct_step_ex(x, cond, null, cond_scale, coef[i], noise, objective, s)
-                    else:
-                        x = ops.ct_step(x, cond, null, cond_scale, coef[i], noise)
-                    if blender is not None:
-                        x = blender.exact(x) if i == total - 1 else blender.level(x, coef[i], ct.ALPHA_NEXT, ct.SIGMA_NEXT)
-                    if u < passes - 1:
-                        x = ops.axpby_rows(x, torch.randn(x.shape, device=device), k_r[i], k_g[i])
-        return x
+
+        def step(i, x, cond, null, noise, state):
+            if plain:
+                return ops.ct_step(x, cond, null, cond_scale, coef[i], noise), None
+            s = self._threshold(x, cond, null, cond_scale, coef[i])
+            return ops.ct_step_ex(x, cond, null, cond_scale, coef[i], noise, self.pred_objective, s), None
+        return _Steps(coef, log_snr, step, draw_steps=total - 1, fresh=True, start_cols=(ct.ALPHA, ct.SIGMA),
+                      step_cols=(ct.ALPHA_NEXT, ct.SIGMA_NEXT), last=total - 1, resample=resample, k_r=k_r, k_g=k_g)
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"

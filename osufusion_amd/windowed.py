@@ -1,7 +1,7 @@
 """Windowed sampling: generate a song longer than the trained context by fused-window denoising (MultiDiffusion).  At every step the
 iterate is cut into overlapping windows of the trained length (osuf_window_gather), the denoiser runs on all windows as one batch, and
 the window predictions are fused back into one full-length prediction by a tapered, normalised overlap-add (osuf_window_fuse, both in
-csrc/elementwise.hip; reached as ops.window_gather / ops.window_fuse).  The step kernels then work on the full-length tensors as they do
+csrc/sampling.hip; reached as ops.window_gather / ops.window_fuse).  The step kernels then work on the full-length tensors as they do
 without windows.  The window layout, the taper, the allocating wrappers and the argument rules of every sample() live here, as
 inpaint.py's do; the closure the sampling loops call is _TransformerOsuFusion._windowed_denoiser (models/transformer_diffusion.py).  The
 guarded-memory cases are in tests/test_windowed_gpu.py."""
