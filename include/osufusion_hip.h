@@ -386,6 +386,22 @@ int osuf_mse_w(const float* pred, const float* target, const int* orig_len, cons
 int osuf_sqnorm(const float* g, long n, double* out, hipStream_t stream);
 int osuf_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps, float wd,
                int step, const float* gscale, hipStream_t stream);
+/* Exponential moving averages of the weights, kept in the optimizer pass.  ema holds `tracks` buffers (1..4): track j is ema + j * ema_ld,
+ * n floats; ema_ld >= n, the rest of a row is padding and is never touched.  d_j = 1 - beta_j (d_j for j >= tracks is ignored).
+ *   osuf_adamw_ema: osuf_adamw's effect on p, m, v bit for bit (the same device function), then, from the parameter value just written,
+ *                   e_j <- fma(d_j, p_new - e_j, e_j) for every track: one more read and one more write per element and track.
+ *   osuf_ema_update: the same track update (the same device function: the same bits) from p as it stands, no optimizer.
+ * Two values of d_j are selects: d_j == 0 neither reads nor writes track j, d_j >= 1 stores p_new itself without reading the track.
+ * Four-wide body, scalar tail (n % 4 elements), as osuf_adamw.  OSUF_EINVAL, nothing launched: tracks outside 1..4; ema_ld < n; a NULL
+ * ema; a d_j < 0 or NaN; what osuf_adamw rejects; and, when n >= 4 (the four-wide path runs), an ema or an ema_ld that is not 16-byte
+ * aligned (ema_ld % 4 != 0).
+ *   osuf_swap: a <-> b, n floats each, in place.  OSUF_EINVAL: a == b or overlapping ranges, NULL, n < 1, a pointer not 16-byte aligned. */
+int osuf_adamw_ema(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps, float wd,
+                   int step, const float* gscale, float* ema, long ema_ld, int tracks, float d0, float d1, float d2, float d3,
+                   hipStream_t stream);
+int osuf_ema_update(const float* p, float* ema, long ema_ld, long n, int tracks, float d0, float d1, float d2, float d3,
+                    hipStream_t stream);
+int osuf_swap(float* a, float* b, long n, hipStream_t stream);
 int osuf_clip_coef(const double* sumsq, float max_norm, float base, float* coef, float* total_norm, hipStream_t stream);
 int osuf_cast_f32_bf16(const float* src, void* dst, long n, hipStream_t stream);
 /* GEMM operand layouts of one conv / linear weight, both from the fp32 master (O, I, k) in one pass -- what the reference gets

@@ -83,6 +83,9 @@ SIGNATURES = {
     "osuf_mse_w": [P, P, P, P, P, P, I, I, I, P],
     "osuf_sqnorm": [P, L, P, P],
     "osuf_adamw": [P, P, P, P, L, F, F, F, F, F, I, P, P],
+    "osuf_adamw_ema": [P, P, P, P, L, F, F, F, F, F, I, P, P, L, I, F, F, F, F, P],
+    "osuf_ema_update": [P, P, L, L, I, F, F, F, F, P],
+    "osuf_swap": [P, P, L, P],
     "osuf_clip_coef": [P, F, F, P, P, P],
     "osuf_cast_f32_bf16": [P, P, L, P],
     "osuf_pack_weight": [P, I, I, I, I, P, L, L, P, L, L, I, P],

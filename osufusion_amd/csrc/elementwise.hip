@@ -112,34 +112,124 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* g, long n, dou
 
 // torch.optim.AdamW semantics (decoupled decay), one launch over the flat parameter buffer.
 // gscale (device scalar, may be null) multiplies the gradient: 1/world or a clip coefficient, no host sync.
-__global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                                                    float eps, float wd, float inv_bc1, float inv_sqrt_bc2, const float* gscale) {
+struct AdamWArgs { float lr, beta1, beta2, eps, wd, inv_bc1, inv_sqrt_bc2; };
+
+// The update of ONE element, written once: adamw_kernel and adamw_ema_kernel (vector body and scalar tail of both) call it.  Every fused
+// multiply-add is spelled out and contraction is off for the rest: left to the compiler, the same source line became an fma in one kernel and
+// a multiply plus an add in another (it did, between the four-wide body and the scalar tail), and the kernels' bits drifted apart.  The
+// forms are the ones the four-wide body has always compiled to.
+__device__ __forceinline__ void adamw_element(float& p, float g, float& m, float& v, float gs, const AdamWArgs& a) {
+#pragma clang fp contract(off)
+  const float ge = g * gs;
+  m = fmaf(1.f - a.beta1, ge, a.beta1 * m);
+  v = fmaf(a.beta2, v, ((1.f - a.beta2) * ge) * ge);
+  const float denom = fmaf(sqrtf(v), a.inv_sqrt_bc2, a.eps);
+  p = fmaf(fmaf(-a.lr, a.wd, 1.f), p, -((a.lr * a.inv_bc1) * m / denom));
+}
+
+// ---- EMA tracks of the weights: e <- e + d (p - e), up to four tracks per pass -----------------------------------------------
+// Track j is ema + j * ld (n floats).  d[j] = 1 - beta_j.  Two values are selects, not arithmetic: d == 0 neither reads nor writes the
+// track, d >= 1 stores p without reading the track.  In between, one subtraction and one fused multiply-add (two roundings).
+struct EmaArgs { float* ema; long ld; float d[4]; };
+
+__device__ __forceinline__ bool ema_blends(float d) { return d > 0.f && d < 1.f; }
+__device__ __forceinline__ float ema_element(float e, float p, float d) { return fmaf(d, p - e, e); }
+__device__ __forceinline__ f32x4 ema_element(f32x4 e, f32x4 p, float d) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) e[c] = ema_element(e[c], p[c], d);
+  return e;
+}
+// V = f32x4 (i counts vectors) or float (i counts elements).  The loads are a step of their own so that the fused kernel issues them
+// ahead of the AdamW arithmetic; a track that does not blend loads nothing.
+template <int TRACKS, typename V>
+__device__ __forceinline__ void ema_load(const EmaArgs& a, long i, V (&e)[TRACKS]) {
+#pragma unroll
+  for (int j = 0; j < TRACKS; ++j)
+    if (ema_blends(a.d[j])) e[j] = reinterpret_cast<const V*>(a.ema + j * a.ld)[i];
+}
+template <int TRACKS, typename V>
+__device__ __forceinline__ void ema_store(const EmaArgs& a, long i, const V (&e)[TRACKS], V p) {
+#pragma unroll
+  for (int j = 0; j < TRACKS; ++j) {
+    V* dst = reinterpret_cast<V*>(a.ema + j * a.ld) + i;
+    if (ema_blends(a.d[j])) *dst = ema_element(e[j], p, a.d[j]);
+    else if (a.d[j] >= 1.f) *dst = p;
+  }
+}
+
+// TRACKS = 0 is torch.optim.AdamW alone (osuf_adamw); TRACKS = 1..4 also moves that many EMA tracks towards the parameter just written.
+template <int TRACKS>
+__device__ __forceinline__ void adamw_body(float* p, const float* g, float* m, float* v, long n, const AdamWArgs& a, const float* gscale,
+                                           const EmaArgs& ea) {
   const float gs = gscale ? *gscale : 1.f;
   const long n4 = n >> 2;
   GRID_STRIDE(i, n4) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i], gv = reinterpret_cast<const f32x4*>(g)[i];
     f32x4 mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+    f32x4 ev[TRACKS ? TRACKS : 1];
+    if constexpr (TRACKS > 0) ema_load<TRACKS>(ea, i, ev);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float ge = gv[e] * gs;
-      pv[e] *= 1.f - lr * wd;
-      mv[e] = beta1 * mv[e] + (1.f - beta1) * ge;
-      vv[e] = beta2 * vv[e] + (1.f - beta2) * ge * ge;
-      const float denom = sqrtf(vv[e]) * inv_sqrt_bc2 + eps;
-      pv[e] -= lr * inv_bc1 * mv[e] / denom;
+      float pe = pv[e], me = mv[e], ve = vv[e];
+      adamw_element(pe, gv[e], me, ve, gs, a);
+      pv[e] = pe; mv[e] = me; vv[e] = ve;
     }
     reinterpret_cast<f32x4*>(p)[i] = pv;
     reinterpret_cast<f32x4*>(m)[i] = mv;
     reinterpret_cast<f32x4*>(v)[i] = vv;
+    if constexpr (TRACKS > 0) ema_store<TRACKS>(ea, i, ev, pv);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const long i = (n4 << 2) + threadIdx.x;
-    const float ge = g[i] * gs;
-    float pe = p[i] * (1.f - lr * wd);
-    const float me = beta1 * m[i] + (1.f - beta1) * ge;
-    const float ve = beta2 * v[i] + (1.f - beta2) * ge * ge;
-    pe -= lr * inv_bc1 * me / (sqrtf(ve) * inv_sqrt_bc2 + eps);
+    float pe = p[i], me = m[i], ve = v[i];
+    float es[TRACKS ? TRACKS : 1];
+    if constexpr (TRACKS > 0) ema_load<TRACKS>(ea, i, es);
+    adamw_element(pe, g[i], me, ve, gs, a);
     p[i] = pe; m[i] = me; v[i] = ve;
+    if constexpr (TRACKS > 0) ema_store<TRACKS>(ea, i, es, pe);
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+                                                    float eps, float wd, float inv_bc1, float inv_sqrt_bc2, const float* gscale) {
+  adamw_body<0>(p, g, m, v, n, AdamWArgs{lr, beta1, beta2, eps, wd, inv_bc1, inv_sqrt_bc2}, gscale, EmaArgs{});
+}
+
+template <int TRACKS>
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* p, const float* g, float* m, float* v, long n, AdamWArgs a, const float* gscale,
+                                                        EmaArgs ea) {
+  adamw_body<TRACKS>(p, g, m, v, n, a, gscale, ea);
+}
+
+// the tracks alone, from the parameters as they stand
+template <int TRACKS>
+__global__ __launch_bounds__(256) void ema_update_kernel(const float* p, long n, EmaArgs ea) {
+  const long n4 = n >> 2;
+  GRID_STRIDE(i, n4) {
+    f32x4 ev[TRACKS];
+    ema_load<TRACKS>(ea, i, ev);
+    ema_store<TRACKS>(ea, i, ev, reinterpret_cast<const f32x4*>(p)[i]);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long i = (n4 << 2) + threadIdx.x;
+    float es[TRACKS];
+    ema_load<TRACKS>(ea, i, es);
+    ema_store<TRACKS>(ea, i, es, p[i]);
+  }
+}
+
+// a <-> b, in place
+__global__ __launch_bounds__(256) void swap_kernel(float* a, float* b, long n) {
+  const long n4 = n >> 2;
+  GRID_STRIDE(i, n4) {
+    const f32x4 av = reinterpret_cast<f32x4*>(a)[i], bv = reinterpret_cast<f32x4*>(b)[i];
+    reinterpret_cast<f32x4*>(a)[i] = bv;
+    reinterpret_cast<f32x4*>(b)[i] = av;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long i = (n4 << 2) + threadIdx.x;
+    const float ae = a[i], be = b[i];
+    a[i] = be; b[i] = ae;
   }
 }
 
@@ -232,6 +322,50 @@ extern "C" int osuf_adamw(float* p, const float* g, float* m, float* v, long n, 
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, stream, p, g, m, v, n, lr, beta1, beta2, eps, wd,
                      (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), gscale);
+  return osuf_launch_status();
+}
+
+// tracks in 1..4, every d >= 0, ld >= n; on the four-wide path (n >= 4) the base and the track stride must keep every track 16-byte aligned
+static bool ema_args(float* ema, long ld, long n, int tracks, float d0, float d1, float d2, float d3, EmaArgs* out) {
+  *out = EmaArgs{ema, ld, {d0, d1, d2, d3}};
+  if (!ema || tracks < 1 || tracks > 4 || ld < n) return false;
+  if (n >= 4 && (!al16(ema) || (ld & 3))) return false;
+  for (int j = 0; j < tracks; ++j)
+    if (!(out->d[j] >= 0.f)) return false;
+  return true;
+}
+#define DISPATCH_TRACKS(tracks, ...)                 \
+  switch (tracks) {                                  \
+    case 1: { constexpr int TRACKS = 1; __VA_ARGS__; } break; \
+    case 2: { constexpr int TRACKS = 2; __VA_ARGS__; } break; \
+    case 3: { constexpr int TRACKS = 3; __VA_ARGS__; } break; \
+    default: { constexpr int TRACKS = 4; __VA_ARGS__; } break; \
+  }
+
+extern "C" int osuf_adamw_ema(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps, float wd,
+                              int step, const float* gscale, float* ema, long ema_ld, int tracks, float d0, float d1, float d2, float d3,
+                              hipStream_t stream) {
+  EmaArgs ea;
+  if (n <= 0 || step <= 0 || !al16(p) || !al16(g) || !al16(m) || !al16(v) || !ema_args(ema, ema_ld, n, tracks, d0, d1, d2, d3, &ea))
+    return OSUF_EINVAL;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  const AdamWArgs a{lr, beta1, beta2, eps, wd, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2))};
+  DISPATCH_TRACKS(tracks, hipLaunchKernelGGL(adamw_ema_kernel<TRACKS>, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, stream, p, g, m, v, n, a, gscale, ea));
+  return osuf_launch_status();
+}
+
+extern "C" int osuf_ema_update(const float* p, float* ema, long ema_ld, long n, int tracks, float d0, float d1, float d2, float d3,
+                               hipStream_t stream) {
+  EmaArgs ea;
+  if (n <= 0 || !al16(p) || !ema_args(ema, ema_ld, n, tracks, d0, d1, d2, d3, &ea)) return OSUF_EINVAL;
+  DISPATCH_TRACKS(tracks, hipLaunchKernelGGL(ema_update_kernel<TRACKS>, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, stream, p, n, ea));
+  return osuf_launch_status();
+}
+
+extern "C" int osuf_swap(float* a, float* b, long n, hipStream_t stream) {
+  if (n <= 0 || !a || !b || !al16(a) || !al16(b)) return OSUF_EINVAL;
+  if (a == b || (a < b ? b - a : a - b) < n) return OSUF_EINVAL;       // the same or overlapping buffers
+  hipLaunchKernelGGL(swap_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, stream, a, b, n);
   return osuf_launch_status();
 }
 

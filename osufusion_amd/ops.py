@@ -786,6 +786,32 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, gscale=None) -> None:
     call("osuf_adamw", _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, wd, step, _p(gscale), _stream())
 
 
+def _ema_rows(ema: torch.Tensor, n: int, d) -> Tuple[int, int, Tuple[float, ...]]:
+    """(row stride, tracks, d padded to four) of an fp32 (tracks, >= n) EMA buffer whose rows are contiguous."""
+    assert ema.dtype == torch.float32 and ema.dim() == 2 and ema.stride(1) == 1 and ema.shape[1] >= n and ema.is_cuda
+    d = tuple(float(x) for x in d)
+    assert len(d) == ema.shape[0], "one d = 1 - beta per track"
+    return ema.stride(0), ema.shape[0], d + (0.0,) * (4 - len(d))
+
+
+def adamw_ema(p, g, m, v, lr, beta1, beta2, eps, wd, step, gscale, ema: torch.Tensor, d) -> None:
+    """adamw, and in the same pass every row of ema (tracks, ld) moves towards the new parameters: e += d[j] * (p_new - e)."""
+    ld, tracks, d4 = _ema_rows(ema, p.numel(), d)
+    call("osuf_adamw_ema", _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, wd, step, _p(gscale), _p(ema), ld, tracks, *d4, _stream())
+
+
+def ema_update(p: torch.Tensor, ema: torch.Tensor, d) -> None:
+    """The track update of adamw_ema from p as it stands (no optimizer step)."""
+    ld, tracks, d4 = _ema_rows(ema, p.numel(), d)
+    call("osuf_ema_update", _p(p), _p(ema), ld, p.numel(), tracks, *d4, _stream())
+
+
+def swap(a: torch.Tensor, b: torch.Tensor) -> None:
+    """Exchange the contents of two contiguous fp32 buffers of one length, in place."""
+    assert a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel() and a.is_cuda and b.is_cuda
+    call("osuf_swap", _p(a), _p(b), a.numel(), _stream())
+
+
 def clip_coef(sumsq: torch.Tensor, max_norm: float, base: float, coef: torch.Tensor, total_norm: Optional[torch.Tensor]) -> None:
     call("osuf_clip_coef", _p(sumsq), float(max_norm), float(base), _p(coef), _p(total_norm), _stream())
 

@@ -17,6 +17,7 @@ from __future__ import annotations
 import math
 import os
 import time
+from contextlib import contextmanager
 from typing import List, Optional
 
 import torch
@@ -25,6 +26,7 @@ import torch.nn as nn
 
 from . import functional as Fn
 from . import ops
+from .ema import as_tracks, ema_d
 
 
 class FlatParameters:
@@ -278,7 +280,8 @@ class GradReducer:
 class FusedAdamW:
     """torch.optim.AdamW semantics (trainer.py:230,307) as one kernel over the flat buffers; lr may be changed per step."""
 
-    def __init__(self, flat: FlatParameters, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2) -> None:
+    def __init__(self, flat: FlatParameters, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 ema=None) -> None:
         self.flat, self.lr, self.betas, self.eps, self.weight_decay = flat, lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat.data)
         self.exp_avg_sq = torch.zeros_like(flat.data)
@@ -287,6 +290,26 @@ class FusedAdamW:
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
         self.coef = torch.ones(1, dtype=torch.float32, device=dev)
         self.total_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        # EMA tracks of the weights (osufusion_amd/ema.py): one (tracks, ld) buffer, row j = track j in the layout of flat.data, moved by
+        # the AdamW launch itself.  ema_step counts the steps the tracks have seen (not step_count: a resumed run may start them later).
+        self.ema_cfgs = as_tracks(ema)
+        self.ema_step = 0
+        self.ema: Optional[torch.Tensor] = None
+        if self.ema_cfgs:
+            self.ema = torch.zeros(len(self.ema_cfgs), (flat.numel + 3) // 4 * 4, dtype=torch.float32, device=dev)
+            self.reset_ema()
+
+    def reset_ema(self) -> None:
+        """Every track becomes a copy of the weights as they stand; the schedules start over."""
+        self.ema_step = 0
+        if self.ema is not None:
+            self.ema[:, :self.flat.numel].copy_(self.flat.data.unsqueeze(0).expand(len(self.ema_cfgs), -1))
+
+    def ema_track(self, j: int) -> torch.Tensor:
+        """Track j as a flat view in the layout of flat.data."""
+        if self.ema is None or not 0 <= j < len(self.ema_cfgs):
+            raise IndexError(f"EMA track {j}: the optimizer keeps {len(self.ema_cfgs)}")
+        return self.ema[j, :self.flat.numel]
 
     def step(self, grad_scale: float = 1.0, clip_grad_norm: float = 0.0) -> torch.Tensor:
         """grad_scale: e.g. 1/world after a SUM all-reduce.  Returns the (device) total gradient norm of the scaled gradient."""
@@ -295,8 +318,13 @@ class FusedAdamW:
         ops.sqnorm(self.flat.grad, self.sumsq)
         # total_norm of the averaged gradient = grad_scale * sqrt(sumsq); clip coefficient computed on device
         ops.clip_coef(self.sumsq, clip_grad_norm / grad_scale if clip_grad_norm > 0 else 0.0, grad_scale, self.coef, self.total_norm)
-        ops.adamw(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
-                  self.weight_decay, self.step_count, self.coef)
+        if self.ema is None:
+            ops.adamw(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
+                      self.weight_decay, self.step_count, self.coef)
+        else:
+            self.ema_step += 1
+            ops.adamw_ema(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
+                          self.weight_decay, self.step_count, self.coef, self.ema, [ema_d(c, self.ema_step) for c in self.ema_cfgs])
         Fn.bump_weight_epoch()
         return self.total_norm * grad_scale
 
@@ -341,6 +369,37 @@ class FusedAdamW:
             raise ValueError("per-parameter step counts differ; the fused kernel keeps one step count for all parameters")
         self.step_count = steps.pop() if steps else 0
 
+    # -- EMA tracks by parameter name (checkpoint.pt["ema_state_dict"]) -------------------------------------------------------
+    def _named_slices(self, module: nn.Module):
+        """(name, parameter, offset) of every trainable parameter, in module.named_parameters() order."""
+        off = {id(p): o for p, o in zip(self.flat.params, self.flat.offsets)}
+        return [(k, p, off[id(p)]) for k, p in module.named_parameters() if id(p) in off]
+
+    def ema_state_dict(self, module: nn.Module) -> List[dict]:
+        return [{k: self.ema_track(j)[o:o + p.numel()].view_as(p).clone() for k, p, o in self._named_slices(module)}
+                for j in range(len(self.ema_cfgs))]
+
+    def check_ema_state_dict(self, module: nn.Module, tracks: List[dict]) -> None:
+        """ValueError unless `tracks` is one {name: tensor} per track of this optimizer, over this model's trainable parameters."""
+        if len(tracks) != len(self.ema_cfgs):
+            raise ValueError(f"the checkpoint holds {len(tracks)} EMA tracks, this trainer keeps {len(self.ema_cfgs)} (its ema= argument)")
+        named = self._named_slices(module)
+        for sd in tracks:
+            if set(sd) != {k for k, _, _ in named}:
+                raise ValueError("the checkpoint's EMA tracks do not name this model's trainable parameters")
+            for k, p, _ in named:
+                if tuple(sd[k].shape) != tuple(p.shape):
+                    raise ValueError(f"EMA track of {k}: shape {tuple(sd[k].shape)} in the checkpoint, {tuple(p.shape)} in the model")
+
+    def load_ema_state_dict(self, module: nn.Module, tracks: List[dict], step: int) -> None:
+        self.check_ema_state_dict(module, tracks)
+        named = self._named_slices(module)
+        with torch.no_grad():
+            for j, sd in enumerate(tracks):
+                for k, p, o in named:
+                    self.ema_track(j)[o:o + p.numel()].view_as(p).copy_(sd[k])
+        self.ema_step = int(step)
+
 
 def cosine_warmup_lr(step: int, base_lr: float, warmup: int, total: int, num_cycles: float = 0.5) -> float:
     """diffusers.get_cosine_schedule_with_warmup as called at trainer.py:231-236."""
@@ -357,18 +416,24 @@ class Trainer:
     (trainer.py:293-309): each step() call is one micro-batch; the first k-1 add their gradients into the flat buffer without
     any communication (no-sync), the k-th also reduces, clips and applies AdamW on the mean over all k * world micro-batches.
     After the first optimizer step the flat buffers are re-laid out in the order in which that backward completed the
-    gradients (reorder_buckets), so that bucket i is complete -- and on the wire -- before bucket i+1."""
+    gradients (reorder_buckets), so that bucket i is complete -- and on the wire -- before bucket i+1.
+
+    ema = an EMAConfig or up to four (osufusion_amd/ema.py): the AdamW launch also moves that many exponential moving averages of the
+    weights, once per optimizer step (not per micro-batch); they are re-laid out with the parameters, need no communication (every rank
+    holds the same parameters) and are read through ema_weights() / ema_state_dict().  ema=None issues exactly the launches of before."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 1e-2, clip_grad_norm: float = 0.0,
                  bucket_mib: float = 64.0, compute_dtype: Optional[torch.dtype] = torch.bfloat16,
                  gradient_accumulation_steps: int = 1, overlap: bool = True, reorder_buckets: bool = True,
-                 comm_dtype: Optional[torch.dtype] = None) -> None:
+                 comm_dtype: Optional[torch.dtype] = None, ema=None) -> None:
         assert gradient_accumulation_steps >= 1
+        ema = as_tracks(ema)                                # an EMAConfig or up to four (ValueError) before anything is re-homed
         self.model = model
         self.flat = FlatParameters(model)
         self.reducer = GradReducer(self.flat, bucket_mib, overlap=overlap, comm_dtype=comm_dtype)
         self.reducer.names = {id(p): n for n, p in model.named_parameters()}
-        self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay)
+        self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, ema=ema)
+        self._ema_swapped: Optional[int] = None             # the track whose values stand in flat.data (inside ema_weights)
         self.clip = clip_grad_norm
         self.compute_dtype = compute_dtype
         self.accum = gradient_accumulation_steps
@@ -378,7 +443,8 @@ class Trainer:
         self.order_disagreements = 0
         if self.reducer.enabled:                            # identical replicas (guard; inits are already deterministic)
             dist.broadcast(self.flat.data, src=0)
-            self.check_layout_agreement()
+            self.opt.reset_ema()                            # the tracks start as copies of rank 0's weights; identical replicas
+            self.check_layout_agreement()                   # keep them identical from there on: no communication
         Fn.bump_weight_epoch()
         Fn.enable_direct_grads(True, self.reducer.param_ready, self.reducer.param_complete)
 
@@ -386,6 +452,7 @@ class Trainer:
         """One micro-batch.  Returns (loss, total_norm): total_norm is the device scalar of the clipped step's gradient norm on
         the micro-batch that applied the optimizer, None on accumulation-only micro-batches."""
         from .runtime import forced_compute_dtype
+        self._not_swapped("step")
         if self.micro == 0:
             self.flat.zero_grad()
         last = self.micro + 1 == self.accum
@@ -427,7 +494,10 @@ class Trainer:
         if self.reducer.enabled:
             order = self._agree_on_order(order)
         if order != list(range(len(order))):
-            self.opt.exp_avg, self.opt.exp_avg_sq = self.flat.reorder(order, (self.opt.exp_avg, self.opt.exp_avg_sq))
+            tracks = [self.opt.ema_track(j) for j in range(len(self.opt.ema_cfgs))]     # every EMA track travels with its parameter
+            self.opt.exp_avg, self.opt.exp_avg_sq, *moved = self.flat.reorder(order, (self.opt.exp_avg, self.opt.exp_avg_sq, *tracks))
+            for dst, src in zip(tracks, moved):
+                dst.copy_(src)
             self.reducer.rebuild()
             Fn.bump_weight_epoch()                          # parameter storage moved: cached operand packs key on data_ptr
         self.check_layout_agreement()
@@ -481,14 +551,70 @@ class Trainer:
         if len(set(vals)) != 1:
             raise RuntimeError(f"flat parameter layouts differ across ranks (fingerprints {vals}): refusing to all-reduce positionally")
 
+    # -- the averaged weights ------------------------------------------------------------------------------------------------
+    def _not_swapped(self, what: str) -> None:
+        if self._ema_swapped is not None:
+            raise RuntimeError(f"Trainer.{what} inside ema_weights(): EMA track {self._ema_swapped} stands in for the live weights")
+
+    @contextmanager
+    def ema_weights(self, track: int = 0):
+        """Inside the block the model's trainable parameters hold EMA track `track`: model.sample(...), model(...) in eval mode and
+        model.state_dict() see the averaged weights.  Entry exchanges flat.data with the track in place (osuf_swap: no third buffer of
+        model size) and re-packs the GEMM operands; exit exchanges them back, so the live weights and the track return bit for bit.
+        Not re-entrant: entering it again, step(), state_dict() and load_state_dict() raise RuntimeError inside the block."""
+        self._not_swapped("ema_weights")
+        if self.micro:
+            raise RuntimeError("Trainer.ema_weights in the middle of a gradient-accumulation window")
+        e = self.opt.ema_track(track)
+        self._swap_with(e)
+        self._ema_swapped = track
+        try:
+            yield self.model
+        finally:
+            self._swap_with(e)
+            self._ema_swapped = None
+
+    def _swap_with(self, e: torch.Tensor) -> None:
+        ops.swap(self.flat.data, e)
+        Fn.bump_weight_epoch()                              # the packed GEMM operands key on the weight epoch
+        Fn.refresh_packs()
+
+    def ema_state_dict(self, track: int = 0) -> dict:
+        """A state dict in the model's own key layout (model.load_state_dict loads it, data.save_model_sd's format stores it): EMA track
+        `track` for every trainable parameter, the current values for buffers and frozen parameters."""
+        e = self.flat.data if self._ema_swapped == track else self.opt.ema_track(track)
+        off = {id(p): o for p, o in zip(self.flat.params, self.flat.offsets)}
+        sd = {}
+        for k, v in self.model.state_dict(keep_vars=True).items():
+            o = off.get(id(v))
+            sd[k] = v.detach().clone() if o is None else e[o:o + v.numel()].view_as(v).clone()
+        return sd
+
     # -- checkpoint.pt in the reference's layout (trainer.py:148-203): resumable by either trainer ------------------------
     def state_dict(self, scheduler_state: Optional[dict] = None) -> dict:
-        return {"model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.opt.state_dict(self.model),
-                "scheduler_state_dict": scheduler_state if scheduler_state is not None else {}, "rng_state": torch.get_rng_state()}
+        """With EMA tracks three keys follow the reference's four: "ema_state_dict" (one {name: tensor} per track, trainable parameters
+        in model.named_parameters() order), "ema_config" (the tracks' EMAConfig fields as plain dicts) and "ema_step"."""
+        self._not_swapped("state_dict")
+        sd = {"model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.opt.state_dict(self.model),
+              "scheduler_state_dict": scheduler_state if scheduler_state is not None else {}, "rng_state": torch.get_rng_state()}
+        if self.opt.ema_cfgs:
+            sd["ema_state_dict"] = self.opt.ema_state_dict(self.model)
+            sd["ema_config"] = [c.as_dict() for c in self.opt.ema_cfgs]
+            sd["ema_step"] = self.opt.ema_step
+        return sd
 
     def load_state_dict(self, checkpoint: dict, strict: bool = True) -> None:
+        self._not_swapped("load_state_dict")
+        tracks = checkpoint.get("ema_state_dict")
+        if tracks is not None:
+            self.opt.check_ema_state_dict(self.model, tracks)                   # track count and shapes, before anything is overwritten
         self.model.load_state_dict(checkpoint["model_state_dict"], strict=strict)      # copies into the flat buffer's views
         self.opt.load_state_dict(self.model, checkpoint["optimizer_state_dict"])
+        if tracks is not None:
+            self.opt.load_ema_state_dict(self.model, tracks, checkpoint.get("ema_step", 0))
+        elif self.opt.ema_cfgs:                             # e.g. the reference trainer's own checkpoint.pt
+            self.opt.reset_ema()
+            print(f"checkpoint without EMA state: the {len(self.opt.ema_cfgs)} EMA track(s) restart as copies of the loaded weights")
         if "rng_state" in checkpoint and checkpoint["rng_state"] is not None:
             torch.set_rng_state(checkpoint["rng_state"].cpu())
         Fn.bump_weight_epoch()
