@@ -377,6 +377,24 @@ int osuf_inpaint_blend(const float* x, const float* known, const float* noise, c
 int osuf_window_gather(const float* src, float* out, int R, int W, int D, int n, int window, int stride, hipStream_t stream);
 int osuf_window_fuse(const float* pred, const float* weight, float* out, int R, int W, int D, int n, int window, int stride,
                      hipStream_t stream);
+/* Classifier-free guidance rescale (Lin et al. 2024, sec. 3.4; no counterpart in the reference): the guided prediction brought back to the
+ * conditional prediction's per-sample spread.  cond, nullp and out are fp32 (B, per_sample), contiguous; out may alias neither input.
+ *   g = nullp + (cond - nullp) cond_scale in fp32, three roundings in that order (no contraction);
+ *   f_b = phi sqrt(var_b(cond) / var_b(g)) + (1 - phi), var_b over the per_sample values of sample b (the estimator's normalisation cancels),
+ *     from fp64 sums of c, c^2, g, g^2 as sum x^2 - (sum x)^2 / per_sample, evaluated in fp64 and rounded once -> factor[b];
+ *   out = f_b g, one fp32 multiply per element.
+ * f_b = 1 as a select where per_sample < 2 or var_b(g) <= 0 (all-equal predictions; exact zeros give exactly 0), and a rounding residue
+ * below zero in var_b(cond) counts as zero.  NaN and Inf in a sample propagate into that sample's f_b and out and into no other sample.
+ * Two launches on `stream` over (ceil(per_sample / 4096), min(B, 65535)) workgroups, no atomics: the first writes every 4096-element chunk's four
+ * sums to ws[b][chunk][4] (fp64), the second adds a sample's chunks in index order, stores f_b (the sample's first workgroup) and writes its
+ * chunk of out.  Chunks, lanes and the order of every sum depend on per_sample and on the path alone: sample b's bits do not depend on B or
+ * on scheduling.  ws: osuf_cfg_rescale_workspace_bytes(B, per_sample) bytes, 8-byte aligned, written before it is read (no zeroing needed).
+ * No allocation, no host sync, graph-capturable.  The four-wide path is taken when per_sample % 4 == 0 and cond, nullp and out are 16-byte
+ * aligned; anything else takes the scalar path (a sample's sums may differ between the two in the last bits of fp64).
+ * OSUF_EINVAL, nothing launched: a NULL pointer; B < 1; per_sample < 1; phi outside [0, 1] or not finite; ws not 8-byte aligned. */
+long osuf_cfg_rescale_workspace_bytes(int B, long per_sample);
+int osuf_cfg_rescale(const float* cond, const float* nullp, float cond_scale, float phi, void* ws, float* factor, float* out, int B,
+                     long per_sample, hipStream_t stream);
 int osuf_mse(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum, int B, int Dch, int L,
              hipStream_t stream);
 /* osuf_mse with per-sample weights w[B] (min-SNR-gamma): loss_sum += sum_b w[b] sum_{d, l < len_b} (pred - target)^2 and

@@ -1,6 +1,7 @@
 // The sampling kernels (HBM-bound, fp32, 16 B per lane where the buffers allow), gfx950: the discrete DDPM / DDIM algebra, continuous-time
 // Gaussian diffusion (log-SNR schedule, the step kernel of the ancestral sampler and of the DDIM / DPM-Solver++(2M) solvers, the dynamic
-// threshold's radix select, q_sample), masked generation and the windows of windowed sampling; their entry points follow the kernels.
+// threshold's radix select, q_sample), masked generation, the windows of windowed sampling and the rescale of the guided prediction; their
+// entry points follow the kernels.
 #include "common.hpp"
 
 // ---- DDPM / DDIM algebra on (B, D, L) fp32 tensors; per-sample coefficients in device arrays -------------
@@ -536,6 +537,113 @@ __global__ __launch_bounds__(256) void window_fuse_kernel(const float* pred, con
   }
 }
 
+// ---- classifier-free guidance rescale (Lin et al. 2024, 3.4): the guided prediction brought back to the conditional one's spread ---------------
+// out = f_b g, g the guided prediction and f_b = phi sqrt(var_b(cond) / var_b(g)) + (1 - phi), the variances over the sample's per_sample
+// values.  Two launches over the same grid (chunks of CFGR_CHUNK elements, samples), no atomics: pass 1 writes every chunk's four sums
+// (c, c^2, g, g^2) to ws[b][chunk][4], pass 2 adds a sample's chunks in index order, forms f_b and writes out.  A chunk is a fixed range of
+// the sample and a lane's elements and the order of every sum are fixed too, so sample b's bits depend on per_sample and on the path (four-wide
+// or scalar) alone, never on B or on which workgroup ran when.  The sums are fp64: sum x^2 - (sum x)^2 / n cancels to (spread / mean)^2 of its
+// terms, 1e-4 where the mean is 100 spreads -- beyond fp32, 1e-12 of the variance in fp64.  The squares of fp32 values are exact in fp64.
+#define CFGR_CHUNK 4096                                      // elements per workgroup: 256 lanes x 4 x 4
+
+// g in ct_guide's order, every operation rounded (the sum is not contracted with the product): the restatement's bits, whatever the flags.
+__device__ inline float cfgr_guide(float cond, float nu, float cond_scale) {
+#pragma clang fp contract(off)
+  const float d = cond - nu;
+  const float m = d * cond_scale;
+  return nu + m;
+}
+
+__device__ inline void cfgr_add(double (&s)[4], float c, float g) {
+#pragma clang fp contract(off)
+  const double dc = (double)c, dg = (double)g;
+  s[0] += dc; s[1] += dc * dc; s[2] += dg; s[3] += dg * dg;
+}
+
+// f_b from the sample's four sums.  1 as a select where there is no spread to rescale to: n < 2, or var(g) <= 0 (all-equal predictions: exact
+// zeros give exactly 0; a NaN is not <= 0 and propagates).  A rounding residue below zero in var(cond) counts as zero.
+__device__ inline float cfgr_factor(const double (&s)[4], long n, float phi) {
+#pragma clang fp contract(off)
+  if (n < 2) return 1.f;
+  const double dn = (double)n;
+  double vc = s[1] - s[0] * s[0] / dn;
+  const double vg = s[3] - s[2] * s[2] / dn;
+  if (vg <= 0.0) return 1.f;
+  if (vc < 0.0) vc = 0.0;
+  const double p = (double)phi;
+  return (float)(p * sqrt(vc / vg) + (1.0 - p));
+}
+
+// grid (G, min(B, 65535)), G = ceil(per_sample / CFGR_CHUNK).  VEC: per_sample % 4 == 0 and cond, nullp (and out, which pass 2 writes) 16-byte
+// aligned, so every sample's row is.  Within the wave by shuffles, then the four waves through LDS in wave order.
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_rescale_sums_kernel(const float* cond, const float* nullp, float cond_scale, double* ws, int B,
+                                                               long per_sample) {
+  __shared__ double part[4][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long lo = (long)blockIdx.x * CFGR_CHUNK;
+  const long hi = lo + CFGR_CHUNK < per_sample ? lo + CFGR_CHUNK : per_sample;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const long base = (long)b * per_sample;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    if (VEC) {
+      for (long j = lo + 4 * tid; j < hi; j += 1024) {         // hi is a multiple of 4: the group lies within the chunk
+        const f32x4 cv = *reinterpret_cast<const f32x4*>(cond + base + j), nv = *reinterpret_cast<const f32x4*>(nullp + base + j);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) cfgr_add(s, cv[e], cfgr_guide(cv[e], nv[e], cond_scale));
+      }
+    } else {
+      for (long j = lo + tid; j < hi; j += 256) {
+        const float c = cond[base + j];
+        cfgr_add(s, c, cfgr_guide(c, nullp[base + j], cond_scale));
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+    }
+    if (lane == 0) { part[wave][0] = s[0]; part[wave][1] = s[1]; part[wave][2] = s[2]; part[wave][3] = s[3]; }
+    __syncthreads();
+    if (tid < 4) ws[((long)b * gridDim.x + blockIdx.x) * 4 + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+    __syncthreads();                                          // part is written again for the next sample
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_rescale_apply_kernel(const float* cond, const float* nullp, float cond_scale, float phi, const double* ws,
+                                                                float* factor, float* out, int B, long per_sample) {
+  __shared__ float f_sh;
+  const int tid = threadIdx.x;
+  const long lo = (long)blockIdx.x * CFGR_CHUNK;
+  const long hi = lo + CFGR_CHUNK < per_sample ? lo + CFGR_CHUNK : per_sample;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    if (tid == 0) {                                           // every workgroup of the sample adds the same G rows in the same order
+      const double* p = ws + (long)b * gridDim.x * 4;
+      double s[4] = {0.0, 0.0, 0.0, 0.0};
+      for (unsigned i = 0; i < gridDim.x; ++i) { s[0] += p[4 * i]; s[1] += p[4 * i + 1]; s[2] += p[4 * i + 2]; s[3] += p[4 * i + 3]; }
+      const float f = cfgr_factor(s, per_sample, phi);
+      f_sh = f;
+      if (blockIdx.x == 0) factor[b] = f;
+    }
+    __syncthreads();
+    const float f = f_sh;
+    const long base = (long)b * per_sample;
+    if (VEC) {
+      for (long j = lo + 4 * tid; j < hi; j += 1024) {
+        const f32x4 cv = *reinterpret_cast<const f32x4*>(cond + base + j), nv = *reinterpret_cast<const f32x4*>(nullp + base + j);
+        f32x4 ov;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ov[e] = f * cfgr_guide(cv[e], nv[e], cond_scale);
+        *reinterpret_cast<f32x4*>(out + base + j) = ov;
+      }
+    } else {
+      for (long j = lo + tid; j < hi; j += 256) out[base + j] = f * cfgr_guide(cond[base + j], nullp[base + j], cond_scale);
+    }
+    __syncthreads();                                          // f_sh is written again for the next sample
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 
 extern "C" int osuf_axpby_rows(const float* x, const float* y, const float* ca, const float* cb, float* out, int B, long per_sample, hipStream_t stream) {
@@ -700,5 +808,28 @@ extern "C" int osuf_window_fuse(const float* pred, const float* weight, float* o
     hipLaunchKernelGGL(window_fuse_kernel<true>, dim3(ew_grid(per_row / 4), gy), dim3(256), 0, stream, pred, weight, out, R, W, D, n, window, stride);
   else
     hipLaunchKernelGGL(window_fuse_kernel<false>, dim3(ew_grid(per_row), gy), dim3(256), 0, stream, pred, weight, out, R, W, D, n, window, stride);
+  return osuf_launch_status();
+}
+
+static inline long cfgr_chunks(long per_sample) { return (per_sample + CFGR_CHUNK - 1) / CFGR_CHUNK; }
+
+extern "C" long osuf_cfg_rescale_workspace_bytes(int B, long per_sample) {
+  return B > 0 && per_sample > 0 ? (long)B * cfgr_chunks(per_sample) * 4 * (long)sizeof(double) : 0;
+}
+
+extern "C" int osuf_cfg_rescale(const float* cond, const float* nullp, float cond_scale, float phi, void* ws, float* factor, float* out, int B,
+                                long per_sample, hipStream_t stream) {
+  if (!cond || !nullp || !ws || !factor || !out || B < 1 || per_sample < 1 || !(phi >= 0.f && phi <= 1.f)) return OSUF_EINVAL;
+  const long G = cfgr_chunks(per_sample);
+  if ((reinterpret_cast<uintptr_t>(ws) & 7) || G > 0x7fffffffL) return OSUF_EINVAL;
+  const dim3 grid((unsigned)G, (unsigned)(B < 65535 ? B : 65535));
+  double* sums = (double*)ws;
+  if (per_sample % 4 == 0 && al16(cond) && al16(nullp) && al16(out)) {
+    hipLaunchKernelGGL(cfg_rescale_sums_kernel<true>, grid, dim3(256), 0, stream, cond, nullp, cond_scale, sums, B, per_sample);
+    hipLaunchKernelGGL(cfg_rescale_apply_kernel<true>, grid, dim3(256), 0, stream, cond, nullp, cond_scale, phi, sums, factor, out, B, per_sample);
+  } else {
+    hipLaunchKernelGGL(cfg_rescale_sums_kernel<false>, grid, dim3(256), 0, stream, cond, nullp, cond_scale, sums, B, per_sample);
+    hipLaunchKernelGGL(cfg_rescale_apply_kernel<false>, grid, dim3(256), 0, stream, cond, nullp, cond_scale, phi, sums, factor, out, B, per_sample);
+  }
   return osuf_launch_status();
 }

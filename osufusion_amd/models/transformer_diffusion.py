@@ -11,7 +11,9 @@ branches of classifier-free guidance run as one batch of 2B, the guidance combin
 every block is one launch over all K/V groups (ops.one_launch_attention -> osuf_gqa_fwd).  Every ``sample`` takes ``known`` / ``known_mask``:
 masked generation by replacement conditioning, one ops.inpaint_blend per iterate handed to the denoiser (osufusion_amd/inpaint.py), with
 RePaint resampling on the ancestral sampler, and ``window`` / ``window_stride`` / ``window_taper`` / ``window_batch``: songs longer than the
-trained context by fused-window denoising (osufusion_amd/windowed.py), one gather and one fuse around a batched backbone call per step.
+trained context by fused-window denoising (osufusion_amd/windowed.py), one gather and one fuse around a batched backbone call per step,
+and ``guidance_rescale`` / ``guidance_interval``: the CFG rescale (one ops.cfg_rescale before a guided step) and guidance only inside a band
+of log-SNR, the conditional B rows alone outside it (osufusion_amd/guidance.py).
 The three diffusion samplers (discrete DDIM, ancestral, DDIM / 2M solver) share one loop, _TransformerOsuFusion._run; each describes its
 steps to it with a _Steps record.  The flow sampler's loop is models/rectified_flow.midpoint_loop.
 Not here: hipGraph capture of the step, LoRA on these backbones.
@@ -22,7 +24,7 @@ from typing import Callable, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from .. import ct, inpaint, ops, windowed
+from .. import ct, guidance, inpaint, ops, windowed
 from .. import runtime as rt
 from ..modules.dit import DiT
 from ..modules.mmdit import MMDiT
@@ -55,6 +57,25 @@ class _TransformerOsuFusion(nn.Module):
     Out of scope: the two UNet models (their loop is written inline around the hipGraph capture and has no denoiser closure), hipGraph
     capture of a windowed step, and any claim about map quality (no trained weights were at hand)."""
 
+    GUIDANCE_DOC = """The guidance keywords of every sample() here (osufusion_amd/guidance.py).  A denoiser call is guided iff cond_scale != 1 and its
+    log-SNR lies in the interval; all log-SNR values are host floats, fixed before the loop.
+      guidance_interval: (lo, hi) in log-SNR, both ends inclusive, None at an end = unbounded; None (the default): every call is guided.
+        A guided call runs 2B rows, as before.  An unguided call runs the conditional B rows only -- the first B rows of the
+        step-independent audio rows and conditioning vector, the first B entries of the step's time input -- and the step takes
+        (cond, None), the unguided path of every step kernel and of ops.ct_x0_quantile.  window_batch chunks both forms.
+      guidance_rescale: phi in [0, 1] (Lin et al. 2024, sec. 3.4).  With phi > 0 one ops.cfg_rescale goes before the step of every guided
+        call: the guided prediction scaled per sample by phi std(cond) / std(guided) + (1 - phi); the step, and ops.ct_x0_quantile under
+        dynamic thresholding, take (that, None).  With windows it sees the fused full-length prediction.  The 2M state, the draws and
+        their order, known / known_mask, resample and stop_after are unchanged.
+    At the defaults, with (None, None), and with an interval that contains every call at phi = 0: the launches and the bits sample() had
+    before these keywords (a bounded interval on the continuous-time model reads the grid's log-SNR back once).  With cond_scale == 1 both
+    are accepted and change nothing.
+    ValueError: phi outside [0, 1]; an interval that is not a pair; lo > hi; a NaN end.
+    Not promised: that a B-row call equals the first B rows of a 2B-row call bit for bit -- the GEMM dispatch may depend on the row count --
+    so results across different intervals are comparable to fp noise, not bit for bit.
+    Out of scope: the two UNet models (their loop is written inline around the hipGraph capture), a schedule of cond_scale, and any claim
+    about map quality (no trained weights were at hand)."""
+
     def __init__(self, dim_h: int, backbone: str, cond_drop_prob: float, **backbone_kwargs) -> None:
         super().__init__()
         if backbone not in BACKBONES:
@@ -72,8 +93,10 @@ class _TransformerOsuFusion(nn.Module):
         return rt.forced_compute_dtype(torch.bfloat16 if self._full_bf16 else None)
 
     def _denoiser(self, a: torch.Tensor, c: torch.Tensor, cfg: bool):
-        """-> f(x (b, 6, n) fp32, t (nb,)) = the prediction (nb, 6, n), nb = 2b with guidance (conditional rows first), else b.  The audio
-        rows and the step-independent conditioning vector are computed here, once."""
+        """-> f(x (b, 6, n) fp32, t (nb,), guided=cfg) = the prediction (nb, 6, n), nb = 2b with guidance (conditional rows first), else b.
+        The audio rows and the step-independent conditioning vector are computed here, once.  A denoiser built with cfg also serves the
+        unguided call of a guidance interval, f(x, t, False): the conditional b rows alone, from the first b rows of the same audio rows
+        and conditioning vector and the first b entries of t."""
         net = self.unet
         b, n = a.shape[0], a.shape[-1]
         dtype = rt.compute_dtype(next(net.parameters()).dtype)
@@ -85,12 +108,15 @@ class _TransformerOsuFusion(nn.Module):
         else:
             static = net.embed_static(a, c, keep)
 
-        def f(x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
-            xin = torch.cat([x, x], 0) if cfg else x
-            cvec = (static + net.embed_time(t)).contiguous()
+        def f(x: torch.Tensor, t: torch.Tensor, guided: bool = cfg) -> torch.Tensor:
+            rows, st = a_rows, static
+            if cfg and not guided:
+                rows, st, t = a_rows[:b], static[:b], t[:b]
+            xin = torch.cat([x, x], 0) if cfg and guided else x
+            cvec = (st + net.embed_time(t)).contiguous()
             if self.backbone == "mmdit":
-                return net.denoise_rows(net.encode_x(xin, dtype), a_rows, cvec, n).contiguous()
-            return net.denoise_rows(net.encode_x(xin, a_rows, dtype), cvec, n).contiguous()
+                return net.denoise_rows(net.encode_x(xin, dtype), rows, cvec, n).contiguous()
+            return net.denoise_rows(net.encode_x(xin, rows, dtype), cvec, n).contiguous()
         return f
 
     def _windowed_denoiser(self, a: torch.Tensor, c: torch.Tensor, cfg: bool, window: int, stride: int, taper: str = "trapezoid",
@@ -101,10 +127,11 @@ class _TransformerOsuFusion(nn.Module):
         chunk), so the audio rows and the static conditioning vector are still computed once per call; the statistics pooling sees the
         window, as it does in training on sub-sequences.  Per step: one ops.window_gather of the iterate, one inner call per chunk with the
         step's t repeated per window, the halves of its [cond; null] result written into one (2, b W, 6, window) buffer (a single chunk's
-        result is that buffer already), one ops.window_fuse over R = nb rows."""
+        result is that buffer already), one ops.window_fuse over R = nb rows.  f(x, t, False) on a denoiser built with cfg: the
+        unguided call of a guidance interval, every chunk's inner denoiser on its conditional rows alone, nb = b."""
         b, n = a.shape[0], a.shape[-1]
         W = len(windowed.window_starts(n, window, stride))
-        rows, g = b * W, 2 if cfg else 1
+        rows = b * W
         a_w = ops.window_gather(a.float().contiguous(), window, stride)
         c_w = c.repeat_interleave(W, 0)
         step = rows if window_batch is None else min(int(window_batch), rows)
@@ -112,15 +139,17 @@ class _TransformerOsuFusion(nn.Module):
         inner = [self._denoiser(a_w[lo:hi], c_w[lo:hi], cfg) for lo, hi in chunks]
         weight = windowed.window_weight(window, stride, taper).to(a.device)
 
-        def f(x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        def f(x: torch.Tensor, t: torch.Tensor, guided: bool = cfg) -> torch.Tensor:
+            g = 2 if cfg and guided else 1
+            how = (False,) if cfg and not guided else ()     # the inner denoisers' own default otherwise
             x_w = ops.window_gather(x, window, stride)
-            t_w = t.view(g, b).repeat_interleave(W, 1)
+            t_w = t[:g * b].view(g, b).repeat_interleave(W, 1)
             if len(chunks) == 1:
-                pred = inner[0](x_w, t_w.reshape(-1))
+                pred = inner[0](x_w, t_w.reshape(-1), *how)
             else:
                 pred = torch.empty((g, rows, x.shape[1], window), dtype=torch.float32, device=x.device)
                 for (lo, hi), den in zip(chunks, inner):
-                    pred[:, lo:hi] = den(x_w[lo:hi], t_w[:, lo:hi].reshape(-1)).view(g, hi - lo, x.shape[1], window)
+                    pred[:, lo:hi] = den(x_w[lo:hi], t_w[:, lo:hi].reshape(-1), *how).view(g, hi - lo, x.shape[1], window)
             return ops.window_fuse(pred.view(g * rows, x.shape[1], window), weight, n, stride)
         return f
 
@@ -146,16 +175,22 @@ class _TransformerOsuFusion(nn.Module):
         rt.require_gpu(x)
         return x.float().contiguous()
 
-    def _run(self, describe, a, c, x, cond_scale, stop_after, keep_region=None, wp=None):
+    def _run(self, describe, a, c, x, cond_scale, stop_after, keep_region=None, wp=None, gd: Optional[guidance.Guidance] = None):
         """The sampling loop of the diffusion samplers; describe(b, cfg, cond_scale, device) -> the sampler's _Steps.  Draws, in this order:
         the start iterate (x None), the start blend's noise; then per pass of a step its own noise, its level blend's noise, the resample
-        draw -- each only where the sampler has one.  Per pass: the denoiser, the step, the blend of the known region, the resample."""
+        draw -- each only where the sampler has one.  Per pass: the denoiser, the step, the blend of the known region, the resample.
+        gd (guidance.plan; None: the loop as it was before it): with an interval, which steps are guided is decided here, before the loop,
+        from the sampler's per-step log-SNR -- the one host read; the passes of a step share its decision.  An unguided step calls the
+        denoiser on the conditional b rows and hands (pred, None) to the step; with gd.phi > 0 a guided step hands it
+        (ops.cfg_rescale(cond, null), None)."""
         x = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
         sp = describe(b, cfg, cond_scale, device)
         total = sp.coef.shape[0]
         steps = total if stop_after is None else min(stop_after, total)
+        gd = gd if cfg else None                           # cond_scale == 1: nothing to control
+        guided = guidance.guided_calls(sp.log_snr(), gd, cond_scale) if gd is not None and gd.bounded else None
         blender = inpaint.Blender(*keep_region, x, fresh=sp.fresh) if keep_region is not None else None
         if blender is not None and steps > 0:
             x = blender.level(x, sp.coef[0], *sp.start_cols)
@@ -165,9 +200,15 @@ class _TransformerOsuFusion(nn.Module):
             for i in range(steps):
                 passes = sp.resample if i < sp.last else 1
                 for u in range(passes):
-                    pred = f(x, sp.t_in[i])
+                    if guided is not None and not guided[i]:
+                        cond, null = f(x, sp.t_in[i], False), None
+                    else:
+                        pred = f(x, sp.t_in[i])
+                        cond, null = pred[:b], pred[b:] if cfg else None
+                        if gd is not None and gd.phi > 0.0:
+                            cond, null = ops.cfg_rescale(cond, null, cond_scale, gd.phi)[0], None
                     noise = torch.randn(x.shape, device=device) if i < sp.draw_steps else None
-                    x, state = sp.step(i, x, pred[:b], pred[b:] if cfg else None, noise, state)
+                    x, state = sp.step(i, x, cond, null, noise, state)
                     if blender is not None:
                         x = blender.exact(x) if i == sp.last else blender.level(x, sp.coef[i], *sp.step_cols)
                     if u < passes - 1:
@@ -189,6 +230,7 @@ class _Steps:
     resample: int = 1                   # the ancestral sampler's RePaint passes per step, with the factors of the way back one level:
     k_r: Optional[torch.Tensor] = None  # (S, b) x = k_r x + k_g z
     k_g: Optional[torch.Tensor] = None
+    log_snr: Optional[Callable] = None  # log_snr() -> S host floats, step i's log-SNR for a guidance interval; called at most once per run
 
 
 class DiffusionOsuFusionDiT(_TransformerOsuFusion):
@@ -204,7 +246,8 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
                known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
                window: Optional[int] = None, window_stride: Optional[int] = None, window_taper: str = "trapezoid",
-               window_batch: Optional[int] = None) -> torch.Tensor:
+               window_batch: Optional[int] = None, guidance_rescale: float = 0.0,
+               guidance_interval: Optional[Tuple[Optional[float], Optional[float]]] = None) -> torch.Tensor:
         """diffusion.py:59-77 on the transformer backbones.  Bit-reproducible.  (Attribute `stop_after`, None by default: return the iterate
         after that many of the sampling_timesteps steps, as models/diffusion.OsuFusion.)
 
@@ -213,11 +256,15 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
         columns (2, 3) of its row, the final step of a full run exactly; one fixed noise tensor (a clone of the start iterate), no new draw.
         With both None: no extra launch, the unmasked sampler's bits.
 
-        window, window_stride, window_taper, window_batch: windowed sampling, see _TransformerOsuFusion.WINDOW_DOC."""
+        window, window_stride, window_taper, window_batch: windowed sampling, see _TransformerOsuFusion.WINDOW_DOC.
+
+        guidance_rescale, guidance_interval: see _TransformerOsuFusion.GUIDANCE_DOC; a step's log-SNR is log(abar_t / (1 - abar_t)) of the
+        scheduler's cumulative alphas, in fp64."""
         masked = inpaint.check_pair(known, known_mask)
         wp = self._window_plan(a, window, window_stride, window_taper, window_batch)
+        gd = guidance.plan(guidance_rescale, guidance_interval)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
-            return self._run(self._ddim, a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None, wp)
+            return self._run(self._ddim, a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None, wp, gd)
 
     def _ddim(self, b, cfg, cond_scale, device) -> _Steps:
         self.scheduler.set_timesteps(self.sampling_timesteps)
@@ -227,7 +274,8 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
 
         def step(i, x, cond, null, noise, state):
             return ops.ddim_step(x, cond, null, cond_scale, coef[i]), None
-        return _Steps(coef, t_in, step, draw_steps=0, fresh=False, start_cols=(1, 0), step_cols=(2, 3), last=self.sampling_timesteps - 1)
+        return _Steps(coef, t_in, step, draw_steps=0, fresh=False, start_cols=(1, 0), step_cols=(2, 3), last=self.sampling_timesteps - 1,
+                      log_snr=lambda: guidance.ddim_log_snr(self.scheduler.alphas_cumprod, steps))
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"
@@ -286,7 +334,8 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
                known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None, resample: int = 1,
                window: Optional[int] = None, window_stride: Optional[int] = None, window_taper: str = "trapezoid",
-               window_batch: Optional[int] = None) -> torch.Tensor:
+               window_batch: Optional[int] = None, guidance_rescale: float = 0.0,
+               guidance_interval: Optional[Tuple[Optional[float], Optional[float]]] = None) -> torch.Tensor:
         """sampler = "ddpm": ancestral sampling over scheduler.get_sampling_timesteps: per step one denoiser call at log_snr(t) (2B rows with guidance) and one
         ops.ct_step (guidance, start prediction clamped to [-1, 1], posterior mean, noise).  Draws from the global generator, in this order:
         the start iterate torch.randn((B, 6, n)) when x is None, then one torch.randn of the iterate's shape per step, in step order; the
@@ -318,8 +367,13 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         nothing cancels), computed in fp32 torch once per call.  r (S - 1) + 1 denoiser calls for S steps.
 
         window, window_stride, window_taper, window_batch: windowed sampling, see _TransformerOsuFusion.WINDOW_DOC; the draws above are of
-        the full-length iterate's shape and keep their order."""
+        the full-length iterate's shape and keep their order.
+
+        guidance_rescale, guidance_interval: see _TransformerOsuFusion.GUIDANCE_DOC; a step's log-SNR is the fp32 value the denoiser is
+        given for it, under every sampler, read back once per call when an interval is given.  The RePaint passes of a step share its
+        decision; with dynamic_thresholding the quantile of a rescaled step is taken of the rescaled prediction."""
         masked = inpaint.check_pair(known, known_mask)
+        gd = guidance.plan(guidance_rescale, guidance_interval)
         resample = int(resample)
         if resample < 1:
             raise ValueError(f"resample must be >= 1 (got {resample})")
@@ -329,7 +383,7 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         wp = self._window_plan(a, window, window_stride, window_taper, window_batch)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
             describe = self._solver if self.sampler != "ddpm" else lambda *args: self._ancestral(*args, resample)
-            return self._run(describe, a, c, x, cond_scale, self.stop_after, keep_region, wp)
+            return self._run(describe, a, c, x, cond_scale, self.stop_after, keep_region, wp, gd)
 
     def _threshold(self, x, cond, null, cond_scale, row) -> Optional[torch.Tensor]:
         """The per-sample dynamic threshold of a step, one ops.ct_x0_quantile; None (the static clamp) without dynamic_thresholding."""
@@ -348,7 +402,7 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
             s = self._threshold(x, cond, null, cond_scale, coef[i])
             return ops.ct_solver_step(x, cond, null, cond_scale, coef[i], fac[i], x0_prev, noise, self.pred_objective, s)
         return _Steps(coef, log_snr, step, draw_steps=total if draws else 0, fresh=draws, start_cols=(ct.ALPHA, ct.SIGMA),
-                      step_cols=(ct.ALPHA_NEXT, ct.SIGMA_NEXT), last=total - 1)
+                      step_cols=(ct.ALPHA_NEXT, ct.SIGMA_NEXT), last=total - 1, log_snr=lambda: grid[:-1].tolist())
 
     def _ancestral(self, b, cfg, cond_scale, device, resample=1) -> _Steps:
         total = self.scheduler.timesteps
@@ -367,7 +421,8 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
             s = self._threshold(x, cond, null, cond_scale, coef[i])
             return ops.ct_step_ex(x, cond, null, cond_scale, coef[i], noise, self.pred_objective, s), None
         return _Steps(coef, log_snr, step, draw_steps=total - 1, fresh=True, start_cols=(ct.ALPHA, ct.SIGMA),
-                      step_cols=(ct.ALPHA_NEXT, ct.SIGMA_NEXT), last=total - 1, resample=resample, k_r=k_r, k_g=k_g)
+                      step_cols=(ct.ALPHA_NEXT, ct.SIGMA_NEXT), last=total - 1, resample=resample, k_r=k_r, k_g=k_g,
+                      log_snr=lambda: coef[:, 0, ct.LOG_SNR].tolist())
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"
@@ -404,28 +459,40 @@ class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0,
                known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
                window: Optional[int] = None, window_stride: Optional[int] = None, window_taper: str = "trapezoid",
-               window_batch: Optional[int] = None) -> torch.Tensor:
+               window_batch: Optional[int] = None, guidance_rescale: float = 0.0,
+               guidance_interval: Optional[Tuple[Optional[float], Optional[float]]] = None) -> torch.Tensor:
         """rectified_flow.py:57-79 on the transformer backbones: the fixed-grid midpoint loop, 2 * (S - 1) evaluations.  Bit-reproducible.
         known / known_mask (both or neither): masked generation as in models/rectified_flow.OsuFusion.sample_masked -- every state handed to the
         backbone blended at (t, 1 - t), the end of the last interval exactly, one fixed noise tensor, no new draw.
 
-        window, window_stride, window_taper, window_batch: windowed sampling, see _TransformerOsuFusion.WINDOW_DOC."""
+        window, window_stride, window_taper, window_batch: windowed sampling, see _TransformerOsuFusion.WINDOW_DOC.
+
+        guidance_rescale, guidance_interval: see _TransformerOsuFusion.GUIDANCE_DOC; an evaluation's log-SNR is 2 log(t / (1 - t)) of its
+        time, in fp64, -inf at t = 0, and both evaluations of a midpoint step decide for themselves.  On a rescaled evaluation
+        ops.cfg_rescale replaces the ops.axpby_rows combine."""
         masked = inpaint.check_pair(known, known_mask)
         wp = self._window_plan(a, window, window_stride, window_taper, window_batch)
+        gd = guidance.plan(guidance_rescale, guidance_interval)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
-            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None, wp)
+            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None, wp, gd)
 
-    def _sample(self, a, c, x, cond_scale, keep_region=None, wp=None):
+    def _sample(self, a, c, x, cond_scale, keep_region=None, wp=None, gd: Optional[guidance.Guidance] = None):
         x = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
+        gd = gd if cfg else None                           # cond_scale == 1: nothing to control
         ones = torch.ones(b, dtype=torch.float32, device=device)
         with self._dtype_ctx():
             den = self._make_denoiser(a, c, cfg, wp)
 
             def f(t: float, y: torch.Tensor) -> torch.Tensor:
-                out = den(y, torch.full((2 * b if cfg else b,), t, dtype=torch.float32, device=device))
-                if cfg:                                    # null + (cond - null) * s  ==  (1 - s) * null + s * cond
+                tt = torch.full((2 * b if cfg else b,), t, dtype=torch.float32, device=device)
+                if gd is not None and gd.bounded and not gd.contains(guidance.flow_log_snr(t)):
+                    return den(y, tt, False)               # outside the interval: the conditional b rows are the flow
+                out = den(y, tt)
+                if gd is not None and gd.phi > 0.0:
+                    out = ops.cfg_rescale(out[:b], out[b:], cond_scale, gd.phi)[0]
+                elif cfg:                                  # null + (cond - null) * s  ==  (1 - s) * null + s * cond
                     out = ops.axpby_rows(out[b:].contiguous(), out[:b].contiguous(), ones * (1.0 - cond_scale), ones * cond_scale)
                 return out
 

@@ -763,6 +763,14 @@ def window_fuse(pred: torch.Tensor, weight: torch.Tensor, n: int, stride: int, o
     return windowed.window_fuse(pred, weight, n, stride, out)
 
 
+def cfg_rescale(cond: torch.Tensor, null: torch.Tensor, cond_scale: float, phi: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """CFG rescale (Lin et al. 2024, 3.4): -> (out, factor), out = factor[b] (null + (cond - null) cond_scale) with
+    factor[b] = phi std_b(cond) / std_b(guided) + (1 - phi), the per-sample deviations from fp64 sums; two launches, deterministic.  The
+    allocating wrapper lives in osufusion_amd/guidance.py (its guarded-memory cases in tests/test_guidance_gpu.py)."""
+    from . import guidance
+    return guidance.cfg_rescale(cond, null, cond_scale, phi)
+
+
 def mse(pred: torch.Tensor, target: torch.Tensor, orig_len: Optional[torch.Tensor], want_grad: bool, weight: Optional[torch.Tensor] = None):
     """weight: per-sample fp32 (B,) loss weights (osuf_mse_w); None is osuf_mse."""
     B, Dc, Lx = pred.shape
