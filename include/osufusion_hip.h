@@ -474,7 +474,10 @@ int osuf_adapter_finish(const float* tb, const float* sg, float* dB, const float
  *      (autocast semantics), OSUF_DT_F32 is exact f32.  in_act: 0 none, 1 SiLU applied to x; out_act: 0 none, 2 sigmoid.
  *        fwd: y = out_act(in_act(x) W^T + b)
  *        bwd: dz = dy * out_act'(y); dx = (dz W) * in_act'(x) [dx may be NULL]; dW (+)= dz^T in_act(x), db += colsum(dz)
- *             [dW / db may be NULL; db needs dW] ---- */
+ *             [dW / db may be NULL; db needs dW]
+ *      x, y, dy and dx are rows at strides of their own (ldx >= K, ldy / lddy >= N, lddx >= K; OSUF_EINVAL for lddx < K); a kernel
+ *      writes the N columns of y and the K columns of dx only -- columns between the width and the stride keep what they held, also
+ *      where dx is zeroed first for the atomic slices. ---- */
 int osuf_skinny_fwd(int mode, const float* x, long ldx, const float* W, const float* bias, float* y, long ldy, int M, int N, int K,
                     int in_act, int out_act, hipStream_t stream);
 int osuf_skinny_bwd(int mode, const float* dy, long lddy, const float* y, long ldy, const float* x, long ldx, const float* W,

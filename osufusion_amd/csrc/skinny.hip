@@ -318,6 +318,12 @@ __global__ __launch_bounds__(256) void skinny_dw_kernel(const float* __restrict_
 }
 
 static bool sk_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// zero the K columns of M rows of dx at pitch lddx, and nothing else: the slack columns of a strided dx belong to the caller, and the
+// last row ends at column K (one contiguous memset when lddx == K; the 2-D form is a memset node under capture as well)
+static hipError_t sk_zero_dx(float* dx, long lddx, int M, int K, hipStream_t stream) {
+  if (lddx == K) return hipMemsetAsync(dx, 0, (size_t)M * K * sizeof(float), stream);
+  return hipMemset2DAsync(dx, (size_t)lddx * sizeof(float), 0, (size_t)K * sizeof(float), (size_t)M, stream);
+}
 static bool sk_bad(int M, int N, int K, int in_act, int out_act) {
   return M <= 0 || N <= 0 || K <= 0 || (in_act != SK_ACT_NONE && in_act != SK_ACT_SILU) ||
          (out_act != SK_ACT_NONE && out_act != SK_ACT_SIGMOID);
@@ -338,7 +344,7 @@ extern "C" int osuf_skinny_fwd(int mode, const float* x, long ldx, const float* 
 extern "C" int osuf_skinny_bwd(int mode, const float* dy, long lddy, const float* y, long ldy, const float* x, long ldx, const float* W,
                                float* dx, long lddx, float* dW, float* db, int M, int N, int K, int in_act, int out_act, int accumulate,
                                hipStream_t stream) {
-  if (!dy || !x || !W || sk_bad(M, N, K, in_act, out_act) || (out_act != SK_ACT_NONE && !y)) return OSUF_EINVAL;
+  if (!dy || !x || !W || sk_bad(M, N, K, in_act, out_act) || (out_act != SK_ACT_NONE && !y) || (dx && lddx < K)) return OSUF_EINVAL;
   if (dx) {
     const int ktiles = (K + 31) / 32;
     int nsplit = (256 + ktiles - 1) / ktiles;                 // about one workgroup per CU
@@ -349,7 +355,10 @@ extern "C" int osuf_skinny_bwd(int mode, const float* dy, long lddy, const float
     int nps = (N + nsplit - 1) / nsplit;
     nps = (nps + 63) / 64 * 64;                                // whole 64-row steps (4 waves x 16) and 8-float alignment of the slices
     nsplit = (N + nps - 1) / nps;
-    if (nsplit > 1) (void)hipMemsetAsync(dx, 0, (size_t)M * lddx * sizeof(float), stream);
+    if (nsplit > 1) {
+      hipError_t e = sk_zero_dx(dx, lddx, M, K, stream);
+      if (e != hipSuccess) return (int)e;
+    }
     const dim3 grid(ktiles, nsplit);
     const bool vec = N % 8 == 0 && lddy % 4 == 0 && sk_al16(dy) && (out_act == SK_ACT_NONE || (ldy % 4 == 0 && sk_al16(y)));
     void (*kern)(const float*, long, const float*, long, const float*, const float*, long, float*, long, int, int, int, int, int, int) =
@@ -384,7 +393,7 @@ extern "C" int osuf_skinny_fwd_group(int mode, const float* x, long ldx, const o
 extern "C" int osuf_skinny_dx_group(int mode, const osuf_linear_desc* descs, int n, int total_slices, const float* x, long ldx, float* dx, long lddx,
                                     int M, int K, int in_act, hipStream_t stream) {
   if (sk_group_bad(x, ldx, M, K, in_act) || !descs || n <= 0 || total_slices <= 0 || !dx || lddx < K) return OSUF_EINVAL;
-  hipError_t e = hipMemsetAsync(dx, 0, (size_t)M * lddx * sizeof(float), stream);
+  hipError_t e = sk_zero_dx(dx, lddx, M, K, stream);
   if (e != hipSuccess) return (int)e;
   const dim3 grid((K + 31) / 32, total_slices);
   if (mode == OSUF_DT_BF16) hipLaunchKernelGGL(skinny_dx_group_kernel<1>, grid, dim3(256), 0, stream, descs, n, x, ldx, dx, lddx, M, K, in_act);
