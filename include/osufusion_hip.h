@@ -420,6 +420,15 @@ int osuf_adamw_ema(float* p, const float* g, float* m, float* v, long n, float l
 int osuf_ema_update(const float* p, float* ema, long ema_ld, long n, int tracks, float d0, float d1, float d2, float d3,
                     hipStream_t stream);
 int osuf_swap(float* a, float* b, long n, hipStream_t stream);
+/* Linear combination of K fp32 buffers of n elements in fp64 (post-hoc EMA reconstruction from snapshots).  src and w are HOST arrays of
+ * K device pointers and K weights, 1 <= K <= 8; they travel to the kernel by value.  Per element a = (flags & 1) ? acc[i] : 0, then
+ * a = fma(w[k], (double)src[k][i], a) for k = 0 .. K-1 in that order (one rounding per step); acc[i] = a if acc is not NULL and
+ * out[i] = (float)a if out is not NULL.  The chain is sequential and fp64 is stored exactly: a source list cut into several calls (flags
+ * = 1 on all but the first) gives the bits of one call.  w[k] == 0 is a select: source k is not read (it may be NULL or hold NaN) and a
+ * stays as it is.  Four elements per lane when every source and out are 16-byte aligned and acc is 32-byte aligned, one per lane
+ * otherwise, with the same bits.  n == 0 launches nothing.  OSUF_EINVAL, nothing launched: K outside 1..8, n < 0, a NaN weight, a NULL
+ * source under a non-zero weight, acc and out both NULL, flags & 1 with a NULL acc. */
+int osuf_lincomb(const float* const* src, const double* w, int K, double* acc, float* out, long n, int flags, hipStream_t stream);
 int osuf_clip_coef(const double* sumsq, float max_norm, float base, float* coef, float* total_norm, hipStream_t stream);
 int osuf_cast_f32_bf16(const float* src, void* dst, long n, hipStream_t stream);
 /* GEMM operand layouts of one conv / linear weight, both from the fp32 master (O, I, k) in one pass -- what the reference gets

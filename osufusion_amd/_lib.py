@@ -88,6 +88,7 @@ SIGNATURES = {
     "osuf_adamw_ema": [P, P, P, P, L, F, F, F, F, F, I, P, P, L, I, F, F, F, F, P],
     "osuf_ema_update": [P, P, L, L, I, F, F, F, F, P],
     "osuf_swap": [P, P, L, P],
+    "osuf_lincomb": [P, P, I, P, P, L, I, P],
     "osuf_clip_coef": [P, F, F, P, P, P],
     "osuf_cast_f32_bf16": [P, P, L, P],
     "osuf_pack_weight": [P, I, I, I, I, P, L, L, P, L, L, I, P],

@@ -233,6 +233,59 @@ __global__ __launch_bounds__(256) void swap_kernel(float* a, float* b, long n) {
   }
 }
 
+// ---- linear combination of up to eight fp32 buffers in an fp64 accumulator (post-hoc EMA: osufusion_amd/posthoc_ema.py) ----------------
+// a = CONT ? acc[i] : 0;  a = fma(w[k], (double)src[k][i], a) for k = 0..K-1 in that order;  acc[i] = a (if acc);  out[i] = (float)a (if
+// out).  The chain is sequential in k and fp64 is stored exactly, so a list of sources cut into several launches (CONT on all but the
+// first) gives the bits of one launch.  Pointers and weights travel by value; K is a template parameter so that every index into them is
+// a constant and all K loads are issued before the first fma.  The host drops the sources whose weight is zero before the launch (K = 0
+// is then possible: the accumulator alone), so a skipped source costs no branch here and is never read.
+struct LincombArgs { const float* src[8]; double w[8]; };
+typedef __attribute__((ext_vector_type(2))) double f64x2;
+
+__device__ __forceinline__ double lincomb_step(double w, float x, double a) {
+#pragma clang fp contract(off)
+  return __builtin_fma(w, (double)x, a);
+}
+
+// VEC: four elements per lane (every pointer 16-byte aligned, acc 32-byte) and a scalar tail; otherwise one element per lane.
+template <int K, bool VEC>
+__global__ __launch_bounds__(256) void lincomb_kernel(LincombArgs a, double* acc, float* out, long n, int cont) {
+  if constexpr (VEC) {
+    const long n4 = n >> 2;
+    GRID_STRIDE(i, n4) {
+      f32x4 x[K ? K : 1];
+#pragma unroll
+      for (int k = 0; k < K; ++k) x[k] = reinterpret_cast<const f32x4*>(a.src[k])[i];
+      f64x2 lo = {0.0, 0.0}, hi = {0.0, 0.0};
+      if (cont) { lo = reinterpret_cast<const f64x2*>(acc)[2 * i]; hi = reinterpret_cast<const f64x2*>(acc)[2 * i + 1]; }
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        lo[0] = lincomb_step(a.w[k], x[k][0], lo[0]);
+        lo[1] = lincomb_step(a.w[k], x[k][1], lo[1]);
+        hi[0] = lincomb_step(a.w[k], x[k][2], hi[0]);
+        hi[1] = lincomb_step(a.w[k], x[k][3], hi[1]);
+      }
+      if (acc) { reinterpret_cast<f64x2*>(acc)[2 * i] = lo; reinterpret_cast<f64x2*>(acc)[2 * i + 1] = hi; }
+      if (out) {
+        f32x4 o; o[0] = (float)lo[0]; o[1] = (float)lo[1]; o[2] = (float)hi[0]; o[3] = (float)hi[1];
+        reinterpret_cast<f32x4*>(out)[i] = o;
+      }
+    }
+  }
+  const long first = VEC ? (n >> 2) << 2 : 0;               // VEC: the n % 4 elements left over; else all of them
+  GRID_STRIDE(j, n - first) {
+    const long i = first + j;
+    float x[K ? K : 1];
+#pragma unroll
+    for (int k = 0; k < K; ++k) x[k] = a.src[k][i];
+    double v = cont ? acc[i] : 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v = lincomb_step(a.w[k], x[k], v);
+    if (acc) acc[i] = v;
+    if (out) out[i] = (float)v;
+  }
+}
+
 // clip coefficient on device: coef = min(1, max_norm / (sqrt(sumsq) + 1e-6)) * base   (torch clip_grad_norm_ semantics)
 __global__ void clip_coef_kernel(const double* sumsq, float max_norm, float base, float* coef, float* total_norm) {
   const float tn = (float)sqrt(*sumsq);
@@ -366,6 +419,43 @@ extern "C" int osuf_swap(float* a, float* b, long n, hipStream_t stream) {
   if (n <= 0 || !a || !b || !al16(a) || !al16(b)) return OSUF_EINVAL;
   if (a == b || (a < b ? b - a : a - b) < n) return OSUF_EINVAL;       // the same or overlapping buffers
   hipLaunchKernelGGL(swap_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, stream, a, b, n);
+  return osuf_launch_status();
+}
+
+template <int K>
+static void lincomb_launch(const LincombArgs& a, double* acc, float* out, long n, int cont, bool vec, hipStream_t stream) {
+  if (vec) hipLaunchKernelGGL((lincomb_kernel<K, true>), dim3(ew_grid(n / 4 + 1)), dim3(256), 0, stream, a, acc, out, n, cont);
+  else hipLaunchKernelGGL((lincomb_kernel<K, false>), dim3(ew_grid(n)), dim3(256), 0, stream, a, acc, out, n, cont);
+}
+
+// src and w are HOST arrays.  flags & 1: continue from acc.
+extern "C" int osuf_lincomb(const float* const* src, const double* w, int K, double* acc, float* out, long n, int flags,
+                            hipStream_t stream) {
+  const int cont = flags & 1;
+  if (!src || !w || K < 1 || K > 8 || n < 0 || (!acc && !out) || (cont && !acc)) return OSUF_EINVAL;
+  LincombArgs a{};
+  int used = 0;
+  bool vec = (reinterpret_cast<uintptr_t>(acc) & 31) == 0 && al16(out);
+  for (int k = 0; k < K; ++k) {
+    if (w[k] != w[k]) return OSUF_EINVAL;
+    if (w[k] == 0.0) continue;                             // a select: the source is neither read nor required to exist
+    if (!src[k]) return OSUF_EINVAL;
+    vec = vec && al16(src[k]);
+    a.src[used] = src[k];
+    a.w[used++] = w[k];
+  }
+  if (n == 0) return OSUF_OK;
+  switch (used) {
+    case 0: lincomb_launch<0>(a, acc, out, n, cont, vec, stream); break;
+    case 1: lincomb_launch<1>(a, acc, out, n, cont, vec, stream); break;
+    case 2: lincomb_launch<2>(a, acc, out, n, cont, vec, stream); break;
+    case 3: lincomb_launch<3>(a, acc, out, n, cont, vec, stream); break;
+    case 4: lincomb_launch<4>(a, acc, out, n, cont, vec, stream); break;
+    case 5: lincomb_launch<5>(a, acc, out, n, cont, vec, stream); break;
+    case 6: lincomb_launch<6>(a, acc, out, n, cont, vec, stream); break;
+    case 7: lincomb_launch<7>(a, acc, out, n, cont, vec, stream); break;
+    default: lincomb_launch<8>(a, acc, out, n, cont, vec, stream); break;
+  }
   return osuf_launch_status();
 }
 

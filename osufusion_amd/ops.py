@@ -820,6 +820,27 @@ def swap(a: torch.Tensor, b: torch.Tensor) -> None:
     call("osuf_swap", _p(a), _p(b), a.numel(), _stream())
 
 
+LINCOMB_MAX = 8                                            # sources per osuf_lincomb launch
+
+
+def lincomb(srcs, weights, acc: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, cont: bool = False) -> None:
+    """a = (acc if cont else 0); a = fma(weights[k], srcs[k], a) in fp64 for k in order; acc <- a (fp64), out <- float32(a).  Up to
+    LINCOMB_MAX contiguous fp32 buffers of one length; a source under a zero weight is not read."""
+    import ctypes
+    K = len(srcs)
+    assert K == len(weights) and (acc is not None or out is not None)
+    ref = acc if acc is not None else out
+    n = ref.numel()
+    for s in srcs:
+        assert s.dtype == torch.float32 and s.is_contiguous() and s.numel() == n and s.device == ref.device and s.is_cuda
+    assert acc is None or (acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == n and acc.is_cuda)
+    assert out is None or (out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n and out.device == ref.device)
+    ptrs = (ctypes.c_void_p * max(K, 1))(*[s.data_ptr() for s in srcs])
+    ws = (ctypes.c_double * max(K, 1))(*[float(w) for w in weights])
+    call("osuf_lincomb", ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(ws, ctypes.c_void_p), K, _p(acc), _p(out), n, 1 if cont else 0,
+         _stream())
+
+
 def clip_coef(sumsq: torch.Tensor, max_norm: float, base: float, coef: torch.Tensor, total_norm: Optional[torch.Tensor]) -> None:
     call("osuf_clip_coef", _p(sumsq), float(max_norm), float(base), _p(coef), _p(total_norm), _stream())
 

@@ -420,14 +420,28 @@ class Trainer:
 
     ema = an EMAConfig or up to four (osufusion_amd/ema.py): the AdamW launch also moves that many exponential moving averages of the
     weights, once per optimizer step (not per micro-batch); they are re-laid out with the parameters, need no communication (every rank
-    holds the same parameters) and are read through ema_weights() / ema_state_dict().  ema=None issues exactly the launches of before."""
+    holds the same parameters) and are read through ema_weights() / ema_state_dict().  ema=None issues exactly the launches of before.
+
+    ema_snapshots = posthoc_ema.SnapshotConfig(dir, every): after every optimizer step k with k % every == 0 (once per optimizer step, not
+    per micro-batch; rank 0 only) the kind="power" tracks are written to a posthoc_ema.SnapshotStore, from which posthoc_ema.reconstruct /
+    posthoc_weights() rebuild the average for any other sigma_rel or an earlier end point.  A run resumed from a checkpoint without EMA
+    state restarts its tracks as copies of the loaded weights: snapshots from before and after such a restart do not belong to one
+    averaging profile.  Each file records ema_step next to the step, and reconstruct refuses a store whose files disagree on their
+    difference -- write the resumed run's snapshots to a directory of their own.  ema_snapshots=None: no launch, no file, no changed bit."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 1e-2, clip_grad_norm: float = 0.0,
                  bucket_mib: float = 64.0, compute_dtype: Optional[torch.dtype] = torch.bfloat16,
                  gradient_accumulation_steps: int = 1, overlap: bool = True, reorder_buckets: bool = True,
-                 comm_dtype: Optional[torch.dtype] = None, ema=None) -> None:
+                 comm_dtype: Optional[torch.dtype] = None, ema=None, ema_snapshots=None) -> None:
         assert gradient_accumulation_steps >= 1
         ema = as_tracks(ema)                                # an EMAConfig or up to four (ValueError) before anything is re-homed
+        self._snap_cfg, self._snap_tracks, self.snapshots = ema_snapshots, [], None
+        if ema_snapshots is not None:
+            from .posthoc_ema import SnapshotStore
+            self._snap_tracks = [j for j, c in enumerate(ema) if c.kind == "power"]
+            if not self._snap_tracks:
+                raise ValueError("ema_snapshots stores the kind='power' EMA tracks and this trainer keeps none (its ema= argument)")
+            self.snapshots = SnapshotStore(ema_snapshots.dir)
         self.model = model
         self.flat = FlatParameters(model)
         self.reducer = GradReducer(self.flat, bucket_mib, overlap=overlap, comm_dtype=comm_dtype)
@@ -485,7 +499,18 @@ class Trainer:
             self._reorder_pending = False
             self.apply_observed_order()
         Fn.refresh_packs()                                  # every packed GEMM operand went stale with that step: one grouped launch
+        if self._snap_cfg is not None and self.opt.step_count % self._snap_cfg.every == 0:
+            self.write_ema_snapshot()
         return loss.detach(), total_norm
+
+    def write_ema_snapshot(self) -> None:
+        """Every power track as it stands, by parameter name, into the snapshot store (rank 0 only)."""
+        if self.reducer.enabled and dist.get_rank(self.reducer.group) != 0:
+            return
+        named = self.opt._named_slices(self.model)
+        rows = [torch.cat([self.opt.ema_track(j)[o:o + p.numel()] for _, p, o in named]) for j in self._snap_tracks]
+        self.snapshots.write(self.opt.step_count, [self.opt.ema_cfgs[j].power_gamma() for j in self._snap_tracks],
+                             [k for k, _, _ in named], [list(p.shape) for _, p, _ in named], torch.stack(rows), ema_step=self.opt.ema_step)
 
     def apply_observed_order(self) -> None:
         """Re-lay the flat buffers (parameters, gradients, Adam moments) out in the gradient-completion order of the last
@@ -554,6 +579,8 @@ class Trainer:
     # -- the averaged weights ------------------------------------------------------------------------------------------------
     def _not_swapped(self, what: str) -> None:
         if self._ema_swapped is not None:
+            if self._ema_swapped == "post-hoc":
+                raise RuntimeError(f"Trainer.{what} inside posthoc_weights(): the reconstructed average stands in for the live weights")
             raise RuntimeError(f"Trainer.{what} inside ema_weights(): EMA track {self._ema_swapped} stands in for the live weights")
 
     @contextmanager
@@ -572,6 +599,40 @@ class Trainer:
             yield self.model
         finally:
             self._swap_with(e)
+            self._ema_swapped = None
+
+    @contextmanager
+    def posthoc_weights(self, source, sigma_rel: Optional[float] = None, gamma: Optional[float] = None, at_step: Optional[int] = None,
+                        profile: str = "discrete", max_resident: int = 8):
+        """ema_weights() for an average that no track holds.  `source` is a posthoc_ema.SnapshotStore (or its directory), reconstructed
+        here for `sigma_rel` or `gamma` at `at_step`, or the {name: tensor} dict of an earlier posthoc_ema.reconstruct.  The values are laid
+        out as flat.data is (a buffer of model size, freed on exit) and exchanged with it exactly as ema_weights() exchanges a track:
+        osuf_swap, a new weight epoch, a re-pack; on exit the live weights are back bit for bit.  The same RuntimeError guards apply."""
+        self._not_swapped("posthoc_weights")
+        if self.micro:
+            raise RuntimeError("Trainer.posthoc_weights in the middle of a gradient-accumulation window")
+        if isinstance(source, dict):
+            if not (sigma_rel is None and gamma is None and at_step is None):
+                raise ValueError("a {name: tensor} dict is already reconstructed: sigma_rel, gamma and at_step go to posthoc_ema.reconstruct")
+            named = source
+        else:
+            from .posthoc_ema import reconstruct
+            named, _ = reconstruct(source, sigma_rel=sigma_rel, gamma=gamma, at_step=at_step, device=self.flat.data.device, profile=profile,
+                                   max_resident=max_resident)
+        slices = self.opt._named_slices(self.model)
+        if set(named) != {k for k, _, _ in slices}:
+            raise ValueError("the reconstructed weights do not name this model's trainable parameters")
+        buf = self.flat.data.clone()                        # the padding between parameters keeps its bits
+        for k, p, o in slices:
+            if tuple(named[k].shape) != tuple(p.shape):
+                raise ValueError(f"reconstructed {k}: shape {tuple(named[k].shape)}, {tuple(p.shape)} in the model")
+            buf[o:o + p.numel()].view_as(p).copy_(named[k])
+        self._swap_with(buf)
+        self._ema_swapped = "post-hoc"
+        try:
+            yield self.model
+        finally:
+            self._swap_with(buf)
             self._ema_swapped = None
 
     def _swap_with(self, e: torch.Tensor) -> None:
