@@ -395,6 +395,27 @@ int osuf_window_fuse(const float* pred, const float* weight, float* out, int R, 
 long osuf_cfg_rescale_workspace_bytes(int B, long per_sample);
 int osuf_cfg_rescale(const float* cond, const float* nullp, float cond_scale, float phi, void* ws, float* factor, float* out, int B,
                      long per_sample, hipStream_t stream);
+/* Scaled error norm of an embedded Runge-Kutta step (the adaptive ODE samplers, osufusion_amd/ode.py; torchdiffeq's RMS norm per sample).
+ * y0, y1: fp32 (B, per_sample), contiguous, the state before the step and the proposed state after it.  k, e and step are HOST arrays: S
+ * device pointers to the fp32 (B, per_sample) stage derivatives, the S error weights b_j - b*_j, 1 <= S <= 7, and step = {dt, atol, rtol};
+ * all three travel to the kernel by value.  Per element, in fp64:
+ *   a = fma(e[j], (double)k[j][i], a) for j = 0 .. S-1 in that order from a = 0;  err = dt a;  tol = atol + rtol max(|y0_i|, |y1_i|);
+ *   term = (err / tol)^2, every operation after the chain rounded on its own; term = 0 as a select where err == 0 (tol == 0 without an
+ *   error is no NaN);  ratio[b] = sqrt(sum_i term / per_sample), fp64 (B,).
+ * e[j] == 0 is a select: stage j is not read (it may be NULL or hold NaN).  A NaN or Inf in a stage that is read, and a NaN in y0 or
+ * y1 (the maximum keeps a NaN of either state) at an element whose error is not 0, reach that sample's ratio and no other sample's.  What
+ * the formula itself absorbs stays absorbed: an element whose error is exactly 0 contributes 0 whatever its states hold, and an infinite
+ * state makes an infinite tolerance, so a finite error there contributes 0 too.  Two launches on `stream`, no atomics: the first, over (ceil(per_sample / 4096), min(B, 65535))
+ * workgroups, writes every 4096-element chunk's sum to ws[b][chunk] (fp64), the second adds a sample's chunks in index order and writes
+ * ratio[b].  Chunks, lanes and the order of every sum depend on per_sample and on the path alone: sample b's bits do not depend on B or on
+ * scheduling.  ws: osuf_rk_error_workspace_bytes(B, per_sample) bytes, 8-byte aligned, written before it is read.  No allocation, no host
+ * sync, graph-capturable.  The four-wide path is taken when per_sample % 4 == 0 and y0, y1 and every stage that is read are 16-byte aligned;
+ * anything else takes the scalar path (a sample's sum may differ between the two in the last bits of fp64).
+ * OSUF_EINVAL, nothing launched: a NULL y0, y1, k, e, step, ws or ratio; a NULL stage under a non-zero weight; S outside 1..7; B < 1;
+ * per_sample < 1; a NaN weight; dt, atol or rtol not finite; atol < 0; rtol < 0; atol == rtol == 0; ws not 8-byte aligned. */
+long osuf_rk_error_workspace_bytes(int B, long per_sample);
+int osuf_rk_error(const float* y0, const float* y1, const float* const* k, const double* e, int S, const double* step, void* ws,
+                  double* ratio, int B, long per_sample, hipStream_t stream);
 int osuf_mse(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum, int B, int Dch, int L,
              hipStream_t stream);
 /* osuf_mse with per-sample weights w[B] (min-SNR-gamma): loss_sum += sum_b w[b] sum_{d, l < len_b} (pred - target)^2 and

@@ -81,6 +81,8 @@ SIGNATURES = {
     "osuf_window_fuse": [P, P, P, I, I, I, I, I, I, P],
     "osuf_cfg_rescale_workspace_bytes": [I, L],
     "osuf_cfg_rescale": [P, P, F, F, P, P, P, I, L, P],
+    "osuf_rk_error_workspace_bytes": [I, L],
+    "osuf_rk_error": [P, P, P, P, I, P, P, P, I, L, P],
     "osuf_mse": [P, P, P, P, P, I, I, I, P],
     "osuf_mse_w": [P, P, P, P, P, P, I, I, I, P],
     "osuf_sqnorm": [P, L, P, P],

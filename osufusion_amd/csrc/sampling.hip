@@ -644,6 +644,82 @@ __global__ __launch_bounds__(256) void cfg_rescale_apply_kernel(const float* con
   }
 }
 
+// ---- scaled error norm of an embedded Runge-Kutta step (the adaptive ODE samplers: osufusion_amd/ode.py) --------------------------------------
+// ratio[b] = sqrt(mean_i (err_i / tol_i)^2), err = dt sum_j e_j k_j and tol = atol + rtol max(|y0|, |y1|), everything in fp64.  The structure is
+// osuf_cfg_rescale's: pass 1 over (chunks of CFGR_CHUNK elements, samples) writes every chunk's sum of terms to ws[b][chunk]; pass 2, one lane
+// per sample, adds the sample's chunks in index order and takes the root.  No atomics, a fixed order for every sum: sample b's bits depend on
+// per_sample and on the path alone.  Up to nine streams are read once, four floats per lane and stream on the four-wide path; the stage count is a
+// template parameter so that every index into the by-value pointer table is a constant and all loads of an element group are issued before
+// the first fma.  The host drops the stages whose weight is zero before the launch, as osuf_lincomb's does: they are never read.
+struct RkErrArgs { const float* k[7]; double e[7]; };
+
+// (err / tol)^2; 0 as a select where err == 0, so that tol == 0 without an error is no 0 / 0.  The maximum keeps a NaN of either state (fmax
+// would drop it).  Every operation is rounded on its own but the chain, which is one fma per stage.
+__device__ __forceinline__ double rk_term(double a, double dt, float y0, float y1, double atol, double rtol) {
+#pragma clang fp contract(off)
+  const double err = dt * a;
+  const double m0 = fabs((double)y0), m1 = fabs((double)y1);
+  const double m = (m0 > m1 || m0 != m0) ? m0 : m1;
+  const double tol = atol + rtol * m;
+  const double q = err / tol;
+  return err == 0.0 ? 0.0 : q * q;
+}
+
+// grid (G, min(B, 65535)), G = ceil(per_sample / CFGR_CHUNK).  VEC: per_sample % 4 == 0 and y0, y1 and every stage read 16-byte aligned.
+template <int S, bool VEC>
+__global__ __launch_bounds__(256) void rk_error_sums_kernel(const float* y0, const float* y1, RkErrArgs a, double dt, double atol, double rtol,
+                                                            double* ws, int B, long per_sample) {
+  __shared__ double part[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long lo = (long)blockIdx.x * CFGR_CHUNK;
+  const long hi = lo + CFGR_CHUNK < per_sample ? lo + CFGR_CHUNK : per_sample;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const long base = (long)b * per_sample;
+    double s = 0.0;
+    if (VEC) {
+      for (long j = lo + 4 * tid; j < hi; j += 1024) {         // hi is a multiple of 4: the group lies within the chunk
+        f32x4 kv[S ? S : 1];
+#pragma unroll
+        for (int st = 0; st < S; ++st) kv[st] = *reinterpret_cast<const f32x4*>(a.k[st] + base + j);
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(y0 + base + j), v1 = *reinterpret_cast<const f32x4*>(y1 + base + j);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          double acc = 0.0;
+#pragma unroll
+          for (int st = 0; st < S; ++st) acc = __builtin_fma(a.e[st], (double)kv[st][c], acc);
+          s += rk_term(acc, dt, v0[c], v1[c], atol, rtol);
+        }
+      }
+    } else {
+      for (long j = lo + tid; j < hi; j += 256) {
+        float kv[S ? S : 1];
+#pragma unroll
+        for (int st = 0; st < S; ++st) kv[st] = a.k[st][base + j];
+        double acc = 0.0;
+#pragma unroll
+        for (int st = 0; st < S; ++st) acc = __builtin_fma(a.e[st], (double)kv[st], acc);
+        s += rk_term(acc, dt, y0[base + j], y1[base + j], atol, rtol);
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (tid == 0) ws[(long)b * gridDim.x + blockIdx.x] = ((part[0] + part[1]) + part[2]) + part[3];
+    __syncthreads();                                          // part is written again for the next sample
+  }
+}
+
+// one lane per sample: the G chunk sums in index order, then sqrt(sum / per_sample)
+__global__ __launch_bounds__(64) void rk_error_ratio_kernel(const double* ws, double* ratio, int B, long G, long per_sample) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const double* p = ws + (long)b * G;
+  double s = 0.0;
+  for (long i = 0; i < G; ++i) s += p[i];
+  ratio[b] = sqrt(s / (double)per_sample);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 
 extern "C" int osuf_axpby_rows(const float* x, const float* y, const float* ca, const float* cb, float* out, int B, long per_sample, hipStream_t stream) {
@@ -831,5 +907,53 @@ extern "C" int osuf_cfg_rescale(const float* cond, const float* nullp, float con
     hipLaunchKernelGGL(cfg_rescale_sums_kernel<false>, grid, dim3(256), 0, stream, cond, nullp, cond_scale, sums, B, per_sample);
     hipLaunchKernelGGL(cfg_rescale_apply_kernel<false>, grid, dim3(256), 0, stream, cond, nullp, cond_scale, phi, sums, factor, out, B, per_sample);
   }
+  return osuf_launch_status();
+}
+
+extern "C" long osuf_rk_error_workspace_bytes(int B, long per_sample) {
+  return B > 0 && per_sample > 0 ? (long)B * cfgr_chunks(per_sample) * (long)sizeof(double) : 0;
+}
+
+template <int S>
+static void rk_error_launch(const float* y0, const float* y1, const RkErrArgs& a, double dt, double atol, double rtol, double* ws, int B,
+                            long per_sample, bool vec, dim3 grid, hipStream_t stream) {
+  if (vec) hipLaunchKernelGGL((rk_error_sums_kernel<S, true>), grid, dim3(256), 0, stream, y0, y1, a, dt, atol, rtol, ws, B, per_sample);
+  else hipLaunchKernelGGL((rk_error_sums_kernel<S, false>), grid, dim3(256), 0, stream, y0, y1, a, dt, atol, rtol, ws, B, per_sample);
+}
+
+static inline bool finite64(double v) { return v - v == 0.0; }
+
+// k, e and step are HOST arrays; step = {dt, atol, rtol}.
+extern "C" int osuf_rk_error(const float* y0, const float* y1, const float* const* k, const double* e, int S, const double* step, void* ws,
+                             double* ratio, int B, long per_sample, hipStream_t stream) {
+  if (!y0 || !y1 || !k || !e || !step || !ws || !ratio || S < 1 || S > 7 || B < 1 || per_sample < 1) return OSUF_EINVAL;
+  const double dt = step[0], atol = step[1], rtol = step[2];
+  if (!finite64(dt) || !finite64(atol) || !finite64(rtol) || atol < 0.0 || rtol < 0.0 || (atol == 0.0 && rtol == 0.0)) return OSUF_EINVAL;
+  const long G = cfgr_chunks(per_sample);
+  if ((reinterpret_cast<uintptr_t>(ws) & 7) || G > 0x7fffffffL) return OSUF_EINVAL;
+  RkErrArgs a{};
+  int used = 0;
+  bool vec = per_sample % 4 == 0 && al16(y0) && al16(y1);
+  for (int j = 0; j < S; ++j) {
+    if (e[j] != e[j]) return OSUF_EINVAL;
+    if (e[j] == 0.0) continue;                              // a select: the stage is neither read nor required to exist
+    if (!k[j]) return OSUF_EINVAL;
+    vec = vec && al16(k[j]);
+    a.k[used] = k[j];
+    a.e[used++] = e[j];
+  }
+  const dim3 grid((unsigned)G, (unsigned)(B < 65535 ? B : 65535));
+  double* sums = (double*)ws;
+  switch (used) {
+    case 0: rk_error_launch<0>(y0, y1, a, dt, atol, rtol, sums, B, per_sample, vec, grid, stream); break;
+    case 1: rk_error_launch<1>(y0, y1, a, dt, atol, rtol, sums, B, per_sample, vec, grid, stream); break;
+    case 2: rk_error_launch<2>(y0, y1, a, dt, atol, rtol, sums, B, per_sample, vec, grid, stream); break;
+    case 3: rk_error_launch<3>(y0, y1, a, dt, atol, rtol, sums, B, per_sample, vec, grid, stream); break;
+    case 4: rk_error_launch<4>(y0, y1, a, dt, atol, rtol, sums, B, per_sample, vec, grid, stream); break;
+    case 5: rk_error_launch<5>(y0, y1, a, dt, atol, rtol, sums, B, per_sample, vec, grid, stream); break;
+    case 6: rk_error_launch<6>(y0, y1, a, dt, atol, rtol, sums, B, per_sample, vec, grid, stream); break;
+    default: rk_error_launch<7>(y0, y1, a, dt, atol, rtol, sums, B, per_sample, vec, grid, stream); break;
+  }
+  hipLaunchKernelGGL(rk_error_ratio_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, (const double*)sums, ratio, B, G, per_sample);
   return osuf_launch_status();
 }

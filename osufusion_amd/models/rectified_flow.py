@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F  # noqa: N812
 
-from .. import inpaint, ops
+from .. import inpaint, ode, ops
 from .. import runtime as rt
 from ..modules.unet import UNet
 from .diffusion import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, _MSEFn
@@ -67,6 +67,7 @@ class OsuFusion(nn.Module):
         self.sample_timesteps = sampling_timesteps
         self.cond_drop_prob = cond_drop_prob
         self._full_bf16 = False
+        self.last_ode_stats = None
 
     def set_full_bf16(self) -> None:
         """Keeps fp32 master weights; all kernels compute in bf16 (see models/diffusion.py)."""
@@ -85,18 +86,24 @@ class OsuFusion(nn.Module):
 
     @torch.inference_mode()
     def sample_masked(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0,
-                      known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None, method: str = "midpoint",
+                      rtol: float = 1e-5, atol: float = 1e-5, first_step: Optional[float] = None, max_steps: int = 1000) -> torch.Tensor:
         """sample() with the keywords the transformer models' sample() takes (the reference's signature of sample() is kept as it is).
         known (B, 6, n) and known_mask ((n,), (B, n) or (B, 1, n); 1 / True = keep), both or neither: masked generation (flow_levels,
         osufusion_amd/inpaint.py).  The iterate at ODE time t is t x_0 + (1 - t) noise -- the sampler's own state, not the cosmap position of
         training -- so every state handed to the UNet is blended at (t, 1 - t): the start iterate at (0, 1), the midpoint state at
         t0 + dt / 2, the end of an interval at t1, and the end of the last interval by the exact blend (`known` bit for bit where the mask is
-        1).  The noise is one fixed tensor, a clone of the start iterate: nothing new is drawn.  With both None: the unmasked sampler's bits."""
+        1).  The noise is one fixed tensor, a clone of the start iterate: nothing new is drawn.  With both None: the unmasked sampler's bits.
+        method, rtol, atol, first_step, max_steps: the ODE solver (osufusion_amd/ode.py): "euler", "midpoint" (the default: sample()'s launches
+        and bits) and "rk4" on the sampler's grid, "bosh3" and "dopri5" adaptive from rtol / atol; an adaptive method with known / known_mask
+        raises ValueError.  The call's evaluations and accepted / rejected steps are left in self.last_ode_stats."""
         masked = inpaint.check_pair(known, known_mask)
+        solver = dict(method=method, rtol=rtol, atol=atol, first_step=first_step, max_steps=max_steps)
+        ode.check_options(**solver)
         with ops.reproducible_mode(True):
-            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None)
+            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None, solver)
 
-    def _sample(self, a, c, x, cond_scale, keep_region=None):
+    def _sample(self, a, c, x, cond_scale, keep_region=None, solver=None):
         (b, _, n), device = a.shape, a.device
         rt.require_gpu(a)
         if x is None:
@@ -127,7 +134,7 @@ class OsuFusion(nn.Module):
                 return out
 
             times = torch.linspace(0.0, 1.0, self.sample_timesteps).tolist()
-            x = midpoint_loop(f, x, times, ones, keep_region)
+            x, self.last_ode_stats = ode.ode_loop(f, x, times, ones, keep_region=keep_region, **(solver or {}))
         return x
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -15,7 +15,8 @@ trained context by fused-window denoising (osufusion_amd/windowed.py), one gathe
 and ``guidance_rescale`` / ``guidance_interval``: the CFG rescale (one ops.cfg_rescale before a guided step) and guidance only inside a band
 of log-SNR, the conditional B rows alone outside it (osufusion_amd/guidance.py).
 The three diffusion samplers (discrete DDIM, ancestral, DDIM / 2M solver) share one loop, _TransformerOsuFusion._run; each describes its
-steps to it with a _Steps record.  The flow sampler's loop is models/rectified_flow.midpoint_loop.
+steps to it with a _Steps record.  The flow sampler's loop is osufusion_amd/ode.ode_loop: models/rectified_flow.midpoint_loop by default,
+fixed-grid Euler / RK4 or an adaptive embedded pair by ``method``.
 Not here: hipGraph capture of the step, LoRA on these backbones.
 """
 from dataclasses import dataclass
@@ -24,13 +25,13 @@ from typing import Callable, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from .. import ct, guidance, inpaint, ops, windowed
+from .. import ct, guidance, inpaint, ode, ops, windowed
 from .. import runtime as rt
 from ..modules.dit import DiT
 from ..modules.mmdit import MMDiT
 from ..modules.scheduler import GaussianDiffusionContinuousTimes
 from .diffusion import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, DDIMSchedule, _MSEFn
-from .rectified_flow import cosmap, midpoint_loop
+from .rectified_flow import cosmap
 
 BACKBONES = {"mmdit": MMDiT, "dit": DiT}
 SAMPLERS = ("ddpm", "ddim", "dpmpp_2m")                      # of ContinuousDiffusionOsuFusionDiT
@@ -454,13 +455,15 @@ class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
                  **backbone_kwargs) -> None:
         super().__init__(dim_h, backbone, cond_drop_prob, **backbone_kwargs)
         self.sample_timesteps = sampling_timesteps
+        self.last_ode_stats = None
 
     @torch.inference_mode()
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0,
                known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
                window: Optional[int] = None, window_stride: Optional[int] = None, window_taper: str = "trapezoid",
                window_batch: Optional[int] = None, guidance_rescale: float = 0.0,
-               guidance_interval: Optional[Tuple[Optional[float], Optional[float]]] = None) -> torch.Tensor:
+               guidance_interval: Optional[Tuple[Optional[float], Optional[float]]] = None, method: str = "midpoint",
+               rtol: float = 1e-5, atol: float = 1e-5, first_step: Optional[float] = None, max_steps: int = 1000) -> torch.Tensor:
         """rectified_flow.py:57-79 on the transformer backbones: the fixed-grid midpoint loop, 2 * (S - 1) evaluations.  Bit-reproducible.
         known / known_mask (both or neither): masked generation as in models/rectified_flow.OsuFusion.sample_masked -- every state handed to the
         backbone blended at (t, 1 - t), the end of the last interval exactly, one fixed noise tensor, no new draw.
@@ -468,15 +471,24 @@ class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
         window, window_stride, window_taper, window_batch: windowed sampling, see _TransformerOsuFusion.WINDOW_DOC.
 
         guidance_rescale, guidance_interval: see _TransformerOsuFusion.GUIDANCE_DOC; an evaluation's log-SNR is 2 log(t / (1 - t)) of its
-        time, in fp64, -inf at t = 0, and both evaluations of a midpoint step decide for themselves.  On a rescaled evaluation
-        ops.cfg_rescale replaces the ops.axpby_rows combine."""
+        time, in fp64, -inf at t = 0, and every evaluation of a step decides for itself.  On a rescaled evaluation
+        ops.cfg_rescale replaces the ops.axpby_rows combine.
+
+        method, rtol, atol, first_step, max_steps: the ODE solver, as the reference's odeint call takes them (osufusion_amd/ode.py).
+        "euler", "midpoint" (the default: this loop's launches and bits as they were) and "rk4" step over the sampler's grid, S - 1,
+        2 (S - 1) and 4 (S - 1) evaluations, and ignore the tolerances; "bosh3" and "dopri5" choose their steps from rtol / atol (one step
+        size for the batch, B doubles read back per attempted step), start at first_step (None: the grid's 1 / (S - 1)) and raise
+        RuntimeError after max_steps attempted steps; with known / known_mask they raise ValueError.  The call's evaluations, accepted and
+        rejected steps and accepted step ends are left in self.last_ode_stats."""
         masked = inpaint.check_pair(known, known_mask)
         wp = self._window_plan(a, window, window_stride, window_taper, window_batch)
         gd = guidance.plan(guidance_rescale, guidance_interval)
+        solver = dict(method=method, rtol=rtol, atol=atol, first_step=first_step, max_steps=max_steps)
+        ode.check_options(**solver)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
-            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None, wp, gd)
+            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None, wp, gd, solver)
 
-    def _sample(self, a, c, x, cond_scale, keep_region=None, wp=None, gd: Optional[guidance.Guidance] = None):
+    def _sample(self, a, c, x, cond_scale, keep_region=None, wp=None, gd: Optional[guidance.Guidance] = None, solver: Optional[dict] = None):
         x = self._start(a, x)
         b, device = a.shape[0], a.device
         cfg = cond_scale != 1.0
@@ -497,7 +509,7 @@ class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
                 return out
 
             times = torch.linspace(0.0, 1.0, self.sample_timesteps).tolist()
-            x = midpoint_loop(f, x, times, ones, keep_region)
+            x, self.last_ode_stats = ode.ode_loop(f, x, times, ones, keep_region=keep_region, **(solver or {}))
         return x
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:

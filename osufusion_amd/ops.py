@@ -771,6 +771,14 @@ def cfg_rescale(cond: torch.Tensor, null: torch.Tensor, cond_scale: float, phi: 
     return guidance.cfg_rescale(cond, null, cond_scale, phi)
 
 
+def rk_error(y0: torch.Tensor, y1: torch.Tensor, ks, e, dt: float, atol: float, rtol: float) -> torch.Tensor:
+    """Scaled error norm of an embedded Runge-Kutta step: -> ratio (B,) fp64, ratio[b] = sqrt(mean_i ((dt sum_j e[j] ks[j]) /
+    (atol + rtol max(|y0|, |y1|)))^2) over sample b, in fp64; two launches, deterministic; a stage under a zero weight is not read (it may be
+    None).  The allocating wrapper lives in osufusion_amd/ode.py (its guarded-memory cases in tests/test_ode_gpu.py)."""
+    from . import ode
+    return ode.rk_error(y0, y1, ks, e, dt, atol, rtol)
+
+
 def mse(pred: torch.Tensor, target: torch.Tensor, orig_len: Optional[torch.Tensor], want_grad: bool, weight: Optional[torch.Tensor] = None):
     """weight: per-sample fp32 (B,) loss weights (osuf_mse_w); None is osuf_mse."""
     B, Dc, Lx = pred.shape
