@@ -555,18 +555,14 @@ int osuf_vqt_logmag(const float* spec, long ld, float* out, long ldo, const floa
 int osuf_fir_decimate2(const float* in, long n_in, const float* taps, int ntaps, float* out, long n_out, hipStream_t stream);
 int osuf_frame_rows(const float* in, long n_in, int hop, int K, float* out, long frames, hipStream_t stream);
 
-/* ---- DiT row kernels (dit.hip)    replaces: osu_fusion/modules/dit.py:14-15 modulate(LayerNorm(x)), 63-70 MultiHeadRMSNorm, 275-277 the
- *      audio statistics pooling.  Rows [M][C], M = B * L, sample of row m = m / L; C % 8 == 0, C <= 2048; row strides multiples of 8
+/* ---- DiT row kernels (dit.hip)    replaces: osu_fusion/modules/dit.py:14-15 modulate(LayerNorm(x)), 275-277 the audio statistics
+ *      pooling (63-70 MultiHeadRMSNorm: osuf_joint_qknorm_fwd / _bwd below, one stream and G = H).  Rows [M][C], M = B * L, sample of row m = m / L; C % 8 == 0, C <= 2048; row strides multiples of 8
  *      elements, 16-B aligned pointers.  No atomics: every cross-row sum goes through per-workgroup partials added in a fixed order.
  * osuf_adaln_fwd: out = LN(x) * (1 + scale[b]) + shift[b] (no affine, eps given); shift / scale fp32 read at [b * ldm + c] (e.g. column
  *      blocks of the (B, 6C) modulation output, ldm = 6C); mr[2m] = mean, mr[2m+1] = rstd (fp32).
  * osuf_adaln_bwd: dx = dres + LN-backward(dy * (1 + scale[b])) (dres may be NULL); stores dshift[b][c] = sum_n dy at dmod[b * ldd + c]
  *      and dscale[b][c] = sum_n dy * xhat at dmod[b * ldd + off2 + c] (e.g. column blocks of the (B, 6C) modulation gradient, ldd = 6C);
  *      B = M / L <= 65535; workspace: osuf_adaln_bwd_workspace_bytes(M, C, L) bytes.
- * osuf_qknorm_fwd: raw q|k|v projection rows [M][3 H D] (dtype) -> bf16 rows: q and k heads x / max(||x||, 1e-12) * gamma[h] * sqrt(D),
- *      v copied; inv[m][2H] = 1 / max(||x||, 1e-12) of the q then k heads.  D in {16, 32, 64, 128}, 3 H D <= 4096.
- * osuf_qknorm_bwd: fp32 dq|dk|dv rows -> gradient of the raw projections (dtype); dgamma [2][H][D] (q then k) stored;
- *      workspace: osuf_qknorm_bwd_workspace_bytes(M, H, D) bytes.
  * osuf_stat_pool: a fp32 (B, C, L) contiguous -> out (B, 2C) = [mean_l | unbiased std_l]. ---- */
 int osuf_adaln_fwd(int dtype, const void* x, long ldx, void* out, long ldo, float* mr, const float* shift, const float* scale, long ldm,
                    int M, int C, int L, float eps, hipStream_t stream);
@@ -574,12 +570,6 @@ long osuf_adaln_bwd_workspace_bytes(int M, int C, int L);
 int osuf_adaln_bwd(int dtype, const void* dy, long lddy, const void* x, long ldx, const void* dres, long ldr, void* dx, long lddx,
                    const float* mr, const float* scale, long ldm, float* dmod, long ldd, long off2, float* workspace, long workspace_bytes,
                    int M, int C, int L, hipStream_t stream);
-int osuf_qknorm_fwd(int dtype, const void* x, long ldx, void* y, long ldy, float* inv, const float* gamma_q, const float* gamma_k,
-                    int M, int H, int D, hipStream_t stream);
-long osuf_qknorm_bwd_workspace_bytes(int M, int H, int D);
-int osuf_qknorm_bwd(int dtype, const float* g, long ldg, const void* x, long ldx, const float* inv, const float* gamma_q,
-                    const float* gamma_k, void* dx, long lddx, float* dgamma, float* workspace, long workspace_bytes,
-                    int M, int H, int D, hipStream_t stream);
 int osuf_stat_pool(const float* a, float* out, int B, int C, int L, hipStream_t stream);
 
 /* ---- joint attention rows (dit.hip)    replaces: osu_fusion/modules/mmdit.py:99-121 (rearrange, MultiHeadRMSNorm, the GQA repeat and
@@ -589,9 +579,10 @@ int osuf_stat_pool(const float* a, float* out, int B, int C, int L, hipStream_t 
  *      the other untouched (a layer calls each entry point once per stream).  Joint columns are what osuf_mqa_* read with G K/V heads:
  *      [H q heads group-major | G k heads | G v heads], D each; natural query head j (which reads K/V head j % G, as the reference's
  *      "b h n d -> b (r h) n d" repeat has it) sits in column block (j % G) * (H / G) + j / G.  The stream side is always in natural
- *      head order.  D in {16, 32, 64, 128}, H % G == 0, (H + 2G) D <= 4096.
+ *      head order.  D in {16, 32, 64, 128}, H % G == 0, (H + 2G) D <= 4096.  The DiT's fused to_qkv rows are the one-stream case
+ *      Ns == Nj, off == 0, G == H: the joint rows are then the plain q|k|v rows.
  * osuf_joint_qknorm_fwd: raw q|k|v projection rows [M][(H + 2G) D] (dtype) -> bf16 joint rows; q and k heads
- *      x / max(||x||, 1e-12) * gamma[h] * sqrt(D) with one bf16 rounding (osuf_qknorm_fwd's arithmetic; gamma_q [H][D], gamma_k [G][D]),
+ *      x / max(||x||, 1e-12) * gamma[h] * sqrt(D), computed in fp32 with one bf16 rounding (gamma_q [H][D], gamma_k [G][D]),
  *      v copied; inv[m][H + G] = 1 / max(||x||, 1e-12) of the stream's q then k heads.  gamma_q == gamma_k == NULL: cast and permute
  *      only (qk_norm=False), inv unused.
  * osuf_joint_pack: a stream's rows [M][H D] (dtype, natural head order) -> its bf16 joint rows [..][H D] group-major (dO).

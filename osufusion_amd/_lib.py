@@ -111,9 +111,6 @@ SIGNATURES = {
     "osuf_adaln_fwd": [I, P, L, P, L, P, P, P, L, I, I, I, F, P],
     "osuf_adaln_bwd_workspace_bytes": [I, I, I],
     "osuf_adaln_bwd": [I, P, L, P, L, P, L, P, L, P, P, L, P, L, L, P, L, I, I, I, P],
-    "osuf_qknorm_fwd": [I, P, L, P, L, P, P, P, I, I, I, P],
-    "osuf_qknorm_bwd_workspace_bytes": [I, I, I],
-    "osuf_qknorm_bwd": [I, P, L, P, L, P, P, P, P, L, P, P, L, I, I, I, P],
     "osuf_stat_pool": [P, P, I, I, I, P],
     "osuf_joint_qknorm_fwd": [I, P, L, P, L, P, P, P, I, I, I, I, I, I, I, P],
     "osuf_joint_pack": [I, P, L, P, L, I, I, I, I, I, I, I, P],

@@ -204,158 +204,19 @@ extern "C" int osuf_adaln_bwd(int dtype, const void* dy, long lddy, const void* 
 }
 
 // ------------------------------------------------------------------------------------------------
-// QK RMS-norm of the raw to_qkv rows [M][3 H D] = [q (h d) | k (h d) | v (h d)]   (dit.py:63-70,109-113)
+// QK RMS-norm of raw q|k|v projection rows [M][(H + 2G) D] = [q (h d) | k (g d) | v (g d)]   (dit.py:63-70,109-113, mmdit.py:94-127)
 //   y = x / max(||x||, 1e-12) * gamma[h] * sqrt(D) for the q and k heads, v copied; one bf16 rounding (what Attend reads)
 // A head is D / 8 consecutive lanes (16 B each): its sum of squares is a butterfly over those lanes.
-// ------------------------------------------------------------------------------------------------
-static constexpr float kNormEps = 1e-12f;
-
-template <typename T, int J>
-__global__ __launch_bounds__(256) void qknorm_fwd_kernel(const T* x, long ldx, bf16_t* y, long ldy, float* inv, const float* gq, const float* gk,
-                                                         int M, int H, int D) {
-  const int HD = H * D, chunks = 3 * HD / 8, hc = D / 8;
-  const int lane = threadIdx.x & 63;
-  const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long waves = ((long)gridDim.x * blockDim.x) >> 6;
-  const float sD = sqrtf((float)D);
-  for (long m = wave; m < M; m += waves) {
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const int ch = lane + 64 * j;
-      if (ch >= chunks) break;                                  // whole heads drop out together (64 and chunks are multiples of D / 8)
-      float v[8];
-      load8(x + m * ldx + ch * 8, v);
-      if (ch < 2 * HD / 8) {
-        float q = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) q += v[e] * v[e];
-        q = group_sum_dyn(q, hc);
-        const float r = 1.f / fmaxf(sqrtf(q), kNormEps);
-        const int head = ch / hc;                               // 0 .. 2H - 1: q heads, then k heads
-        const float* g = (head < H ? gq + head * D : gk + (head - H) * D) + (ch % hc) * 8;
-        float gv[8];
-        load8(g, gv);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = v[e] * r * gv[e] * sD;
-        if (ch % hc == 0) inv[m * 2 * H + head] = r;
-      }
-      store8(y + m * ldy + ch * 8, v);
-    }
-  }
-}
-
-// dq|dk|dv fp32 [M][3 H D] (ops.mqa_bwd) -> gradients of the raw projections in T.  Per q / k head, with u = x / max(n, eps), gu = g gamma sqrt(D):
-//   n >= eps: dx = (gu - u (u . gu)) / n;   n < eps (the clamp holds the norm constant): dx = gu / eps.
-// dgamma partials: part[k][2 H D] = sum over the workgroup's rows of g * u * sqrt(D).
-template <typename T, int J>
-__global__ __launch_bounds__(256) void qknorm_bwd_kernel(const float* g, long ldg, const T* x, long ldx, const float* inv, const float* gq,
-                                                         const float* gk, T* dx, long lddx, float* part, int M, int H, int D) {
-  const int HD = H * D, chunks = 3 * HD / 8, qk = 2 * HD / 8, hc = D / 8;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const float sD = sqrtf((float)D);
-  float acc[J][8];
-#pragma unroll
-  for (int j = 0; j < J; ++j)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
-  for (long m = 4L * blockIdx.x + wv; m < M; m += 4L * gridDim.x) {
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const int ch = lane + 64 * j;
-      if (ch >= chunks) break;
-      float gv[8];
-      load8(g + m * ldg + ch * 8, gv);
-      if (ch < qk) {
-        float xv[8], ga[8];
-        load8(x + m * ldx + ch * 8, xv);
-        const int head = ch / hc;
-        load8((head < H ? gq + head * D : gk + (head - H) * D) + (ch % hc) * 8, ga);
-        const float r = inv[m * 2 * H + head];
-        float q = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) q += xv[e] * xv[e];
-        q = group_sum_dyn(q, hc);
-        const bool clamped = sqrtf(q) < kNormEps;
-        float d = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float u = xv[e] * r;
-          acc[j][e] += gv[e] * u * sD;
-          gv[e] *= ga[e] * sD;                                  // gu
-          xv[e] = u;
-          d += u * gv[e];
-        }
-        d = group_sum_dyn(d, hc);
-        if (clamped) d = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) gv[e] = (gv[e] - xv[e] * d) * r;
-      }
-      store8(dx + m * lddx + ch * 8, gv);
-    }
-  }
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = reinterpret_cast<float*>(smem);                 // [4][2 H D]
-  const int W = 2 * HD;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int ch = lane + 64 * j;
-    if (ch < qk) store8(red + wv * W + ch * 8, acc[j]);
-  }
-  __syncthreads();
-  float* dst = part + (long)blockIdx.x * W;
-  for (int i = threadIdx.x; i < W; i += blockDim.x) dst[i] = red[i] + red[W + i] + red[2 * W + i] + red[3 * W + i];
-}
-
-static bool bad_heads(int H, int D) { return H <= 0 || !(D == 16 || D == 32 || D == 64 || D == 128) || 3L * H * D / 8 > 8 * 64; }
-static int qknorm_iters(int H, int D) { return chunk_iters(3 * H * D / 8); }
-static int qknorm_bwd_blocks(int M) { long b = ((long)M + 15) / 16; return (int)(b < 1024 ? b : 1024); }
-
-extern "C" int osuf_qknorm_fwd(int dtype, const void* x, long ldx, void* y, long ldy, float* inv, const float* gamma_q, const float* gamma_k,
-                               int M, int H, int D, hipStream_t stream) {
-  if (M <= 0 || bad_heads(H, D) || ldx % 8 || ldy % 8 || !al16(x) || !al16(y) || !inv || !al16(gamma_q) || !al16(gamma_k)) return OSUF_EINVAL;
-  const int J = qknorm_iters(H, D);
-  if (J == 0) return OSUF_EUNSUPPORTED;
-  long blocks = ((long)M + 3) / 4;
-  if (blocks > 4096) blocks = 4096;
-#define QKN_FWD(J_) hipLaunchKernelGGL((qknorm_fwd_kernel<T, J_>), dim3((int)blocks), dim3(256), 0, stream, (const T*)x, ldx, (bf16_t*)y, ldy, inv, gamma_q, gamma_k, M, H, D)
-  DISPATCH_T(dtype, if (J == 1) QKN_FWD(1); else if (J == 2) QKN_FWD(2); else if (J == 4) QKN_FWD(4); else QKN_FWD(8));
-#undef QKN_FWD
-  return osuf_launch_status();
-}
-
-extern "C" long osuf_qknorm_bwd_workspace_bytes(int M, int H, int D) {
-  if (M <= 0 || bad_heads(H, D)) return 0;
-  return (long)qknorm_bwd_blocks(M) * 2 * H * D * (long)sizeof(float);
-}
-
-/* g: fp32 dq|dk|dv rows; x: the raw projections (T), inv: the forward's inverse norms [M][2H].  dx in T; dgamma = [dgamma_q | dgamma_k]
- * fp32 [2][H][D] is stored (not added), summed in a fixed order through `workspace` (osuf_qknorm_bwd_workspace_bytes(M, H, D) bytes). */
-extern "C" int osuf_qknorm_bwd(int dtype, const float* g, long ldg, const void* x, long ldx, const float* inv, const float* gamma_q,
-                               const float* gamma_k, void* dx, long lddx, float* dgamma, float* workspace, long workspace_bytes,
-                               int M, int H, int D, hipStream_t stream) {
-  if (M <= 0 || bad_heads(H, D) || ldg % 4 || ldx % 8 || lddx % 8 || !al16(g) || !al16(x) || !al16(dx) || !inv || !al16(gamma_q) || !al16(gamma_k))
-    return OSUF_EINVAL;
-  if (!dgamma || !workspace || workspace_bytes < osuf_qknorm_bwd_workspace_bytes(M, H, D)) return OSUF_EINVAL;
-  const int J = qknorm_iters(H, D), nblk = qknorm_bwd_blocks(M), HD = H * D;
-  if (J == 0) return OSUF_EUNSUPPORTED;
-  const size_t lds = (size_t)4 * 2 * HD * sizeof(float);
-#define QKN_BWD(J_) hipLaunchKernelGGL((qknorm_bwd_kernel<T, J_>), dim3(nblk), dim3(256), lds, stream, g, ldg, (const T*)x, ldx, inv, gamma_q, gamma_k, \
-                                       (T*)dx, lddx, workspace, M, H, D)
-  DISPATCH_T(dtype, if (J == 1) QKN_BWD(1); else if (J == 2) QKN_BWD(2); else if (J == 4) QKN_BWD(4); else QKN_BWD(8));
-#undef QKN_BWD
-  // one "sample" of 2 H D columns: dgamma = [dgamma_q | dgamma_k], [2][H][D]
-  hipLaunchKernelGGL(rowpart_finish_kernel, dim3((2 * HD + kFinCols - 1) / kFinCols, 1), dim3(kFinCols * kFinSlices), 0, stream, workspace, nblk,
-                     2 * HD, dgamma, (long)0, (long)HD, HD);
-  return osuf_launch_status();
-}
-
-// ------------------------------------------------------------------------------------------------
-// Joint attention rows (mmdit.py:94-127): two streams' q|k|v projections packed into one bf16 buffer over [audio; map].
+// The normed rows land in joint attention rows: two streams' projections packed into one bf16 buffer over [audio; map].
 //   rows:    sample b owns Nj joint rows; a stream with Ns rows per sample at row offset `off` puts its row m = b * Ns + n at b * Nj + off + n
 //   columns: [H q heads GROUP-MAJOR | G k heads | G v heads], D each.  The reference repeats K/V as "b h n d -> b (r h) n d", so natural
 //            query head j reads K/V head j % G: it goes to column block (j % G) * (H / G) + j / G (what ops.mqa_fwd(kv_heads=G) reads)
-// One entry-point call serves ONE stream (a layer calls each twice); the other stream's joint rows are never touched.
+// One entry-point call serves ONE stream (an MMDiT layer calls each twice); the other stream's joint rows are never touched.  The DiT is
+// the one-stream case Ns == Nj, off == 0, G == H: both maps are then the identity and the joint rows are the plain q|k|v rows.
 // ------------------------------------------------------------------------------------------------
+static constexpr float kNormEps = 1e-12f;
+static int qknorm_bwd_blocks(int M) { long b = ((long)M + 15) / 16; return (int)(b < 1024 ? b : 1024); }
+
 __device__ __forceinline__ long joint_row(long m, int Ns, int Nj, int off) {
   const long b = m / Ns;
   return b * Nj + off + (m - b * Ns);
@@ -367,9 +228,11 @@ __device__ __forceinline__ int joint_chunk(int ch, int hc, int H, int G) {
   return ((head % G) * (H / G) + head / G) * hc + (ch - head * hc);
 }
 
-// raw q|k|v rows [M][(H + 2G) D] (T) -> bf16 joint rows; the q and k heads normed as qknorm_fwd_kernel does (the same operations in the
-// same order); gq == NULL: cast only.  inv[m][H + G]: the stream's own rows, natural head order (q heads, then k heads).
-template <typename T, int J>
+// raw q|k|v rows [M][(H + 2G) D] (T) -> bf16 joint rows, the q and k heads normed; gq == NULL: cast only.  inv[m][H + G]: the stream's
+// own rows, natural head order (q heads, then k heads).  JOINT false: one stream with G == H, where joint_row and joint_chunk are the
+// identity; their 64-bit division per row and integer divisions per chunk cost this light kernel 7 % at the DiT's shape
+// (profiles/qknorm_fold.md), so the launcher leaves them out at compile time.  The backward does enough arithmetic to hide them.
+template <typename T, int J, bool JOINT>
 __global__ __launch_bounds__(256) void joint_qknorm_fwd_kernel(const T* x, long ldx, bf16_t* y, long ldy, float* inv, const float* gq, const float* gk,
                                                                int M, int Ns, int Nj, int off, int H, int G, int D) {
   const int hc = D / 8, chunks = (H + 2 * G) * hc, qk = (H + G) * hc;
@@ -378,7 +241,7 @@ __global__ __launch_bounds__(256) void joint_qknorm_fwd_kernel(const T* x, long 
   const long waves = ((long)gridDim.x * blockDim.x) >> 6;
   const float sD = sqrtf((float)D);
   for (long m = wave; m < M; m += waves) {
-    const long jr = joint_row(m, Ns, Nj, off);
+    const long jr = JOINT ? joint_row(m, Ns, Nj, off) : m;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
       const int ch = lane + 64 * j;
@@ -399,7 +262,7 @@ __global__ __launch_bounds__(256) void joint_qknorm_fwd_kernel(const T* x, long 
         for (int e = 0; e < 8; ++e) v[e] = v[e] * r * gv[e] * sD;
         if (ch % hc == 0) inv[m * (H + G) + head] = r;
       }
-      store8(y + jr * ldy + joint_chunk(ch, hc, H, G) * 8, v);
+      store8(y + jr * ldy + (JOINT ? joint_chunk(ch, hc, H, G) : ch) * 8, v);
     }
   }
 }
@@ -420,8 +283,10 @@ __global__ __launch_bounds__(256) void joint_perm_kernel(T* s, long lds, bf16_t*
   }
 }
 
-// fp32 dq|dk|dv JOINT rows (ops.mqa_bwd) -> gradient of one stream's raw projections (T, natural head order); the arithmetic of
-// qknorm_bwd_kernel.  dgamma partials part[k][(H + G) D] (gq != NULL only).
+// fp32 dq|dk|dv JOINT rows (ops.mqa_bwd) -> gradient of one stream's raw projections (T, natural head order).  Per q / k head, with
+// u = x / max(n, eps), gu = g gamma sqrt(D):
+//   n >= eps: dx = (gu - u (u . gu)) / n;   n < eps (the clamp holds the norm constant): dx = gu / eps.
+// dgamma partials (gq != NULL only): part[k][(H + G) D] = sum over the workgroup's rows of g * u * sqrt(D).
 template <typename T, int J>
 __global__ __launch_bounds__(256) void joint_qknorm_bwd_kernel(const float* g, long ldg, const T* x, long ldx, const float* inv, const float* gq,
                                                                const float* gk, T* dx, long lddx, float* part, int M, int Ns, int Nj, int off,
@@ -498,9 +363,12 @@ extern "C" int osuf_joint_qknorm_fwd(int dtype, const void* x, long ldx, void* y
   if (J == 0) return OSUF_EUNSUPPORTED;
   long blocks = ((long)M + 3) / 4;
   if (blocks > 4096) blocks = 4096;
-#define JQKN_FWD(J_) hipLaunchKernelGGL((joint_qknorm_fwd_kernel<T, J_>), dim3((int)blocks), dim3(256), 0, stream, (const T*)x, ldx, (bf16_t*)y, ldy, inv, \
-                                        gamma_q, gamma_k, M, Ns, Nj, off, H, G, D)
-  DISPATCH_T(dtype, if (J == 1) JQKN_FWD(1); else if (J == 2) JQKN_FWD(2); else if (J == 4) JQKN_FWD(4); else JQKN_FWD(8));
+  const bool joint = !(Ns == Nj && off == 0 && G == H);       // else one stream, identity permutation (the DiT)
+#define JQKN_FWD(J_, JOINT_) hipLaunchKernelGGL((joint_qknorm_fwd_kernel<T, J_, JOINT_>), dim3((int)blocks), dim3(256), 0, stream, (const T*)x, ldx, \
+                                                (bf16_t*)y, ldy, inv, gamma_q, gamma_k, M, Ns, Nj, off, H, G, D)
+#define JQKN_FWD_J(JOINT_) if (J == 1) JQKN_FWD(1, JOINT_); else if (J == 2) JQKN_FWD(2, JOINT_); else if (J == 4) JQKN_FWD(4, JOINT_); else JQKN_FWD(8, JOINT_)
+  DISPATCH_T(dtype, if (joint) { JQKN_FWD_J(true); } else { JQKN_FWD_J(false); });
+#undef JQKN_FWD_J
 #undef JQKN_FWD
   return osuf_launch_status();
 }

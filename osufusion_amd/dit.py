@@ -5,9 +5,9 @@ Rows are channels-last (B, L, C) in the compute dtype, as everywhere else in the
     blocks of the fp32 (B, 6C) modulation output, read in place, and their gradients are stored in place into the same blocks of that
     output's gradient; the backward also takes the residual stream's gradient (parked by the
     gated residual through a functional.ResLink) and adds it into dx in the same pass.
-  * DiTAttentionFn: to_qkv GEMM -> osuf_qknorm_fwd (F.normalize * gamma * sqrt(D) of the q and k heads, one bf16 rounding: the rows
-    Attend casts to) -> ops.mqa_fwd with one K/V head per query head (kv_heads = H).  Backward: ops.mqa_bwd, osuf_qknorm_bwd, then the
-    dgrad / wgrad GEMMs of to_qkv.
+  * DiTAttentionFn: to_qkv GEMM -> osuf_joint_qknorm_fwd with one stream and G = H (F.normalize * gamma * sqrt(D) of the q and k heads,
+    one bf16 rounding: the rows Attend casts to) -> ops.mqa_fwd with one K/V head per query head (kv_heads = H).  Backward: ops.mqa_bwd,
+    osuf_joint_qknorm_bwd, then the dgrad / wgrad GEMMs of to_qkv.
   * DiTFeedForwardFn: W2 silu(W1 x + b1) + b2, SiLU in the first GEMM's epilogue (the residual is gated, so it stays out of the GEMM).
   * the gated residual x + gate[b] * f(x) is functional.GateResFn.
   * stat_pool: cat(a.mean(-1), a.std(-1)) of the audio (dit.py:275-277), forward only.
@@ -74,14 +74,16 @@ def adaln_bwd(dy: torch.Tensor, x: torch.Tensor, mr: torch.Tensor, scale: torch.
 
 
 def qknorm_fwd(raw: torch.Tensor, gamma_q: torch.Tensor, gamma_k: torch.Tensor, H: int, D: int):
-    """raw q|k|v projection rows (B, L, 3 H D) -> (bf16 rows for the attention kernels, inv norms (B*L, 2H) fp32)."""
+    """raw q|k|v projection rows (B, L, 3 H D) -> (bf16 rows for the attention kernels, inv norms (B*L, 2H) fp32).  The joint kernel with
+    one stream (Ns = Nj = L, off = 0) and G = H: its row and head permutations are then the identity."""
     M, W, ld = ops._rows(raw)
+    L = raw.shape[1]
     assert W == 3 * H * D and gamma_q.dtype == gamma_k.dtype == torch.float32 and gamma_q.is_contiguous() and gamma_k.is_contiguous()
     assert gamma_q.numel() == gamma_k.numel() == H * D
     y = torch.empty(raw.shape, dtype=torch.bfloat16, device=raw.device)
     inv = torch.empty((M, 2 * H), dtype=torch.float32, device=raw.device)
-    ops.call("osuf_qknorm_fwd", ops.dt_of(raw), raw.data_ptr(), ld, y.data_ptr(), W, inv.data_ptr(), gamma_q.data_ptr(), gamma_k.data_ptr(),
-             M, H, D, ops._stream())
+    ops.call("osuf_joint_qknorm_fwd", ops.dt_of(raw), raw.data_ptr(), ld, y.data_ptr(), W, inv.data_ptr(), gamma_q.data_ptr(), gamma_k.data_ptr(),
+             M, L, L, 0, H, H, D, ops._stream())
     return y, inv
 
 
@@ -89,14 +91,15 @@ def qknorm_bwd(dqkv: torch.Tensor, raw: torch.Tensor, inv: torch.Tensor, gamma_q
     """fp32 dq|dk|dv rows (ops.mqa_bwd) -> (gradient of the raw projections in raw.dtype, dgamma (2, H, D) fp32 = q | k)."""
     M, W, ld = ops._rows(raw)
     Mg, Wg, ldg = ops._rows(dqkv)
+    L = raw.shape[1]
     assert dqkv.dtype == torch.float32 and Mg == M and Wg == W == 3 * H * D and inv.is_contiguous() and inv.numel() == 2 * H * M
     dev = raw.device
     dx = torch.empty(raw.shape, dtype=raw.dtype, device=dev)
     dgamma = torch.empty((2, H, D), dtype=torch.float32, device=dev)
-    need = _lib.load().osuf_qknorm_bwd_workspace_bytes(M, H, D)
+    need = _lib.load().osuf_joint_qknorm_bwd_workspace_bytes(M, H, H, D)
     ws = torch.empty(max(need // 4, 1), dtype=torch.float32, device=dev)
-    ops.call("osuf_qknorm_bwd", ops.dt_of(raw), dqkv.data_ptr(), ldg, raw.data_ptr(), ld, inv.data_ptr(), gamma_q.data_ptr(), gamma_k.data_ptr(),
-             dx.data_ptr(), W, dgamma.data_ptr(), ws.data_ptr(), need, M, H, D, ops._stream())
+    ops.call("osuf_joint_qknorm_bwd", ops.dt_of(raw), dqkv.data_ptr(), ldg, raw.data_ptr(), ld, inv.data_ptr(), gamma_q.data_ptr(),
+             gamma_k.data_ptr(), dx.data_ptr(), W, dgamma.data_ptr(), ws.data_ptr(), need, M, L, L, 0, H, H, D, ops._stream())
     return dx, dgamma
 
 

@@ -115,9 +115,7 @@ class _TransformerOsuFusion(nn.Module):
                 rows, st, t = a_rows[:b], static[:b], t[:b]
             xin = torch.cat([x, x], 0) if cfg and guided else x
             cvec = (st + net.embed_time(t)).contiguous()
-            if self.backbone == "mmdit":
-                return net.denoise_rows(net.encode_x(xin, dtype), rows, cvec, n).contiguous()
-            return net.denoise_rows(net.encode_x(xin, rows, dtype), cvec, n).contiguous()
+            return net.sample_rows(xin, rows, cvec, n, dtype).contiguous()
         return f
 
     def _windowed_denoiser(self, a: torch.Tensor, c: torch.Tensor, cfg: bool, window: int, stride: int, taper: str = "trapezoid",

@@ -26,8 +26,8 @@ class FeedForward(nn.Sequential):
 
 
 class MultiHeadRMSNorm(nn.Module):
-    """dit.py:63-70: F.normalize(x, dim=-1) * gamma[h] * sqrt(dim) on (B, H, N, dim).  Inside DiTAttention it is osuf_qknorm_fwd; the
-    stand-alone forward (plain torch on whatever device) exists for code written against the reference class."""
+    """dit.py:63-70: F.normalize(x, dim=-1) * gamma[h] * sqrt(dim) on (B, H, N, dim).  Inside DiTAttention and JointAttention it is
+    osuf_joint_qknorm_fwd; the stand-alone forward (plain torch on whatever device) exists for code written against the reference class."""
 
     def __init__(self, dim: int, heads: int) -> None:
         super().__init__()
@@ -135,7 +135,65 @@ class FinalLayer(nn.Module):
         return self.forward_rows(x, rt.small_linear(c.float(), lin.weight, lin.bias, in_act=ops.ACT_SILU))
 
 
-class DiT(nn.Module):
+class _TransformerBackbone:
+    """What DiT and MMDiT share; no module, parameter or buffer of its own.  A backbone brings null_cond, embed_time(t) and the hooks
+    _embed_cond(c) (its conditioning MLP) and _embed_audio(a) (its MLP of the audio statistics): fp32 (B, dim_h) each."""
+
+    @staticmethod
+    def _basic_init(module: nn.Module) -> None:
+        if isinstance(module, (nn.Linear, nn.Conv1d)):
+            nn.init.xavier_uniform_(module.weight)
+            if module.bias is not None:
+                nn.init.zeros_(module.bias)
+
+    def set_gradient_checkpointing(self, value: bool) -> None:
+        """dit.py:247-251, mmdit.py:331-335 (same log line per module)."""
+        for name, module in self.named_modules():
+            if hasattr(module, "gradient_checkpointing"):
+                module.gradient_checkpointing = value
+                print(f"Set gradient checkpointing to {value} for {name}")
+
+    def forward_with_cond_scale(self, *args: List, cond_scale: float = 1.0, **kwargs: Dict) -> torch.Tensor:
+        """dit.py:253-260, mmdit.py:337-344."""
+        logits = self(*args, **kwargs)
+        if cond_scale == 1.0:
+            return logits
+        null_logits = self(*args, **kwargs, cond_drop_prob=1.0)
+        return null_logits + (logits - null_logits) * cond_scale
+
+    @staticmethod
+    def _ff(x: torch.Tensor, ff: nn.Sequential) -> torch.Tensor:
+        """Sequential(Linear, SiLU, Linear) on the skinny-linear kernels."""
+        h = rt.small_linear(x, ff[0].weight, ff[0].bias)
+        return rt.small_linear(h, ff[2].weight, ff[2].bias, in_act=ops.ACT_SILU)
+
+    def _cond(self, c: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
+        return torch.where(keep[:, None], self._embed_cond(c), self.null_cond.float()[None, :].expand(keep.shape[0], -1))
+
+    def embed(self, a: torch.Tensor, t: torch.Tensor, c: torch.Tensor, cond_drop_prob: float) -> torch.Tensor:
+        """The conditioning vector where(keep, mlp_cond(c), null_cond) + mlp_time(t) + the audio statistics' MLP (dit.py:274-285,
+        mmdit.py:355-378), fp32 (B, dim_h); keep is drawn here.  a: the audio before any padding."""
+        keep = prob_mask_like((a.shape[0],), 1.0 - cond_drop_prob, device=a.device)
+        return self._cond(c, keep) + self.embed_time(t) + self._embed_audio(a)
+
+    def embed_static(self, a: torch.Tensor, c: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
+        """The part of embed() that does not depend on t, fp32 (B, dim_h).  keep: bool (B,).  A sampler computes it once per call and adds
+        embed_time(t) per step."""
+        return self._cond(c, keep) + self._embed_audio(a)
+
+    @staticmethod
+    def _modulations(cvec: torch.Tensor, lins: List[nn.Linear]) -> List[torch.Tensor]:
+        """The backbone's Sequential(SiLU, Linear) projections of c: one grouped launch (runtime.film_prepare), else one each."""
+        grouped = rt.film_prepare(cvec, lins)
+        outs = []
+        for lin in lins:
+            m = rt.film_take(cvec, lin) if grouped else None
+            outs.append(m if m is not None else rt.small_linear(cvec, lin.weight, lin.bias, in_act=ops.ACT_SILU))
+        rt.film_clear()
+        return outs
+
+
+class DiT(_TransformerBackbone, nn.Module):
     """dit.py:162-292."""
 
     def __init__(self, dim_in_x: int, dim_in_a: int, dim_in_c: int, dim_h: int, dim_h_mult: int = 4, depth: int = 12,
@@ -163,13 +221,7 @@ class DiT(nn.Module):
     def initialize_weights(self) -> None:
         """dit.py:218-245: xavier-uniform Linear / Conv1d weights and zero biases, N(0, 0.02) embedders, zeroed adaLN / final modulation
         and postprocess."""
-        def _basic_init(module: nn.Module) -> None:
-            if isinstance(module, (nn.Linear, nn.Conv1d)):
-                nn.init.xavier_uniform_(module.weight)
-                if module.bias is not None:
-                    nn.init.zeros_(module.bias)
-
-        self.apply(_basic_init)
+        self.apply(self._basic_init)
         for m in (self.mlp_time[1], self.mlp_time[3], self.mlp_cond[0], self.mlp_cond[2], self.mlp_audio[0], self.mlp_audio[2]):
             nn.init.normal_(m.weight, std=0.02)
         for block in self.blocks:
@@ -178,21 +230,6 @@ class DiT(nn.Module):
         nn.init.zeros_(self.final.modulation[1].weight)
         nn.init.zeros_(self.final.modulation[1].bias)
         nn.init.zeros_(self.postprocess.weight)
-
-    def set_gradient_checkpointing(self, value: bool) -> None:
-        """dit.py:247-251 (same log line per module)."""
-        for name, module in self.named_modules():
-            if hasattr(module, "gradient_checkpointing"):
-                module.gradient_checkpointing = value
-                print(f"Set gradient checkpointing to {value} for {name}")
-
-    def forward_with_cond_scale(self, *args: List, cond_scale: float = 1.0, **kwargs: Dict) -> torch.Tensor:
-        """dit.py:253-260."""
-        logits = self(*args, **kwargs)
-        if cond_scale == 1.0:
-            return logits
-        null_logits = self(*args, **kwargs, cond_drop_prob=1.0)
-        return null_logits + (logits - null_logits) * cond_scale
 
     # -- pieces ---------------------------------------------------------------------------------------------------
     def _stem(self, x: torch.Tensor, a: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -209,35 +246,14 @@ class DiT(nn.Module):
         rows = Fn.RowsFromNCLFn.apply(xa.contiguous(), dtype, cpad, 1)
         return Fn.ConvFn.apply(rows, w, b, self._stem_cache, "same", ("dit_stem", *[c.weight for c in pre.convs]))
 
-    def embed(self, a: torch.Tensor, t: torch.Tensor, c: torch.Tensor, cond_drop_prob: float) -> torch.Tensor:
-        """c + mlp_time(t) + mlp_audio(feature_extractor_a(stat_pool(a))) (dit.py:274-285), fp32 (B, dim_h)."""
-        h_a = Dt.stat_pool(a)
-        fe = self.feature_extractor_a
-        h_a = rt.small_linear(h_a, fe.weight, fe.bias)
-        B = a.shape[0]
-        cond_mask = prob_mask_like((B,), 1.0 - cond_drop_prob, device=a.device)
-        e = rt.small_linear(c.float(), self.mlp_cond[0].weight, self.mlp_cond[0].bias)
-        e = rt.small_linear(e, self.mlp_cond[2].weight, self.mlp_cond[2].bias, in_act=ops.ACT_SILU)
-        e = torch.where(cond_mask[:, None], e, self.null_cond.float()[None, :].expand(B, -1))
-        te = self.mlp_time[0](t)
-        te = rt.small_linear(te, self.mlp_time[1].weight, None)
-        te = rt.small_linear(te, self.mlp_time[3].weight, None, in_act=ops.ACT_SILU)
-        ae = rt.small_linear(h_a, self.mlp_audio[0].weight, self.mlp_audio[0].bias)
-        ae = rt.small_linear(ae, self.mlp_audio[2].weight, self.mlp_audio[2].bias, in_act=ops.ACT_SILU)
-        return e + te + ae
+    def _embed_cond(self, c: torch.Tensor) -> torch.Tensor:
+        """mlp_cond(c)."""
+        return self._ff(c.float(), self.mlp_cond)
 
-    def embed_static(self, a: torch.Tensor, c: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
-        """The part of embed() that does not depend on t: where(keep, mlp_cond(c), null_cond) + mlp_audio(feature_extractor_a(stat_pool(a))),
-        fp32 (B, dim_h).  keep: bool (B,).  A sampler computes it once per call and adds embed_time(t) per step."""
+    def _embed_audio(self, a: torch.Tensor) -> torch.Tensor:
+        """mlp_audio(feature_extractor_a(stat_pool(a))) (dit.py:275-279)."""
         fe = self.feature_extractor_a
-        h_a = rt.small_linear(Dt.stat_pool(a), fe.weight, fe.bias)
-        B = a.shape[0]
-        e = rt.small_linear(c.float(), self.mlp_cond[0].weight, self.mlp_cond[0].bias)
-        e = rt.small_linear(e, self.mlp_cond[2].weight, self.mlp_cond[2].bias, in_act=ops.ACT_SILU)
-        e = torch.where(keep[:, None], e, self.null_cond.float()[None, :].expand(B, -1))
-        ae = rt.small_linear(h_a, self.mlp_audio[0].weight, self.mlp_audio[0].bias)
-        ae = rt.small_linear(ae, self.mlp_audio[2].weight, self.mlp_audio[2].bias, in_act=ops.ACT_SILU)
-        return e + ae
+        return self._ff(rt.small_linear(Dt.stat_pool(a), fe.weight, fe.bias), self.mlp_audio)
 
     def embed_time(self, t: torch.Tensor) -> torch.Tensor:
         """mlp_time(t), fp32 (B, dim_h)."""
@@ -265,7 +281,7 @@ class DiT(nn.Module):
 
     def denoise_rows(self, h: torch.Tensor, cvec: torch.Tensor, n: int) -> torch.Tensor:
         """The stem's rows (B, L, dim_h) and the conditioning vector (fp32 (B, dim_h), contiguous) -> the prediction (B, dim_in_x, n)."""
-        mods = self._modulations(cvec)
+        mods = self._modulations(cvec, [b.modulation[1] for b in self.blocks] + [self.final.modulation[1]])      # depth + 1
         for block, mod in zip(self.blocks, mods[:-1]):
             h = block.forward_rows(h, mod)
         h = self.final.forward_rows(h, mods[-1])
@@ -275,16 +291,9 @@ class DiT(nn.Module):
         y = Fn.ConvFn.apply(h, w, None, self._post_cache, "same", ("post", self.postprocess.weight))
         return Fn.NCLFromRowsFn.apply(y, nx)[:, :, :n]
 
-    def _modulations(self, cvec: torch.Tensor):
-        """The depth + 1 Sequential(SiLU, Linear) projections of c: one grouped launch (runtime.film_prepare), else one each."""
-        lins = [b.modulation[1] for b in self.blocks] + [self.final.modulation[1]]
-        grouped = rt.film_prepare(cvec, lins)
-        outs = []
-        for lin in lins:
-            m = rt.film_take(cvec, lin) if grouped else None
-            outs.append(m if m is not None else rt.small_linear(cvec, lin.weight, lin.bias, in_act=ops.ACT_SILU))
-        rt.film_clear()
-        return outs
+    def sample_rows(self, x: torch.Tensor, a_rows: torch.Tensor, cvec: torch.Tensor, n: int, dtype: torch.dtype) -> torch.Tensor:
+        """A sampler's step: the iterate x (B, dim_in_x, n), encode_audio's rows and the conditioning vector -> the prediction."""
+        return self.denoise_rows(self.encode_x(x, a_rows, dtype), cvec, n)
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, t: torch.Tensor, c: torch.Tensor, cond_drop_prob: float = 0.0) -> torch.Tensor:
         rt.require_gpu(x)

@@ -2,7 +2,7 @@
 state_dict keys.  Both streams are rows (B, N, dim_h) in the compute dtype; a block runs the DiT's kernels once per stream (adaLN,
 gated residual, feed-forward: osufusion_amd/dit.py) around one joint attention over [audio; map] (osufusion_amd/mmdit.py).  The tiny
 embedding MLPs run on the skinny-linear kernels and all 2 depth + 1 adaLN modulation projections of a forward in one grouped launch."""
-from typing import Dict, List, Tuple
+from typing import Tuple
 
 import torch
 import torch.nn as nn
@@ -14,9 +14,8 @@ from .. import functional as Fn
 from .. import mmdit as Mm
 from .. import ops
 from .. import runtime as rt
-from .dit import FeedForward, MultiHeadRMSNorm
+from .dit import FeedForward, MultiHeadRMSNorm, _TransformerBackbone
 from .unet import SinusoidalPositionEmbedding
-from .utils import prob_mask_like
 
 __all__ = ["modulate", "SinusoidalPositionEmbedding", "FeedForward", "PatchEmbedding", "MultiHeadRMSNorm", "JointAttention", "MMDiTBlock",
            "FinalLayer", "MMDiT"]
@@ -187,7 +186,7 @@ class FinalLayer(nn.Module):
         return self.forward_rows(x, rt.small_linear(c.float(), lin.weight, lin.bias, in_act=ops.ACT_SILU))
 
 
-class MMDiT(nn.Module):
+class MMDiT(_TransformerBackbone, nn.Module):
     """mmdit.py:241-389."""
 
     def __init__(self, dim_in_x: int, dim_in_a: int, dim_in_c: int, dim_h: int, dim_h_mult: int = 4, patch_size: int = 4, depth: int = 12,
@@ -216,13 +215,7 @@ class MMDiT(nn.Module):
     def initialize_weights(self) -> None:
         """mmdit.py:298-329: xavier-uniform Linear / Conv1d weights and zero biases, N(0, 0.02) embedders, zeroed adaLN modulations,
         final layer and output convolution."""
-        def _basic_init(module: nn.Module) -> None:
-            if isinstance(module, (nn.Linear, nn.Conv1d)):
-                nn.init.xavier_uniform_(module.weight)
-                if module.bias is not None:
-                    nn.init.zeros_(module.bias)
-
-        self.apply(_basic_init)
+        self.apply(self._basic_init)
         for m in (self.mlp_a[0], self.mlp_a[2], self.mlp_time[1][0], self.mlp_time[1][2], self.mlp_cond[1][0], self.mlp_cond[1][2]):
             nn.init.normal_(m.weight, std=0.02)
         for block in self.blocks:
@@ -233,47 +226,15 @@ class MMDiT(nn.Module):
             nn.init.zeros_(m.weight)
             nn.init.zeros_(m.bias)
 
-    def set_gradient_checkpointing(self, value: bool) -> None:
-        """mmdit.py:331-335 (same log line per module)."""
-        for name, module in self.named_modules():
-            if hasattr(module, "gradient_checkpointing"):
-                module.gradient_checkpointing = value
-                print(f"Set gradient checkpointing to {value} for {name}")
-
-    def forward_with_cond_scale(self, *args: List, cond_scale: float = 1.0, **kwargs: Dict) -> torch.Tensor:
-        """mmdit.py:337-344."""
-        logits = self(*args, **kwargs)
-        if cond_scale == 1.0:
-            return logits
-        null_logits = self(*args, **kwargs, cond_drop_prob=1.0)
-        return null_logits + (logits - null_logits) * cond_scale
-
     # -- pieces ---------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _ff(x: torch.Tensor, ff: FeedForward) -> torch.Tensor:
-        h = rt.small_linear(x, ff[0].weight, ff[0].bias)
-        return rt.small_linear(h, ff[2].weight, ff[2].bias, in_act=ops.ACT_SILU)
+    def _embed_cond(self, c: torch.Tensor) -> torch.Tensor:
+        """mlp_cond(c)."""
+        return self._ff(rt.small_linear(c.float(), self.mlp_cond[0].weight, self.mlp_cond[0].bias), self.mlp_cond[1])
 
-    def embed(self, a: torch.Tensor, t: torch.Tensor, c: torch.Tensor, cond_drop_prob: float) -> torch.Tensor:
-        """where(keep, mlp_cond(c), null_cond) + mlp_time(t) + mlp_a(feature_extractor_a(stat_pool(a))) (mmdit.py:355-378), fp32
-        (B, dim_h).  a: the audio before it is padded."""
+    def _embed_audio(self, a: torch.Tensor) -> torch.Tensor:
+        """mlp_a(feature_extractor_a(stat_pool(a))) (mmdit.py:355-359)."""
         fe = self.feature_extractor_a
-        h_a = rt.small_linear(Dt.stat_pool(a), fe.weight, fe.bias)
-        B = a.shape[0]
-        cond_mask = prob_mask_like((B,), 1.0 - cond_drop_prob, device=a.device)
-        e = self._ff(rt.small_linear(c.float(), self.mlp_cond[0].weight, self.mlp_cond[0].bias), self.mlp_cond[1])
-        e = torch.where(cond_mask[:, None], e, self.null_cond.float()[None, :].expand(B, -1))
-        return e + self._ff(self.mlp_time[0](t).float(), self.mlp_time[1]) + self._ff(h_a, self.mlp_a)
-
-    def embed_static(self, a: torch.Tensor, c: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
-        """The part of embed() that does not depend on t: where(keep, mlp_cond(c), null_cond) + mlp_a(feature_extractor_a(stat_pool(a))),
-        fp32 (B, dim_h).  keep: bool (B,).  A sampler computes it once per call and adds embed_time(t) per step."""
-        fe = self.feature_extractor_a
-        h_a = rt.small_linear(Dt.stat_pool(a), fe.weight, fe.bias)
-        B = a.shape[0]
-        e = self._ff(rt.small_linear(c.float(), self.mlp_cond[0].weight, self.mlp_cond[0].bias), self.mlp_cond[1])
-        e = torch.where(keep[:, None], e, self.null_cond.float()[None, :].expand(B, -1))
-        return e + self._ff(h_a, self.mlp_a)
+        return self._ff(rt.small_linear(Dt.stat_pool(a), fe.weight, fe.bias), self.mlp_a)
 
     def embed_time(self, t: torch.Tensor) -> torch.Tensor:
         """mlp_time(t), fp32 (B, dim_h)."""
@@ -293,7 +254,8 @@ class MMDiT(nn.Module):
     def denoise_rows(self, h_x: torch.Tensor, h_a: torch.Tensor, cvec: torch.Tensor, n: int) -> torch.Tensor:
         """The two streams' patch rows and the conditioning vector (fp32 (B, dim_h), contiguous) -> the prediction (B, dim_in_x, n)."""
         p = self.patch_size
-        mods = self._modulations(cvec)
+        lins = [m for b in self.blocks for m in (b.modulation_x[1], b.modulation_a[1])] + [self.final_layer.modulation[1]]
+        mods = self._modulations(cvec, lins)                                    # 2 depth + 1
         for i, block in enumerate(self.blocks):
             h_x, h_a = block.forward_rows(h_x, h_a, mods[2 * i], mods[2 * i + 1])
         h = self.final_layer.forward_rows(h_x, mods[-1])                        # (B, N, p dim_h)
@@ -306,16 +268,9 @@ class MMDiT(nn.Module):
         y = Fn.ConvFn.apply(h, w, b, self._out_cache, "same", ("out", self.out.weight))
         return Fn.NCLFromRowsFn.apply(y, nx)[:, :, :n]
 
-    def _modulations(self, cvec: torch.Tensor):
-        """The 2 depth + 1 Sequential(SiLU, Linear) projections of c: one grouped launch (runtime.film_prepare), else one each."""
-        lins = [m for b in self.blocks for m in (b.modulation_x[1], b.modulation_a[1])] + [self.final_layer.modulation[1]]
-        grouped = rt.film_prepare(cvec, lins)
-        outs = []
-        for lin in lins:
-            m = rt.film_take(cvec, lin) if grouped else None
-            outs.append(m if m is not None else rt.small_linear(cvec, lin.weight, lin.bias, in_act=ops.ACT_SILU))
-        rt.film_clear()
-        return outs
+    def sample_rows(self, x: torch.Tensor, a_rows: torch.Tensor, cvec: torch.Tensor, n: int, dtype: torch.dtype) -> torch.Tensor:
+        """A sampler's step: the iterate x (B, dim_in_x, n), encode_audio's rows and the conditioning vector -> the prediction."""
+        return self.denoise_rows(self.encode_x(x, dtype), a_rows, cvec, n)
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, t: torch.Tensor, c: torch.Tensor, cond_drop_prob: float = 0.0) -> torch.Tensor:
         rt.require_gpu(x)

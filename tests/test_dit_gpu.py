@@ -1,6 +1,7 @@
 """The DiT backbone on the GPU: its row kernels (adaLN, QK-norm, statistics pooling) against fp64 torch, and the module against the
 torch restatement (tests/dit_oracle.py) and the reference's fixtures (tests/golden/dit_*.npz)."""
 import copy
+import hashlib
 import json
 from pathlib import Path
 
@@ -101,6 +102,39 @@ def test_qknorm_fwd_bwd_vs_fp64(D, H, dtype):
         assert e < tol, ("qkv"[blk], e)
     assert rell2(dgamma[0].cpu(), gqr.grad.reshape(H, D)) < 1e-5
     assert rell2(dgamma[1].cpu(), gkr.grad.reshape(H, D)) < 1e-5
+
+
+QKNORM_DIGESTS = json.loads((GOLD / "qknorm_parent_digests.json").read_text())
+
+
+def _sha256(*tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes())
+    return h.hexdigest()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("H,D", [(1, 128), (4, 64), (8, 64), (8, 128), (2, 16)])
+def test_qknorm_bits_equal_the_single_stream_kernels(H, D, dtype):
+    """dit.qknorm_fwd / _bwd ran on kernels of their own (qknorm_fwd_kernel / qknorm_bwd_kernel) before they became the one-stream, G = H
+    call of the joint kernels.  tests/golden/qknorm_parent_digests.json holds the SHA-256 of what those kernels wrote on an MI355X for the
+    inputs of test_qknorm_fwd_bwd_vs_fp64 (134 rows: not a multiple of 4, 9 backward workgroups; the two all-zero heads), one case per
+    chunk-loop depth J = 1, 2, 4, 8 and per head width of 2, 8 and 16 lanes, for both raw dtypes: every output bit is still the same.
+    The digest of the inputs is checked first, so a changed generator is told apart from a changed kernel."""
+    B, L = 2, 67
+    raw = rnd("raw", (B, L, 3 * H * D)).to(dtype)
+    raw[0, 3, :D] = 0
+    raw[1, 5, H * D:H * D + D] = 0
+    gq, gk, g = 1 + 0.2 * rnd("gq", (H, 1, D)), 1 + 0.2 * rnd("gk", (H, 1, D)), rnd("g", (B, L, 3 * H * D))
+    want = QKNORM_DIGESTS[f"H{H}_D{D}_{'f32' if dtype == torch.float32 else 'bf16'}"]
+    assert _sha256(raw, gq, gk, g) == want["inputs"], "the generated inputs differ from the recorded ones"
+    raw, gq, gk, g = (t.to(DEV) for t in (raw, gq, gk, g))
+    y, inv = Dt.qknorm_fwd(raw, gq, gk, H, D)
+    dx, dgamma = Dt.qknorm_bwd(g, raw, inv, gq, gk, H, D)
+    assert y.dtype == torch.bfloat16 and tuple(inv.shape) == (B * L, 2 * H) and dx.dtype == dtype and tuple(dgamma.shape) == (2, H, D)
+    got = {"y": _sha256(y), "inv": _sha256(inv), "dx": _sha256(dx), "dgamma": _sha256(dgamma)}
+    assert got == {k: want[k] for k in got}
 
 
 @pytest.mark.parametrize("L", [1, 7, 4096])

@@ -63,7 +63,7 @@ def _within_one_bf16_spacing(got, ref):
 @pytest.mark.parametrize("shape", KERNEL_SHAPES, ids=lambda s: "B%d_Na%d_Nx%d_H%d_G%d_D%d" % s)
 def test_joint_qknorm_fwd_bwd_vs_fp64(shape, gamma, dtype):
     """Forward: every bf16 output within one bf16 spacing of the fp64 value; inv within 1e-5 (fp32 sum of D <= 128 squares and one
-    reciprocal: D 2^-24 < 1e-5).  Backward at the bounds tests/test_dit_gpu.py holds osuf_qknorm_bwd to: the raw-projection gradient
+    reciprocal: D 2^-24 < 1e-5).  Backward at the bounds tests/test_dit_gpu.py holds dit.qknorm_bwd to: the raw-projection gradient
     1e-5 (fp32 rows) / 1e-2 (bf16 rows) rel-L2 per q / k / v block, the clamped head on its own; dgamma 1e-5.  A stream's call leaves the
     other stream's joint rows untouched."""
     B, Na, Nx, H, G, D = shape
@@ -144,7 +144,9 @@ def test_joint_reductions_bit_identical_across_launches():
 
 
 def test_joint_norm_matches_the_single_stream_kernel_bit_for_bit():
-    """G = H, one stream: osuf_joint_qknorm_fwd / _bwd are osuf_qknorm_fwd / _bwd (the joint layout is then the plain q|k|v rows)."""
+    """G = H, one stream: the joint layout is the plain q|k|v rows, and dit.qknorm_fwd / _bwd are the joint kernels called that way (their
+    Ns / off / G mapping and the inv / dgamma shapes).  The single-stream kernels these replaced are pinned by
+    tests/golden/qknorm_parent_digests.json (tests/test_dit_gpu.py)."""
     from osufusion_amd import dit as Dt
     B, N, H, D = 2, 67, 4, 32
     raw = rnd("raw", (B, N, 3 * H * D)).to(DEV).bfloat16()
@@ -156,6 +158,10 @@ def test_joint_norm_matches_the_single_stream_kernel_bit_for_bit():
     jinv = Mm.joint_qknorm_fwd(raw, joint, 0, gq, gk, H, H, D)
     jdx, jdgamma = Mm.joint_qknorm_bwd(g, raw, 0, jinv, gq, gk, H, H, D)
     assert torch.equal(joint, y) and torch.equal(jinv, inv) and torch.equal(jdx, dx) and torch.equal(jdgamma.view(2, H, D), dgamma)
+    # the same stream at row offset 3 of a longer joint buffer: the forward kernel's general instance (row and head maps not compiled out)
+    wide = torch.empty((B, N + 3, 3 * H * D), dtype=torch.bfloat16, device=DEV)
+    winv = Mm.joint_qknorm_fwd(raw, wide, 3, gq, gk, H, H, D)
+    assert torch.equal(wide[:, 3:], y) and torch.equal(winv, inv)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
