@@ -555,6 +555,16 @@ int osuf_vqt_logmag(const float* spec, long ld, float* out, long ldo, const floa
 int osuf_fir_decimate2(const float* in, long n_in, const float* taps, int ntaps, float* out, long n_out, hipStream_t stream);
 int osuf_frame_rows(const float* in, long n_in, int hop, int K, float* out, long frames, hipStream_t stream);
 
+/* Sample-rate conversion in front of the transform    replaces: librosa.load(file, sr=22050, res_type="kaiser_best")'s resampy pass
+ * (scripts/dataset_creator.py:37-38).  sr_new / sr_orig = L / M in lowest terms; table: [L][T] fp32, row p = the weights of every output
+ * t with t*M % L == p (both wings of resampy's windowed sinc, built by osufusion_amd/audio.py resample_plan); x_pad: the input with
+ * enough zeros on both sides that no output needs an end case.
+ *     y[t] = sum_j table[t*M % L][j] * x_pad[base0 + (t*M)/L + j],  t < n_out      (64-bit positions; fp32 accumulation in tap order)
+ * No atomics: an output's bits do not depend on n_out or on the launch.  y may point into a larger zero-padded buffer.
+ * OSUF_EINVAL: a null pointer, a non-positive size, base0 < 0 or base0 + ((n_out-1)*M)/L + T > n_pad. */
+int osuf_resample(const float* x_pad, long n_pad, const float* table, int L, int M, int T, long base0, float* y, long n_out,
+                  hipStream_t stream);
+
 /* ---- DiT row kernels (dit.hip)    replaces: osu_fusion/modules/dit.py:14-15 modulate(LayerNorm(x)), 275-277 the audio statistics
  *      pooling (63-70 MultiHeadRMSNorm: osuf_joint_qknorm_fwd / _bwd below, one stream and G = H).  Rows [M][C], M = B * L, sample of row m = m / L; C % 8 == 0, C <= 2048; row strides multiples of 8
  *      elements, 16-B aligned pointers.  No atomics: every cross-row sum goes through per-workgroup partials added in a fixed order.

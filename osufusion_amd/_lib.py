@@ -104,6 +104,7 @@ SIGNATURES = {
     "osuf_vqt_logmag": [P, L, P, L, P, I, L, F, P],
     "osuf_fir_decimate2": [P, L, P, I, P, L, P],
     "osuf_frame_rows": [P, L, I, I, P, L, P],
+    "osuf_resample": [P, L, P, I, I, I, L, P, L, P],
     "osuf_skinny_fwd": [I, P, L, P, P, P, L, I, I, I, I, I, P],
     "osuf_skinny_bwd": [I, P, L, P, L, P, L, P, P, L, P, P, I, I, I, I, I, I, P],
     "osuf_skinny_fwd_group": [I, P, L, P, I, I, I, I, I, P],

@@ -19,12 +19,15 @@ of the new Nyquist, ~125 dB) -- every octave's filters sit below 0.36 of its Nyq
 taps move the result by ~1e-5 of the peak.  ``log_vqt_direct`` keeps round 1's full-rate direct form (the quantity the recursion
 approximates: differs by up to 2 % of the peak in the three lowest octaves).  librosa is absent from the build image and the
 reference holds no spectrogram fixtures, so the front end is **parity unpinned** against the reference.
+
+In front of the transform, ``load_audio`` brings a file to SR as ``librosa.load(file, sr=22050, res_type="kaiser_best")`` does:
+resampy's windowed-sinc interpolation, restated from its published algorithm (resampy is absent too: constants unpinned), as a
+per-phase weight table built on the host (``resample_plan``) and one HIP kernel (``osuf_resample``; ``resample``).
 """
 from __future__ import annotations
 
 import functools
 import math
-import wave as _wave
 from pathlib import Path
 from typing import NamedTuple, Union
 
@@ -242,19 +245,189 @@ def log_vqt_direct(wave: Union[np.ndarray, torch.Tensor], device: Union[str, tor
     return ops.log_vqt(y_pad, bank, scale, HOP_LENGTH, frames, LOG_EPS)
 
 
-def read_wave(audio_file: Union[str, Path]) -> np.ndarray:
-    """Decode a PCM .wav (or a .npy waveform already at SR) to mono float32 at SR.  The reference decodes any container through
-    ffmpeg (audioread) and resamples with resampy's kaiser_best (dataset_creator.py:37-38); neither exists in this image, so
-    other rates go through scipy's polyphase resampler and other containers are rejected."""
+# ---------------------------------------------------------------------------------------------------------------- resampling
+# resampy's band-limited sinc interpolation (librosa.load(..., res_type="kaiser_best"), dataset_creator.py:37-38), restated from its
+# published algorithm: a Kaiser-windowed sinc tabulated at 2**precision points per zero crossing, read with linear interpolation
+# between table points, the left wing over x[n], x[n-1], ... and the right wing over x[n+1], ... of output time t / ratio = n + frac.
+# resampy is not in this image; the constants are quoted from its documentation (parity unpinned).
+RES_FILTERS = {                                   # num_zeros, precision, rolloff, Kaiser beta
+    "kaiser_best": (64, 9, 0.9475937167399596, 14.769656459379492),
+    "kaiser_fast": (16, 9, 0.85, 8.555504641634386),
+}
+
+
+class ResamplePlan(NamedTuple):
+    table: np.ndarray       # (L, T) float32: row p holds the weights of every output t with t*M % L == p, oldest input sample first
+    L: int                  # sr_new / gcd
+    M: int                  # sr_orig / gcd
+    T: int                  # taps per row: left wing + right wing, rounded up to a multiple of 4 with zero weights
+    t_left: int             # longest left wing: output t reads x[(t*M)//L - (t_left - 1) + j], j < T
+
+
+def _check_rates(sr_orig: int, sr_new: int, res_type: str):
+    if res_type not in RES_FILTERS:
+        raise ValueError(f"unsupported res_type {res_type!r}: one of {sorted(RES_FILTERS)}")
+    if int(sr_orig) != sr_orig or int(sr_new) != sr_new or sr_orig <= 0 or sr_new <= 0:
+        raise ValueError(f"sample rates must be positive integers, got {sr_orig!r} -> {sr_new!r}")
+    g = math.gcd(int(sr_orig), int(sr_new))
+    return int(sr_new) // g, int(sr_orig) // g
+
+
+def resample_phase(t: int, L: int, M: int):
+    """(n, p): output t sits at input time t*M/L = n + p/L, in integer arithmetic (exact for any t, where t * (1/ratio) in floating
+    point loses the phase: fp32 near t ~ 1e7, fp64 near 1e15)."""
+    return divmod(int(t) * M, L)
+
+
+def resample_table(sr_orig: int, sr_new: int, res_type: str = "kaiser_best"):
+    """-> (W, t_left): the fp64 weights W[L][T] of every phase, both wings with the linear interpolation between table points folded in.
+    The weights of an output depend on t only through p = t*M % L, so L rows serve every t."""
+    L, M = _check_rates(sr_orig, sr_new, res_type)
+    num_zeros, precision, rolloff, beta = RES_FILTERS[res_type]
+    ratio = float(sr_new) / float(sr_orig)
+    n = num_zeros * 2 ** precision
+    win = rolloff * np.sinc(rolloff * np.arange(n + 1, dtype=np.float64) / 2 ** precision) * np.kaiser(2 * n + 1, beta)[n:]
+    scale = min(1.0, ratio)
+    if ratio < 1:
+        win = win * ratio
+    delta = np.diff(win, append=0.0)
+    num_table = 2 ** precision
+    step = int(scale * num_table)
+    if step < 1:
+        raise ValueError(f"{sr_orig} -> {sr_new} Hz: the filter table has {num_table} points per zero crossing, too few for this ratio")
+    nwin = n + 1
+    part = np.arange(L, dtype=np.float64) / L                         # fractional part of the output time, exact rational rounded once
+
+    def wing(frac):
+        index_frac = frac * num_table
+        offset = index_frac.astype(np.int64)
+        eta = index_frac - offset
+        count = (nwin - offset) // step                               # resampy's wing length (it leaves out a last tap at index n)
+        idx = offset[:, None] + step * np.arange(int(count.max()), dtype=np.int64)[None, :]
+        live = np.arange(idx.shape[1])[None, :] < count[:, None]
+        idx = np.where(live, idx, 0)
+        return np.where(live, win[idx] + eta[:, None] * delta[idx], 0.0)
+
+    left = wing(scale * part)                                         # tap i on x[n - i]
+    right = wing(scale - scale * part)                                # tap k on x[n + 1 + k]
+    t_left = left.shape[1]
+    T = -(-(t_left + right.shape[1]) // 4) * 4
+    W = np.zeros((L, T), dtype=np.float64)
+    W[:, :t_left] = left[:, ::-1]
+    W[:, t_left:t_left + right.shape[1]] = right
+    return W, t_left
+
+
+@functools.lru_cache(maxsize=8)
+def resample_plan(sr_orig: int, sr_new: int = SR, res_type: str = "kaiser_best") -> ResamplePlan:
+    """Host plan of osuf_resample, cached per (sr_orig, sr_new, res_type): y[t] = sum_j table[t*M % L][j] * x[(t*M)//L - (t_left-1) + j]
+    with x zero outside the signal (the truncated wings of resampy at both ends are exactly that zero padding)."""
+    L, M = _check_rates(sr_orig, sr_new, res_type)
+    W, t_left = resample_table(sr_orig, sr_new, res_type)
+    return ResamplePlan(np.ascontiguousarray(W, dtype=np.float32), L, M, W.shape[1], t_left)
+
+
+def resample_length(n_orig: int, sr_orig: int, sr_new: int, fix: bool = False) -> int:
+    """resampy's output length int(n * ratio); with fix, librosa.resample's ceil(n * ratio) (both in fp64, as they compute them)."""
+    r = n_orig * (float(sr_new) / float(sr_orig))
+    return int(math.ceil(r)) if fix else int(r)
+
+
+_DEVICE_TABLES = {}
+
+
+def _device_table(sr_orig: int, sr_new: int, res_type: str, device: torch.device):
+    key = (sr_orig, sr_new, res_type, str(device))
+    if key not in _DEVICE_TABLES:
+        if len(_DEVICE_TABLES) >= 8:
+            _DEVICE_TABLES.pop(next(iter(_DEVICE_TABLES)))
+        plan = resample_plan(sr_orig, sr_new, res_type)
+        _DEVICE_TABLES[key] = (plan, torch.from_numpy(plan.table).to(device))
+    return _DEVICE_TABLES[key]
+
+
+def resample(wave: Union[np.ndarray, torch.Tensor], orig_sr: int, target_sr: int = SR, res_type: str = "kaiser_best",
+             device: Union[str, torch.device] = "cuda", fix: bool = True) -> torch.Tensor:
+    """librosa.resample(wave, orig_sr=, target_sr=, res_type=, fix=, scale=False) for a mono waveform, on the GPU (osuf_resample):
+    int(n * ratio) samples, zero-padded to ceil(n * ratio) with fix (at most one sample).  Equal rates return the input unchanged.
+    The result is a tensor of its own: log_vqt copies it once into the first octave's padded frame buffer."""
+    L, M = _check_rates(orig_sr, target_sr, res_type)
+    x = torch.as_tensor(wave)
+    if x.dim() != 1:
+        raise ValueError(f"expected a mono waveform, got shape {tuple(x.shape)}")
+    if L == M:
+        return wave
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("osufusion_amd.audio.resample runs on the GPU only (no CPU fallback)")
+    plan, table = _device_table(int(orig_sr), int(target_sr), res_type, device)
+    n = x.numel()
+    n_out = resample_length(n, orig_sr, target_sr)
+    out = torch.zeros(resample_length(n, orig_sr, target_sr, fix=True) if fix else n_out, dtype=torch.float32, device=device)
+    if n_out > 0:
+        front = plan.t_left - 1                                       # zeros in front: output 0's left wing
+        last = ((n_out - 1) * plan.M) // plan.L                       # integer input position of the last output
+        x_pad = torch.zeros(max(front + n, last + plan.T), dtype=torch.float32, device=device)
+        x_pad[front:front + n] = x.to(device=device, dtype=torch.float32)
+        ops.resample(x_pad, table, plan.L, plan.M, 0, out[:n_out])
+    return out
+
+
+_WAVE_FORMAT_PCM, _WAVE_FORMAT_IEEE_FLOAT, _WAVE_FORMAT_EXTENSIBLE = 0x0001, 0x0003, 0xFFFE
+
+
+def _read_riff(path: Path):
+    """Minimal RIFF/WAVE chunk parser -> (format tag, channels, rate, bytes per sample, raw sample bytes).  Integer PCM, IEEE float and
+    WAVE_FORMAT_EXTENSIBLE headers (whose sub-format's first two bytes are one of the former tags)."""
+    import struct
+    blob = path.read_bytes()
+    if len(blob) < 12 or blob[:4] != b"RIFF" or blob[8:12] != b"WAVE":
+        raise ValueError(f"{path}: not a RIFF/WAVE file")
+    fmt, data, pos = None, None, 12
+    while pos + 8 <= len(blob):
+        cid, size = blob[pos:pos + 4], struct.unpack_from("<I", blob, pos + 4)[0]
+        body = blob[pos + 8:pos + 8 + size]
+        if cid == b"fmt ":
+            fmt = body
+        elif cid == b"data":
+            data = body
+            break
+        pos += 8 + size + (size & 1)                                  # chunks are word-aligned
+    if fmt is None or len(fmt) < 16 or data is None:
+        raise ValueError(f"{path}: missing fmt or data chunk")
+    tag, ch, rate, _, align, bits = struct.unpack_from("<HHIIHH", fmt, 0)
+    if tag == _WAVE_FORMAT_EXTENSIBLE:
+        if len(fmt) < 40:
+            raise ValueError(f"{path}: truncated WAVE_FORMAT_EXTENSIBLE header")
+        tag = struct.unpack_from("<H", fmt, 24)[0]
+    if ch < 1 or rate < 1 or bits % 8 or align != ch * (bits // 8):
+        raise ValueError(f"{path}: unsupported layout ({ch} channels, {bits} bits, block align {align})")
+    width = bits // 8
+    return tag, ch, rate, width, data[:len(data) // (ch * width) * (ch * width)]
+
+
+def read_wave(audio_file: Union[str, Path], resample: bool = True):
+    """Decode a .wav (integer PCM of 8 / 16 / 24 / 32 bits or 32-bit IEEE float, plain or WAVE_FORMAT_EXTENSIBLE header) or a .npy
+    waveform already at SR to mono float32 (the mean over channels).  The reference decodes any container through ffmpeg (audioread);
+    there is none here, other containers are rejected.
+
+    resample=True (the default) returns the waveform at SR; a file at another rate is resampled ON THE HOST with
+    scipy.signal.resample_poly (its default Kaiser(5) FIR: not the reference's filter).  resample=False returns (waveform, rate) at the
+    file's own rate, which is what load_audio takes so that it can resample as the reference does (resampy's kaiser_best, `resample`)."""
     path = Path(audio_file)
     if path.suffix == ".npy":
-        return np.asarray(np.load(path), dtype=np.float32).reshape(-1)
+        data = np.asarray(np.load(path), dtype=np.float32).reshape(-1)
+        return data if resample else (data, SR)
     if path.suffix.lower() != ".wav":
         raise ValueError(f"unsupported audio container {path.suffix!r}: decode to PCM .wav first (no ffmpeg in this build)")
-    with _wave.open(str(path), "rb") as f:
-        ch, width, rate, n = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
-        raw = f.readframes(n)
-    if width == 1:
+    tag, ch, rate, width, raw = _read_riff(path)
+    if tag == _WAVE_FORMAT_IEEE_FLOAT:
+        if width != 4:
+            raise ValueError(f"unsupported IEEE-float sample width {width}")
+        data = np.frombuffer(raw, dtype="<f4").astype(np.float32)
+    elif tag != _WAVE_FORMAT_PCM:
+        raise ValueError(f"unsupported WAVE format tag {tag:#06x}")
+    elif width == 1:
         data = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
     elif width == 2:
         data = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
@@ -267,6 +440,8 @@ def read_wave(audio_file: Union[str, Path]) -> np.ndarray:
     else:
         raise ValueError(f"unsupported sample width {width}")
     data = data.reshape(-1, ch).mean(axis=1) if ch > 1 else data
+    if not resample:
+        return np.ascontiguousarray(data, dtype=np.float32), rate
     if rate != SR:
         from scipy.signal import resample_poly
         g = math.gcd(SR, rate)
@@ -274,10 +449,15 @@ def read_wave(audio_file: Union[str, Path]) -> np.ndarray:
     return np.ascontiguousarray(data, dtype=np.float32)
 
 
-def load_audio(audio_file: Union[str, Path], device: Union[str, torch.device] = "cuda") -> torch.Tensor:
-    """dataset_creator.load_audio: file -> (96, n_frames) log-VQT.  Returns a device tensor (call .cpu().numpy() for the
-    reference's ndarray)."""
-    wave = read_wave(audio_file)
+def load_audio(audio_file: Union[str, Path], device: Union[str, torch.device] = "cuda", res_type: str = "kaiser_best") -> torch.Tensor:
+    """dataset_creator.load_audio: file -> (96, n_frames) log-VQT, the waveform brought to SR as librosa.load(file, sr=SR,
+    res_type=res_type) brings it there (`resample`, on the GPU).  Returns a device tensor (call .cpu().numpy() for the reference's
+    ndarray)."""
+    wave, rate = read_wave(audio_file, resample=False)
     if wave.shape[0] == 0:
         raise ValueError(f"Empty audio file: {audio_file}")
+    if rate != SR:
+        wave = resample(wave, rate, SR, res_type, device)
+        if wave.numel() == 0:
+            raise ValueError(f"Empty audio file: {audio_file}")
     return log_vqt(wave, device)

@@ -74,7 +74,77 @@ __global__ __launch_bounds__(256) void frame_rows_kernel(const float* __restrict
   }
 }
 
+// Rational-ratio resampling (resampy's windowed-sinc interpolation; reference: librosa.load(file, sr=22050, res_type="kaiser_best"),
+// scripts/dataset_creator.py:37-38).  With sr_new / sr_orig = L / M in lowest terms, output t sits at input time t*M/L: its weights
+// depend on t only through t*M % L, so the host tabulates one row of T weights per phase (osufusion_amd/audio.py) and
+//     y[t] = sum_j table[t*M % L][j] * x_pad[base0 + (t*M)/L + j]        (positions in 64-bit integers, never t * increment)
+// A workgroup takes kRun consecutive outputs, one per lane, and stages the input span they cover in LDS once (2*kRun + T floats at
+// ratio 1/2); the single row of L == 1 is staged too, other rows are read through L2 (a lane's row is contiguous, 16-byte aligned).
+// fp32 accumulation in tap order, plain stores, no atomics: an output's bits depend on nothing but its own taps.
+constexpr int kRun = 256;
+constexpr int kResampleLds = 64 * 1024;      // bytes of LDS the two staged arrays may take; a span or a row beyond it is read in place
+
+template <bool kStage, bool kRowLds>
+__global__ __launch_bounds__(kRun) void resample_kernel(const float* __restrict__ x_pad, const float* __restrict__ table, int L, int M, int T,
+                                                        long base0, float* __restrict__ y, long n_out, int row_floats) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];      // [kRowLds ? T : 0] row, then [kStage ? span : 0] input
+  const long t0 = (long)blockIdx.x * kRun;
+  const long left = n_out - t0;
+  const int nt = left < kRun ? (int)left : kRun;
+  const long q0 = t0 * M / L;
+  const float* __restrict__ src = x_pad + base0 + q0;
+  if (kRowLds)
+    for (int j = threadIdx.x; j < T; j += kRun) rs_lds[j] = table[j];
+  if (kStage) {
+    const int span = (int)((t0 + nt - 1) * M / L - q0) + T;
+    for (int e = threadIdx.x; e < span; e += kRun) rs_lds[row_floats + e] = src[e];
+  }
+  if (kStage || kRowLds) __syncthreads();
+  if ((int)threadIdx.x >= nt) return;
+  const long tm = (t0 + threadIdx.x) * M;
+  const long q = tm / L;
+  const int off = (int)(q - q0);
+  float acc = 0.f;
+  if constexpr (kStage && kRowLds) {
+    const float* xs = rs_lds + row_floats + off;
+    for (int j = 0; j < T; ++j) acc = fmaf(rs_lds[j], xs[j], acc);
+  } else if constexpr (kStage) {
+    const float* xs = rs_lds + off;
+    const float* __restrict__ w = table + (tm - q * L) * T;
+    for (int j = 0; j < T; ++j) acc = fmaf(w[j], xs[j], acc);
+  } else if constexpr (kRowLds) {
+    const float* __restrict__ xs = src + off;
+    for (int j = 0; j < T; ++j) acc = fmaf(rs_lds[j], xs[j], acc);
+  } else {
+    const float* __restrict__ xs = src + off;
+    const float* __restrict__ w = table + (tm - q * L) * T;
+    for (int j = 0; j < T; ++j) acc = fmaf(w[j], xs[j], acc);
+  }
+  y[t0 + threadIdx.x] = acc;
+}
+
 }  // namespace
+
+// x_pad: the zero-padded input (n_pad floats); table: [L][T] fp32 weights, row p for the outputs with t*M % L == p;
+// y[t] = sum_j table[t*M % L][j] * x_pad[base0 + (t*M)/L + j], t < n_out.  Every read index is checked here against [0, n_pad).
+extern "C" int osuf_resample(const float* x_pad, long n_pad, const float* table, int L, int M, int T, long base0, float* y, long n_out,
+                             hipStream_t stream) {
+  if (!x_pad || !table || !y || n_pad <= 0 || n_out <= 0 || L <= 0 || M <= 0 || T <= 0 || base0 < 0) return OSUF_EINVAL;
+  if (n_out > (1L << 62) / M || (n_out + kRun - 1) / kRun > 0x7fffffffL) return OSUF_EINVAL;       // t*M in 64 bits; the grid
+  const long last = (n_out - 1) * M / L;
+  if (base0 > n_pad - T || last > n_pad - T - base0) return OSUF_EINVAL;                            // the last output's last tap
+  const long span = ((long)(kRun - 1) * M + L - 1) / L + T;                                         // floats one run can cover
+  const bool row_lds = L == 1 && (long)T * 4 <= kResampleLds / 2;
+  const int row_floats = row_lds ? T : 0;
+  const bool stage = (span + row_floats) * 4 <= kResampleLds;
+  const unsigned grid = (unsigned)((n_out + kRun - 1) / kRun);
+  const size_t lds = (size_t)(row_floats + (stage ? span : 0)) * sizeof(float);
+  if (stage && row_lds) resample_kernel<true, true><<<grid, kRun, lds, stream>>>(x_pad, table, L, M, T, base0, y, n_out, row_floats);
+  else if (stage) resample_kernel<true, false><<<grid, kRun, lds, stream>>>(x_pad, table, L, M, T, base0, y, n_out, row_floats);
+  else if (row_lds) resample_kernel<false, true><<<grid, kRun, lds, stream>>>(x_pad, table, L, M, T, base0, y, n_out, row_floats);
+  else resample_kernel<false, false><<<grid, kRun, lds, stream>>>(x_pad, table, L, M, T, base0, y, n_out, row_floats);
+  return osuf_launch_status();
+}
 
 extern "C" int osuf_fir_decimate2(const float* in, long n_in, const float* taps, int ntaps, float* out, long n_out, hipStream_t stream) {
   if (!in || !taps || !out || n_in <= 0 || n_out <= 0 || ntaps <= 0 || ntaps > 8192 || (ntaps & 1) == 0) return OSUF_EINVAL;

@@ -1070,6 +1070,16 @@ def frame_rows(sig: torch.Tensor, hop: int, K: int, frames: int) -> torch.Tensor
     return out
 
 
+def resample(x_pad: torch.Tensor, table: torch.Tensor, L: int, M: int, base0: int, out: torch.Tensor) -> torch.Tensor:
+    """out[t] = sum_j table[t*M % L][j] * x_pad[base0 + (t*M)//L + j] (audio.hip osuf_resample); `out`: the caller's buffer, e.g. the
+    interior of a zero-padded one."""
+    for t in (x_pad, table, out):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert x_pad.dim() == 1 and out.dim() == 1 and table.dim() == 2 and table.shape[0] == L
+    call("osuf_resample", _p(x_pad), x_pad.numel(), _p(table), L, M, table.shape[1], base0, _p(out), out.numel(), _stream())
+    return out
+
+
 def log_vqt(wave_pad: torch.Tensor, bank: torch.Tensor, scale: torch.Tensor, hop: int, frames: int, eps: float = 1e-10,
             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[k][t] = log(scale[k] |sum_n wave_pad[t*hop+n] (bank[k][n] + i bank[bins+k][n])| + eps) -> (bins, frames) fp32 (audio.hip);
