@@ -275,7 +275,12 @@ long osuf_mqa_bwd_fused_workspace_bytes(int B, int H, int N, int out_dtype, int 
  * replaces: the (B,C,L) <-> (B,L,C) rearranges (modules/unet.py:180,183) at the model boundary, torch.cat (unet.py:500,
  *           507,510), DDIMScheduler.add_noise / .step (models/diffusion.py:96,75; diffusers 0.29.2), the CFG combine
  *           (unet.py:465), F.mse_loss + mask (diffusion.py:101-111), get_total_norm / clip_grad_norm_ / AdamW.step
- *           (trainer.py:32-39,302-307). */
+ *           (trainer.py:32-39,302-307).
+ * OSUF_EINVAL, nothing launched: a size < 1; width, cols or a leading dimension that is no multiple of 8 (8-wide chunks); width <
+ * C * KT or > ld; osuf_rows_to_ncl's ld < C; a NULL in / out / src / dst / a / b, pred / target / loss_sum, osuf_sqnorm's g / out,
+ * osuf_clip_coef's sumsq / coef; a pointer off a 16-byte boundary where the kernel moves 16 bytes per access (osuf_ncl_to_rows' out,
+ * osuf_copy2d's and osuf_add2d's operands, osuf_sqnorm's g, osuf_adamw's four buffers, osuf_cast_f32_bf16's src and dst); step < 1.
+ * OSUF_EUNSUPPORTED: an unknown dtype code.  Checked case by case in tests/test_elementwise_rows_gpu.py. */
 int osuf_ncl_to_rows(int dtype, const float* in, void* out, long ld, int width, int B, int C, int L, int KT, hipStream_t stream);
 int osuf_rows_to_ncl(int dtype, const void* in, long ld, float* out, int B, int C, int L, hipStream_t stream);
 int osuf_copy2d(int src_dtype, const void* src, long lds, int dst_dtype, void* dst, long ldd, int M, int cols, hipStream_t stream);

@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256) void cast_flat_kernel(const float* src, bf16_t
 // ------------------------------------------------------------------------------------------------------------
 
 extern "C" int osuf_ncl_to_rows(int dtype, const float* in, void* out, long ld, int width, int B, int C, int L, int KT, hipStream_t stream) {
-  if (B <= 0 || C <= 0 || L <= 0 || KT <= 0 || width % 8 || ld % 8 || width < C * KT || width > ld || !al16(out)) return OSUF_EINVAL;
+  if (!in || !out || B <= 0 || C <= 0 || L <= 0 || KT <= 0 || width % 8 || ld % 8 || width < C * KT || width > ld || !al16(out)) return OSUF_EINVAL;
   const long tot = (long)B * L * (width / 8);
   if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL(ncl_to_rows_kernel<bf16_t>, dim3(ew_grid(tot)), dim3(256), 0, stream, in, (bf16_t*)out, ld, width, B, C, L, KT);
   else if (dtype == OSUF_DT_F32) hipLaunchKernelGGL(ncl_to_rows_kernel<float>, dim3(ew_grid(tot)), dim3(256), 0, stream, in, (float*)out, ld, width, B, C, L, KT);
@@ -318,7 +318,7 @@ extern "C" int osuf_ncl_to_rows(int dtype, const float* in, void* out, long ld, 
 }
 
 extern "C" int osuf_rows_to_ncl(int dtype, const void* in, long ld, float* out, int B, int C, int L, hipStream_t stream) {
-  if (B <= 0 || C <= 0 || L <= 0 || ld < C) return OSUF_EINVAL;
+  if (!in || !out || B <= 0 || C <= 0 || L <= 0 || ld < C) return OSUF_EINVAL;
   const long tot = (long)B * C * L;
   if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL(rows_to_ncl_kernel<bf16_t>, dim3(ew_grid(tot)), dim3(256), 0, stream, (const bf16_t*)in, ld, out, B, C, L);
   else if (dtype == OSUF_DT_F32) hipLaunchKernelGGL(rows_to_ncl_kernel<float>, dim3(ew_grid(tot)), dim3(256), 0, stream, (const float*)in, ld, out, B, C, L);
@@ -327,7 +327,7 @@ extern "C" int osuf_rows_to_ncl(int dtype, const void* in, long ld, float* out, 
 }
 
 extern "C" int osuf_copy2d(int src_dtype, const void* src, long lds_, int dst_dtype, void* dst, long ldd, int M, int cols, hipStream_t stream) {
-  if (M <= 0 || cols <= 0 || cols % 8 || lds_ % 8 || ldd % 8 || !al16(src) || !al16(dst)) return OSUF_EINVAL;
+  if (!src || !dst || M <= 0 || cols <= 0 || cols % 8 || lds_ % 8 || ldd % 8 || !al16(src) || !al16(dst)) return OSUF_EINVAL;
   const long tot = (long)M * (cols / 8);
   const dim3 g(ew_grid(tot)), b(256);
   if (src_dtype == OSUF_DT_BF16 && dst_dtype == OSUF_DT_BF16) hipLaunchKernelGGL((copy2d_kernel<bf16_t, bf16_t>), g, b, 0, stream, (const bf16_t*)src, lds_, (bf16_t*)dst, ldd, M, cols);
@@ -339,7 +339,7 @@ extern "C" int osuf_copy2d(int src_dtype, const void* src, long lds_, int dst_dt
 }
 
 extern "C" int osuf_add2d(int dtype, const void* a, long lda, const void* b, long ldb, void* dst, long ldd, int M, int cols, hipStream_t stream) {
-  if (M <= 0 || cols <= 0 || cols % 8 || lda % 8 || ldb % 8 || ldd % 8) return OSUF_EINVAL;
+  if (!a || !b || !dst || M <= 0 || cols <= 0 || cols % 8 || lda % 8 || ldb % 8 || ldd % 8 || !al16(a) || !al16(b) || !al16(dst)) return OSUF_EINVAL;
   const long tot = (long)M * (cols / 8);
   if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL(add2d_kernel<bf16_t>, dim3(ew_grid(tot)), dim3(256), 0, stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb, (bf16_t*)dst, ldd, M, cols);
   else if (dtype == OSUF_DT_F32) hipLaunchKernelGGL(add2d_kernel<float>, dim3(ew_grid(tot)), dim3(256), 0, stream, (const float*)a, lda, (const float*)b, ldb, (float*)dst, ldd, M, cols);
@@ -349,7 +349,7 @@ extern "C" int osuf_add2d(int dtype, const void* a, long lda, const void* b, lon
 
 extern "C" int osuf_mse(const float* pred, const float* target, const int* orig_len, float* grad, double* loss_sum, int B, int Dch, int L,
                         hipStream_t stream) {
-  if (B <= 0 || Dch <= 0 || L <= 0) return OSUF_EINVAL;
+  if (!pred || !target || !loss_sum || B <= 0 || Dch <= 0 || L <= 0) return OSUF_EINVAL;
   const long tot = (long)B * Dch * L;
   hipLaunchKernelGGL(mse_kernel<false>, dim3(ew_grid(tot)), dim3(256), 0, stream, pred, target, orig_len, nullptr, grad, loss_sum, Dch, L, tot);
   return osuf_launch_status();
@@ -357,14 +357,14 @@ extern "C" int osuf_mse(const float* pred, const float* target, const int* orig_
 
 extern "C" int osuf_mse_w(const float* pred, const float* target, const int* orig_len, const float* w, float* grad, double* loss_sum, int B,
                           int Dch, int L, hipStream_t stream) {
-  if (B <= 0 || Dch <= 0 || L <= 0 || !w) return OSUF_EINVAL;
+  if (!pred || !target || !loss_sum || B <= 0 || Dch <= 0 || L <= 0 || !w) return OSUF_EINVAL;
   const long tot = (long)B * Dch * L;
   hipLaunchKernelGGL(mse_kernel<true>, dim3(ew_grid(tot)), dim3(256), 0, stream, pred, target, orig_len, w, grad, loss_sum, Dch, L, tot);
   return osuf_launch_status();
 }
 
 extern "C" int osuf_sqnorm(const float* g, long n, double* out, hipStream_t stream) {
-  if (n <= 0 || !al16(g)) return OSUF_EINVAL;
+  if (!g || !out || n <= 0 || !al16(g)) return OSUF_EINVAL;
   hipLaunchKernelGGL(sqnorm_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, stream, g, n, out);
   return osuf_launch_status();
 }
@@ -460,6 +460,7 @@ extern "C" int osuf_lincomb(const float* const* src, const double* w, int K, dou
 }
 
 extern "C" int osuf_clip_coef(const double* sumsq, float max_norm, float base, float* coef, float* total_norm, hipStream_t stream) {
+  if (!sumsq || !coef) return OSUF_EINVAL;
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, stream, sumsq, max_norm, base, coef, total_norm);
   return osuf_launch_status();
 }

@@ -483,7 +483,7 @@ def layout(c):
     x = c.inp(rnd("x", (B, C, L)))
     for dt in (torch.float32, torch.bfloat16):
         r = ops.ncl_to_rows(x, dt, 80)
-        c.eq(f"rows_{dt}", r[..., :C])                                     # columns C..80 are the caller's padding: not defined
+        c.eq(f"rows_{dt}", r)                                              # all 80 columns: C..80 are zeroed by the kernel (the stem GEMM's K padding)
         c.eq(f"ncl_{dt}", ops.rows_to_ncl(r, C))
         c.eq(f"im2col_{dt}", ops.ncl_to_rows(x, dt, 3 * C, kt=3))
         rr = ops.cast_rows(r[..., :C], torch.bfloat16 if dt == torch.float32 else torch.float32)
