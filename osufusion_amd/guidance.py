@@ -76,7 +76,7 @@ def flow_log_snr(t: float) -> float:
 
 
 def midpoint_eval_times(times: Sequence[float]) -> List[float]:
-    """The evaluation times of models/rectified_flow.midpoint_loop over the grid `times`, in call order: t0 and t0 + dt / 2 per interval."""
+    """The evaluation times of ode.midpoint_loop over the grid `times`, in call order: t0 and t0 + dt / 2 per interval."""
     out: List[float] = []
     for t0, t1 in zip(times[:-1], times[1:]):
         out += [t0, t0 + 0.5 * (t1 - t0)]

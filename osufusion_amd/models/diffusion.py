@@ -4,20 +4,18 @@
 The DDIM arithmetic of diffusers==0.29.2's ``DDIMScheduler`` (absent from this image) is restated in ``DDIMSchedule``
 (linear betas 1e-4..0.02, 1000 train steps, "leading" spacing, eta=0, epsilon prediction, clip_sample=True,
 set_alpha_to_one=True) and executed by the osuf_axpby_rows / osuf_ddim_step kernels.
+
+``_DDIM`` is the objective, written once for both backbone families (models/base.py): ``forward`` / ``loss_with`` and the description of the
+DDIM sampler that base._OsuFusion._run loops over.  ``OsuFusion`` is that objective on the UNet family; its sampler is _run over the UNet's
+denoiser closure, and ``use_hip_graph`` wraps the pass of that loop in a captured hipGraph (``_graph_pass``).
 """
 from typing import Optional, Tuple
 
 import torch
-import torch.nn as nn
-import torch.nn.functional as F  # noqa: N812
 
-from .. import inpaint, ops
+from .. import guidance, inpaint, ops
 from .. import runtime as rt
-from ..modules.unet import UNet
-
-TOTAL_DIM = 6        # library/osu/data/encode.py:10-26
-AUDIO_DIM = 96       # scripts/dataset_creator.py:22-24
-CONTEXT_DIM = 5      # scripts/dataset_creator.py:25
+from .base import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, _Steps, _UNetOsuFusion  # noqa: F401  (the dims are imported from here)
 
 
 class DDIMSchedule:
@@ -75,121 +73,25 @@ class _MSEFn(torch.autograd.Function):
         return grad * (g / count.float()), None, None, None      # (a trailing None for an omitted weight is dropped by autograd)
 
 
-class OsuFusion(nn.Module):
-    def __init__(self, dim_h: int, dim_h_mult: Tuple[int] = (1, 2, 3, 4), num_layer_blocks: Tuple[int] = (3, 3, 3, 3),
-                 num_middle_transformers: int = 3, cross_embed_kernel_sizes: Tuple[int] = (3, 7, 15), attn_dim_head: int = 64,
-                 attn_heads: int = 16, attn_kv_heads: int = 1, attn_context_len: int = 4096, cond_drop_prob: float = 0.5,
-                 train_timesteps: int = 1000, sampling_timesteps: int = 35) -> None:
-        super().__init__()
-        self.unet = UNet(dim_in_x=TOTAL_DIM, dim_in_a=AUDIO_DIM, dim_in_c=CONTEXT_DIM, dim_h=dim_h, dim_h_mult=dim_h_mult,
-                         num_layer_blocks=num_layer_blocks, num_middle_transformers=num_middle_transformers,
-                         cross_embed_kernel_sizes=cross_embed_kernel_sizes, attn_dim_head=attn_dim_head, attn_heads=attn_heads,
-                         attn_kv_heads=attn_kv_heads, attn_context_len=attn_context_len)
+class _DDIM:
+    """The discrete DDIM objective of a base._OsuFusion family: the training loss and the sampler's description."""
+
+    def _init_ddim(self, train_timesteps: int, sampling_timesteps: int) -> None:
         self.scheduler = DDIMSchedule(num_train_timesteps=train_timesteps)
         self.train_timesteps = train_timesteps
         self.sampling_timesteps = sampling_timesteps
-        self.cond_drop_prob = cond_drop_prob
-        self._full_bf16 = False
-        self.use_hip_graph = False       # capture one DDIM step (2B-batched CFG forward + fused step kernel) in a hipGraph
-        # GroupNorm statistics / GlobalContext pooling by fixed-order reductions while sampling: the same (a, c, x) gives the same
-        # beatmap bit for bit, eager or graph-replayed (costs one extra read of each conv output; False = the training kernels)
-        self.reproducible_sampling = True
         self.stop_after: Optional[int] = None
 
-    def set_full_bf16(self) -> None:
-        """diffusion.py:56-57 casts the UNet weights to bf16; here the fp32 masters are kept and every kernel computes in
-        bf16 (bf16 MFMA operands and activations) -- the same arithmetic, without losing the master weights."""
-        self._full_bf16 = True
-
-    def _dtype_ctx(self):
-        return rt.forced_compute_dtype(torch.bfloat16 if self._full_bf16 else None)
-
-    @torch.inference_mode()
-    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0) -> torch.Tensor:
-        """diffusion.py:59-77.  Same outputs, restructured: the audio code is computed once (it does not depend on t or x),
-        the conditional and null branches of classifier-free guidance run as one batch of 2B, and the guidance combine is
-        fused into the DDIM-step kernel.  (Attribute `stop_after`, None by default and absent from the reference: return the
-        iterate after that many of the sampling_timesteps steps -- lets tests check single steps of a long schedule.)  The signature is
-        the reference's (tests/test_host_logic.py holds it there); masked generation is `sample_masked`."""
-        with ops.reproducible_mode(self.reproducible_sampling):
-            return self._sample(a, c, x, cond_scale, self.stop_after)
-
-    @torch.inference_mode()
-    def sample_masked(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
-                      known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """sample() with the keywords the transformer models' sample() takes (the reference's signature of sample() is kept as it is).
-        known (B, 6, n) and known_mask ((n,), (B, n) or (B, 1, n); 1 / True = keep), both or neither: masked generation by replacement
-        conditioning (osufusion_amd/inpaint.py).  The iterate handed to the UNet has its known region at its own level: one
-        ops.inpaint_blend of the start iterate at columns (1, 0) of the first coefficient row, one after every step at columns (2, 3) of the
-        step's row, and after the final step of a full run the exact blend, so that the result holds `known` bit for bit where the mask is
-        1.  The noise is one fixed tensor, a clone of the start iterate: nothing new is drawn.  Under use_hip_graph the blend is launched
-        eagerly after each replay.  With both None: no extra launch, the bits of the unmasked sampler."""
-        masked = inpaint.check_pair(known, known_mask)
-        with ops.reproducible_mode(self.reproducible_sampling):
-            return self._sample(a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None)
-
-    def _sample(self, a, c, x, cond_scale, stop_after, keep_region=None):
-        (b, _, n), device = a.shape, a.device
-        rt.require_gpu(a)
-        if x is None:
-            x = torch.randn((b, TOTAL_DIM, n), device=device)
-        x = x.float().contiguous()
-        unet = self.unet
+    def _ddim(self, b, cfg, cond_scale, device) -> _Steps:
         self.scheduler.set_timesteps(self.sampling_timesteps)
-        depth = len(unet.down_layers)
-        pad_len = (2 ** depth - (n % (2 ** depth))) % (2 ** depth)
-        cfg = cond_scale != 1.0
-        with self._dtype_ctx():
-            dtype = rt.compute_dtype(unet.final_conv.weight.dtype)
-            a_rows = unet.encode_audio(a, pad_len, dtype)
-            keep = torch.ones(b, dtype=torch.bool, device=device)
-            if cfg:
-                a_rows = torch.cat([a_rows, a_rows], 0)
-                ce = unet.embed_cond(torch.cat([c, c], 0), torch.cat([keep, ~keep], 0))
-            else:
-                ce = unet.embed_cond(c, keep)
-            steps = self.scheduler.timesteps.tolist()
-            ratio = self.scheduler.num_train_timesteps // self.scheduler.num_inference_steps
-            if stop_after is not None:
-                steps = steps[:stop_after]
-            nb = 2 * b if cfg else b
-            coef_table = torch.tensor([[self.scheduler.step_coefficients(t)] * b for t in steps], dtype=torch.float32, device=device)
-            t_table = torch.tensor([[t] * nb for t in steps], dtype=torch.int64, device=device)
-            x_buf, t_buf, coef_buf = x.clone(), t_table[0].clone(), coef_table[0].clone()
-            total = self.sampling_timesteps
-            blender = inpaint.Blender(*keep_region, x_buf, fresh=False) if keep_region is not None else None
-            if blender is not None and len(steps) > 0:
-                blender.level(x_buf, coef_table[0], 1, 0, out=x_buf)
+        steps = self.scheduler.timesteps.tolist()
+        coef = torch.tensor([[self.scheduler.step_coefficients(t)] * b for t in steps], dtype=torch.float32, device=device)
+        t_in = torch.tensor([[t] * (2 * b if cfg else b) for t in steps], dtype=torch.int64, device=device)
 
-            def one_step() -> None:                      # reads x_buf / t_buf / coef_buf, writes x_buf (static buffers)
-                xin = torch.cat([x_buf, x_buf], 0) if cfg else x_buf
-                x_rows = unet.init_x.forward_rows(F.pad(xin, (0, pad_len), value=-1.0), dtype)
-                pred = unet.denoise_rows(x_rows, a_rows, unet.embed_time(t_buf), ce)[:, :, :n].contiguous()
-                x_buf.copy_(ops.ddim_step(x_buf, pred[:b], pred[b:] if cfg else None, cond_scale, coef_buf))
-
-            graph = None
-            for i in range(len(steps)):
-                if i > 0:
-                    t_buf.copy_(t_table[i])
-                    coef_buf.copy_(coef_table[i])
-                if graph is not None:
-                    graph.replay()
-                else:
-                    one_step()                           # eager (also warms pack caches / RoPE tables before a capture)
-                    if self.use_hip_graph and i == 0 and len(steps) > 1:
-                        torch.cuda.synchronize()
-                        graph = torch.cuda.CUDAGraph()
-                        keep_x = x_buf.clone()
-                        with torch.cuda.graph(graph):    # capture records the launches only; x_buf is restored below
-                            one_step()
-                        x_buf.copy_(keep_x)
-                if blender is not None:                  # outside the captured step: eager and replay issue the same sequence
-                    if i == total - 1:
-                        blender.exact(x_buf, out=x_buf)
-                    else:
-                        blender.level(x_buf, coef_table[i], 2, 3, out=x_buf)
-            x = x_buf
-        return x
+        def step(i, row, x, cond, null, noise, state):
+            return ops.ddim_step(x, cond, null, cond_scale, row), None
+        return _Steps(coef, t_in, step, draw_steps=0, fresh=False, start_cols=(1, 0), step_cols=(2, 3), last=self.sampling_timesteps - 1,
+                      log_snr=lambda: guidance.ddim_log_snr(self.scheduler.alphas_cumprod, steps))
 
     def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"
@@ -205,3 +107,73 @@ class OsuFusion(nn.Module):
             x_noisy = self.scheduler.add_noise(x, noise, timesteps)
             pred = self.unet(x_noisy, a, timesteps, c, cond_drop_prob=p)
         return _MSEFn.apply(pred, noise.float(), orig_len)
+
+
+class OsuFusion(_DDIM, _UNetOsuFusion):
+    def __init__(self, dim_h: int, dim_h_mult: Tuple[int] = (1, 2, 3, 4), num_layer_blocks: Tuple[int] = (3, 3, 3, 3),
+                 num_middle_transformers: int = 3, cross_embed_kernel_sizes: Tuple[int] = (3, 7, 15), attn_dim_head: int = 64,
+                 attn_heads: int = 16, attn_kv_heads: int = 1, attn_context_len: int = 4096, cond_drop_prob: float = 0.5,
+                 train_timesteps: int = 1000, sampling_timesteps: int = 35) -> None:
+        super().__init__(dim_h, dim_h_mult, num_layer_blocks, num_middle_transformers, cross_embed_kernel_sizes, attn_dim_head, attn_heads,
+                         attn_kv_heads, attn_context_len, cond_drop_prob)
+        self._init_ddim(train_timesteps, sampling_timesteps)
+        self.use_hip_graph = False       # capture one DDIM step (2B-batched CFG forward + fused step kernel) in a hipGraph
+        # GroupNorm statistics / GlobalContext pooling by fixed-order reductions while sampling: the same (a, c, x) gives the same
+        # beatmap bit for bit, eager or graph-replayed (costs one extra read of each conv output; False = the training kernels)
+        self.reproducible_sampling = True
+
+    @torch.inference_mode()
+    def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0) -> torch.Tensor:
+        """diffusion.py:59-77.  Same outputs, restructured: the audio code is computed once (it does not depend on t or x),
+        the conditional and null branches of classifier-free guidance run as one batch of 2B, and the guidance combine is
+        fused into the DDIM-step kernel.  (Attribute `stop_after`, None by default and absent from the reference: return the
+        iterate after that many of the sampling_timesteps steps -- lets tests check single steps of a long schedule.)  The signature is
+        the reference's (tests/test_host_logic.py holds it there); masked generation is `sample_masked`."""
+        with ops.reproducible_mode(self.reproducible_sampling):
+            return self._sample(a, c, x, cond_scale)
+
+    @torch.inference_mode()
+    def sample_masked(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
+                      known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """sample() with the keywords the transformer models' sample() takes (the reference's signature of sample() is kept as it is).
+        known (B, 6, n) and known_mask ((n,), (B, n) or (B, 1, n); 1 / True = keep), both or neither: masked generation by replacement
+        conditioning (osufusion_amd/inpaint.py).  The iterate handed to the UNet has its known region at its own level: one
+        ops.inpaint_blend of the start iterate at columns (1, 0) of the first coefficient row, one after every step at columns (2, 3) of the
+        step's row, and after the final step of a full run the exact blend, so that the result holds `known` bit for bit where the mask is
+        1.  The noise is one fixed tensor, a clone of the start iterate: nothing new is drawn.  Under use_hip_graph the blend is launched
+        eagerly after each replay.  With both None: no extra launch, the bits of the unmasked sampler."""
+        masked = inpaint.check_pair(known, known_mask)
+        with ops.reproducible_mode(self.reproducible_sampling):
+            return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None)
+
+    def _sample(self, a, c, x, cond_scale, keep_region=None):
+        return self._run(self._ddim, a, c, x, cond_scale, self.stop_after, keep_region, wrap=self._graph_pass if self.use_hip_graph else None)
+
+    def _graph_pass(self, one_pass, steps):
+        """use_hip_graph: the pass of _run (the 2B-batched UNet call and ops.ddim_step) replayed from a hipGraph.  Step 0 runs eagerly (it
+        also warms pack caches / RoPE tables); then one synchronise and one capture of the pass and the copy of its result into the static
+        iterate, reading static x / t / coef buffers; the iterate is restored and every later step is a replay after its t and coef rows are
+        copied in.  _run's blends stay outside the graph: eager and replay issue the same sequence."""
+        if steps < 2:
+            return one_pass
+        graph = x_buf = t_buf = coef_buf = None
+
+        def run(i, t, row, x, state):
+            nonlocal graph, x_buf, t_buf, coef_buf
+            if graph is None:
+                x_buf, t_buf, coef_buf = one_pass(i, t, row, x, state)[0], t.clone(), row.clone()
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                keep_x = x_buf.clone()
+                with torch.cuda.graph(graph):            # capture records the launches only; x_buf is restored below
+                    x_buf.copy_(one_pass(i, t_buf, coef_buf, x_buf, None)[0])
+                x_buf.copy_(keep_x)
+                return x_buf, None
+            if x is not x_buf:                           # a blend wrote the iterate to a new tensor
+                x_buf.copy_(x)
+            t_buf.copy_(t)
+            coef_buf.copy_(row)
+            graph.replay()
+            return x_buf, None
+        return run
+

@@ -14,31 +14,32 @@ RePaint resampling on the ancestral sampler, and ``window`` / ``window_stride`` 
 trained context by fused-window denoising (osufusion_amd/windowed.py), one gather and one fuse around a batched backbone call per step,
 and ``guidance_rescale`` / ``guidance_interval``: the CFG rescale (one ops.cfg_rescale before a guided step) and guidance only inside a band
 of log-SNR, the conditional B rows alone outside it (osufusion_amd/guidance.py).
-The three diffusion samplers (discrete DDIM, ancestral, DDIM / 2M solver) share one loop, _TransformerOsuFusion._run; each describes its
-steps to it with a _Steps record.  The flow sampler's loop is osufusion_amd/ode.ode_loop: models/rectified_flow.midpoint_loop by default,
-fixed-grid Euler / RK4 or an adaptive embedded pair by ``method``.
+The three diffusion samplers (discrete DDIM, ancestral, DDIM / 2M solver) share one loop with the UNet's DDIM sampler, base._OsuFusion._run;
+each describes its steps to it with a _Steps record.  The flow sampler's loop is osufusion_amd/ode.ode_loop: ode.midpoint_loop by default,
+fixed-grid Euler / RK4 or an adaptive embedded pair by ``method``.  The DDIM and flow objectives (``forward``, ``loss_with``, the sampler)
+are the UNet models' own, diffusion._DDIM and rectified_flow._Flow; this module adds the transformer family under them --
+``_TransformerOsuFusion``: the backbone, its denoiser closures and the window plan -- and each model's ``sample`` keywords.
 Not here: hipGraph capture of the step, LoRA on these backbones.
 """
-from dataclasses import dataclass
-from typing import Callable, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
-import torch.nn as nn
 
 from .. import ct, guidance, inpaint, ode, ops, windowed
 from .. import runtime as rt
 from ..modules.dit import DiT
 from ..modules.mmdit import MMDiT
 from ..modules.scheduler import GaussianDiffusionContinuousTimes
-from .diffusion import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, DDIMSchedule, _MSEFn
-from .rectified_flow import cosmap
+from .base import AUDIO_DIM, CONTEXT_DIM, TOTAL_DIM, _OsuFusion, _Steps
+from .diffusion import _DDIM, _MSEFn
+from .rectified_flow import _Flow
 
 BACKBONES = {"mmdit": MMDiT, "dit": DiT}
 SAMPLERS = ("ddpm", "ddim", "dpmpp_2m")                      # of ContinuousDiffusionOsuFusionDiT
 
 
-class _TransformerOsuFusion(nn.Module):
-    """What the two variants share: the backbone as `unet`, the compute-dtype switch and the step-independent part of a sample call."""
+class _TransformerOsuFusion(_OsuFusion):
+    """The transformer family: a DiT or MMDiT as `unet` and the step-independent part of a sample call, whole or in windows."""
 
     WINDOW_DOC = """The window keywords of every sample() here: windowed sampling (fused-window denoising, MultiDiffusion), for songs longer than the
     trained context.
@@ -55,7 +56,7 @@ class _TransformerOsuFusion(nn.Module):
         different window_batch values are not promised to be bit-equal: the GEMM dispatch may depend on the row count.
     ValueError: window < 1; a stride outside [1, window]; an unknown taper; window_batch < 1; window, the stride or (when n > window) n not
     a multiple of the patch size; any of the other three given while window is None.
-    Out of scope: the two UNet models (their loop is written inline around the hipGraph capture and has no denoiser closure), hipGraph
+    Out of scope: the two UNet models (the same loops over a closure of the same contract, but not wired to windows yet), hipGraph
     capture of a windowed step, and any claim about map quality (no trained weights were at hand)."""
 
     GUIDANCE_DOC = """The guidance keywords of every sample() here (osufusion_amd/guidance.py).  A denoiser call is guided iff cond_scale != 1 and its
@@ -74,24 +75,15 @@ class _TransformerOsuFusion(nn.Module):
     ValueError: phi outside [0, 1]; an interval that is not a pair; lo > hi; a NaN end.
     Not promised: that a B-row call equals the first B rows of a 2B-row call bit for bit -- the GEMM dispatch may depend on the row count --
     so results across different intervals are comparable to fp noise, not bit for bit.
-    Out of scope: the two UNet models (their loop is written inline around the hipGraph capture), a schedule of cond_scale, and any claim
+    Out of scope: the two UNet models (not wired to these keywords yet: their closure has no unguided call), a schedule of cond_scale, and any claim
     about map quality (no trained weights were at hand)."""
 
     def __init__(self, dim_h: int, backbone: str, cond_drop_prob: float, **backbone_kwargs) -> None:
-        super().__init__()
+        super().__init__(cond_drop_prob)
         if backbone not in BACKBONES:
             raise ValueError(f"backbone must be one of {sorted(BACKBONES)} (got {backbone!r})")
         self.backbone = backbone
         self.unet = BACKBONES[backbone](dim_in_x=TOTAL_DIM, dim_in_a=AUDIO_DIM, dim_in_c=CONTEXT_DIM, dim_h=dim_h, **backbone_kwargs)
-        self.cond_drop_prob = cond_drop_prob
-        self._full_bf16 = False
-
-    def set_full_bf16(self) -> None:
-        """Keeps fp32 master weights; all kernels compute in bf16 (see models/diffusion.py)."""
-        self._full_bf16 = True
-
-    def _dtype_ctx(self):
-        return rt.forced_compute_dtype(torch.bfloat16 if self._full_bf16 else None)
 
     def _denoiser(self, a: torch.Tensor, c: torch.Tensor, cfg: bool):
         """-> f(x (b, 6, n) fp32, t (nb,), guided=cfg) = the prediction (nb, 6, n), nb = 2b with guidance (conditional rows first), else b.
@@ -167,79 +159,12 @@ class _TransformerOsuFusion(nn.Module):
             windowed.check_length(a.shape[-1], wp, p)
         return wp
 
-    def _start(self, a: torch.Tensor, x: Optional[torch.Tensor]) -> torch.Tensor:
-        rt.require_gpu(a)
-        if x is None:
-            x = torch.randn((a.shape[0], TOTAL_DIM, a.shape[-1]), device=a.device)
-        rt.require_gpu(x)
-        return x.float().contiguous()
 
-    def _run(self, describe, a, c, x, cond_scale, stop_after, keep_region=None, wp=None, gd: Optional[guidance.Guidance] = None):
-        """The sampling loop of the diffusion samplers; describe(b, cfg, cond_scale, device) -> the sampler's _Steps.  Draws, in this order:
-        the start iterate (x None), the start blend's noise; then per pass of a step its own noise, its level blend's noise, the resample
-        draw -- each only where the sampler has one.  Per pass: the denoiser, the step, the blend of the known region, the resample.
-        gd (guidance.plan; None: the loop as it was before it): with an interval, which steps are guided is decided here, before the loop,
-        from the sampler's per-step log-SNR -- the one host read; the passes of a step share its decision.  An unguided step calls the
-        denoiser on the conditional b rows and hands (pred, None) to the step; with gd.phi > 0 a guided step hands it
-        (ops.cfg_rescale(cond, null), None)."""
-        x = self._start(a, x)
-        b, device = a.shape[0], a.device
-        cfg = cond_scale != 1.0
-        sp = describe(b, cfg, cond_scale, device)
-        total = sp.coef.shape[0]
-        steps = total if stop_after is None else min(stop_after, total)
-        gd = gd if cfg else None                           # cond_scale == 1: nothing to control
-        guided = guidance.guided_calls(sp.log_snr(), gd, cond_scale) if gd is not None and gd.bounded else None
-        blender = inpaint.Blender(*keep_region, x, fresh=sp.fresh) if keep_region is not None else None
-        if blender is not None and steps > 0:
-            x = blender.level(x, sp.coef[0], *sp.start_cols)
-        state = None
-        with self._dtype_ctx():
-            f = self._make_denoiser(a, c, cfg, wp)
-            for i in range(steps):
-                passes = sp.resample if i < sp.last else 1
-                for u in range(passes):
-                    if guided is not None and not guided[i]:
-                        cond, null = f(x, sp.t_in[i], False), None
-                    else:
-                        pred = f(x, sp.t_in[i])
-                        cond, null = pred[:b], pred[b:] if cfg else None
-                        if gd is not None and gd.phi > 0.0:
-                            cond, null = ops.cfg_rescale(cond, null, cond_scale, gd.phi)[0], None
-                    noise = torch.randn(x.shape, device=device) if i < sp.draw_steps else None
-                    x, state = sp.step(i, x, cond, null, noise, state)
-                    if blender is not None:
-                        x = blender.exact(x) if i == sp.last else blender.level(x, sp.coef[i], *sp.step_cols)
-                    if u < passes - 1:
-                        x = ops.axpby_rows(x, torch.randn(x.shape, device=device), sp.k_r[i], sp.k_g[i])
-        return x
-
-
-@dataclass
-class _Steps:
-    """What a sampler tells _TransformerOsuFusion._run.  S = the steps of a full run."""
-    coef: torch.Tensor                  # (S, b, cols): step i's coefficient rows, also the levels of the blends
-    t_in: torch.Tensor                  # (S, nb): step i's time input of the denoiser
-    step: Callable                      # step(i, x, cond, null, noise, state) -> (x, state); state is None on the first call
-    draw_steps: int                     # steps i < draw_steps draw a torch.randn of the iterate's shape for `noise`, the others get None
-    fresh: bool                         # the level blends draw fresh noise (else: one fixed tensor, a clone of the start iterate)
-    start_cols: Tuple[int, int]         # columns (a, s) of coef[0] for the level blend of the start iterate
-    step_cols: Tuple[int, int]          # columns (a, s) of coef[i] for the level blend after step i
-    last: int                           # the step that ends a full run: the exact blend instead of a level blend, and no resampling
-    resample: int = 1                   # the ancestral sampler's RePaint passes per step, with the factors of the way back one level:
-    k_r: Optional[torch.Tensor] = None  # (S, b) x = k_r x + k_g z
-    k_g: Optional[torch.Tensor] = None
-    log_snr: Optional[Callable] = None  # log_snr() -> S host floats, step i's log-SNR for a guidance interval; called at most once per run
-
-
-class DiffusionOsuFusionDiT(_TransformerOsuFusion):
+class DiffusionOsuFusionDiT(_DDIM, _TransformerOsuFusion):
     def __init__(self, dim_h: int, backbone: str = "mmdit", cond_drop_prob: float = 0.5, train_timesteps: int = 1000,
                  sampling_timesteps: int = 35, **backbone_kwargs) -> None:
         super().__init__(dim_h, backbone, cond_drop_prob, **backbone_kwargs)
-        self.scheduler = DDIMSchedule(num_train_timesteps=train_timesteps)
-        self.train_timesteps = train_timesteps
-        self.sampling_timesteps = sampling_timesteps
-        self.stop_after: Optional[int] = None
+        self._init_ddim(train_timesteps, sampling_timesteps)
 
     @torch.inference_mode()
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 7.0,
@@ -264,32 +189,6 @@ class DiffusionOsuFusionDiT(_TransformerOsuFusion):
         gd = guidance.plan(guidance_rescale, guidance_interval)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
             return self._run(self._ddim, a, c, x, cond_scale, self.stop_after, (known, known_mask) if masked else None, wp, gd)
-
-    def _ddim(self, b, cfg, cond_scale, device) -> _Steps:
-        self.scheduler.set_timesteps(self.sampling_timesteps)
-        steps = self.scheduler.timesteps.tolist()
-        coef = torch.tensor([[self.scheduler.step_coefficients(t)] * b for t in steps], dtype=torch.float32, device=device)
-        t_in = torch.tensor([[t] * (2 * b if cfg else b) for t in steps], dtype=torch.int64, device=device)
-
-        def step(i, x, cond, null, noise, state):
-            return ops.ddim_step(x, cond, null, cond_scale, coef[i]), None
-        return _Steps(coef, t_in, step, draw_steps=0, fresh=False, start_cols=(1, 0), step_cols=(2, 3), last=self.sampling_timesteps - 1,
-                      log_snr=lambda: guidance.ddim_log_snr(self.scheduler.alphas_cumprod, steps))
-
-    def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
-        assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"
-        rt.require_gpu(x)
-        noise = torch.randn_like(x, device=x.device)
-        timesteps = torch.randint(0, self.scheduler.num_train_timesteps, (x.shape[0],), dtype=torch.int64, device=x.device)
-        return self.loss_with(x, a, c, noise, timesteps, orig_len)
-
-    def loss_with(self, x, a, c, noise, timesteps, orig_len=None, cond_drop_prob: Optional[float] = None) -> torch.Tensor:
-        """forward() with the RNG draws passed in (parity tests, benchmarks)."""
-        p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
-        with self._dtype_ctx():
-            x_noisy = self.scheduler.add_noise(x, noise, timesteps)
-            pred = self.unet(x_noisy, a, timesteps, c, cond_drop_prob=p)
-        return _MSEFn.apply(pred, noise.float(), orig_len)
 
 
 class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
@@ -397,9 +296,9 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         log_snr = grid[:-1, None].repeat(1, 2 * b if cfg else b)
         draws = self.sampler == "ddim" and self.ddim_eta > 0.0
 
-        def step(i, x, cond, null, noise, x0_prev):        # the state: the clamped start prediction, the next 2M step's x0_prev
-            s = self._threshold(x, cond, null, cond_scale, coef[i])
-            return ops.ct_solver_step(x, cond, null, cond_scale, coef[i], fac[i], x0_prev, noise, self.pred_objective, s)
+        def step(i, row, x, cond, null, noise, x0_prev):   # the state: the clamped start prediction, the next 2M step's x0_prev
+            s = self._threshold(x, cond, null, cond_scale, row)
+            return ops.ct_solver_step(x, cond, null, cond_scale, row, fac[i], x0_prev, noise, self.pred_objective, s)
         return _Steps(coef, log_snr, step, draw_steps=total if draws else 0, fresh=draws, start_cols=(ct.ALPHA, ct.SIGMA),
                       step_cols=(ct.ALPHA_NEXT, ct.SIGMA_NEXT), last=total - 1, log_snr=lambda: grid[:-1].tolist())
 
@@ -414,11 +313,11 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
             k_r = (coef[:, :, ct.ALPHA] / coef[:, :, ct.ALPHA_NEXT]).contiguous()
             k_g = (coef[:, :, ct.SIGMA] * torch.sqrt(coef[:, :, ct.C])).contiguous()
 
-        def step(i, x, cond, null, noise, state):
+        def step(i, row, x, cond, null, noise, state):
             if plain:
-                return ops.ct_step(x, cond, null, cond_scale, coef[i], noise), None
-            s = self._threshold(x, cond, null, cond_scale, coef[i])
-            return ops.ct_step_ex(x, cond, null, cond_scale, coef[i], noise, self.pred_objective, s), None
+                return ops.ct_step(x, cond, null, cond_scale, row, noise), None
+            s = self._threshold(x, cond, null, cond_scale, row)
+            return ops.ct_step_ex(x, cond, null, cond_scale, row, noise, self.pred_objective, s), None
         return _Steps(coef, log_snr, step, draw_steps=total - 1, fresh=True, start_cols=(ct.ALPHA, ct.SIGMA),
                       step_cols=(ct.ALPHA_NEXT, ct.SIGMA_NEXT), last=total - 1, resample=resample, k_r=k_r, k_g=k_g,
                       log_snr=lambda: coef[:, 0, ct.LOG_SNR].tolist())
@@ -448,12 +347,11 @@ class ContinuousDiffusionOsuFusionDiT(_TransformerOsuFusion):
         return _MSEFn.apply(pred, target, orig_len, weight.float().contiguous())
 
 
-class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
+class RectifiedFlowOsuFusionDiT(_Flow, _TransformerOsuFusion):
     def __init__(self, dim_h: int, backbone: str = "mmdit", cond_drop_prob: float = 0.5, sampling_timesteps: int = 16,
                  **backbone_kwargs) -> None:
         super().__init__(dim_h, backbone, cond_drop_prob, **backbone_kwargs)
         self.sample_timesteps = sampling_timesteps
-        self.last_ode_stats = None
 
     @torch.inference_mode()
     def sample(self, a: torch.Tensor, c: torch.Tensor, x: Optional[torch.Tensor] = None, cond_scale: float = 2.0,
@@ -485,46 +383,3 @@ class RectifiedFlowOsuFusionDiT(_TransformerOsuFusion):
         ode.check_options(**solver)
         with ops.reproducible_mode(True), ops.one_launch_attention(True):
             return self._sample(a, c, x, cond_scale, (known, known_mask) if masked else None, wp, gd, solver)
-
-    def _sample(self, a, c, x, cond_scale, keep_region=None, wp=None, gd: Optional[guidance.Guidance] = None, solver: Optional[dict] = None):
-        x = self._start(a, x)
-        b, device = a.shape[0], a.device
-        cfg = cond_scale != 1.0
-        gd = gd if cfg else None                           # cond_scale == 1: nothing to control
-        ones = torch.ones(b, dtype=torch.float32, device=device)
-        with self._dtype_ctx():
-            den = self._make_denoiser(a, c, cfg, wp)
-
-            def f(t: float, y: torch.Tensor) -> torch.Tensor:
-                tt = torch.full((2 * b if cfg else b,), t, dtype=torch.float32, device=device)
-                if gd is not None and gd.bounded and not gd.contains(guidance.flow_log_snr(t)):
-                    return den(y, tt, False)               # outside the interval: the conditional b rows are the flow
-                out = den(y, tt)
-                if gd is not None and gd.phi > 0.0:
-                    out = ops.cfg_rescale(out[:b], out[b:], cond_scale, gd.phi)[0]
-                elif cfg:                                  # null + (cond - null) * s  ==  (1 - s) * null + s * cond
-                    out = ops.axpby_rows(out[b:].contiguous(), out[:b].contiguous(), ones * (1.0 - cond_scale), ones * cond_scale)
-                return out
-
-            times = torch.linspace(0.0, 1.0, self.sample_timesteps).tolist()
-            x, self.last_ode_stats = ode.ode_loop(f, x, times, ones, keep_region=keep_region, **(solver or {}))
-        return x
-
-    def forward(self, x: torch.Tensor, a: torch.Tensor, c: torch.Tensor, orig_len: Optional[torch.Tensor] = None) -> torch.Tensor:
-        assert x.shape[-1] == a.shape[-1], "x and a must have the same number of sequence length"
-        rt.require_gpu(x)
-        noise = torch.randn_like(x, device=x.device)
-        times = torch.rand(x.shape[0], device=x.device)
-        return self.loss_with(x, a, c, noise, times, orig_len)
-
-    def loss_with(self, x, a, c, noise, times, orig_len=None, cond_drop_prob: Optional[float] = None) -> torch.Tensor:
-        """forward() with the RNG draws passed in (parity tests, benchmarks)."""
-        p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
-        x, noise = x.float().contiguous(), noise.float().contiguous()
-        t = cosmap(times.float())
-        ones = torch.ones_like(t)
-        with self._dtype_ctx():
-            x_noisy = ops.axpby_rows(x, noise, t.contiguous(), (1 - t).contiguous())
-            flow = ops.axpby_rows(x, noise, ones, -ones)
-            pred = self.unet(x_noisy, a, times.float(), c, cond_drop_prob=p)
-        return _MSEFn.apply(pred, flow, orig_len)

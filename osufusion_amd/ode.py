@@ -167,13 +167,46 @@ def _combine(y: torch.Tensor, ks: List[torch.Tensor], weights: Sequence[float], 
 
 
 def _levels(ts: Sequence[float], b: int, device) -> torch.Tensor:
-    """(len(ts), b, 2) fp32 = (t, 1 - t) per sample: the levels a masked loop blends at (models/rectified_flow.flow_levels' layout)."""
+    """(len(ts), b, 2) fp32 = (t, 1 - t) per sample: the levels a masked loop blends at; t and 1 - t are python floats rounded to fp32."""
     return torch.tensor([[[t, 1.0 - t]] * b for t in ts], dtype=torch.float32, device=device)
+
+
+def flow_levels(times, b: int, device) -> torch.Tensor:
+    """The levels a masked midpoint loop over `times` blends at, (1 + 2 (S - 1), b, 2): row 0 the start (times[0]), then per interval its
+    midpoint t0 + dt / 2 and its end t1.  Built once per call."""
+    ts = [times[0]]
+    for t0, t1 in zip(times[:-1], times[1:]):
+        ts += [t0 + 0.5 * (t1 - t0), t1]
+    return _levels(ts, b, device)
+
+
+def midpoint_loop(f, x: torch.Tensor, times, ones: torch.Tensor, keep_region=None) -> torch.Tensor:
+    """The reference's sampler, torchdiffeq==0.2.4's fixed-grid ``odeint(..., method="midpoint")`` restated: per interval of `times`
+    ``k1 = f(t0, y); k2 = f(t0 + dt/2, y + dt/2 * k1); y += dt * k2``, each update one ops.axpby_rows (its own rounding, which is why this is
+    not fixed_grid_loop over the midpoint tableau: ops.lincomb rounds differently).  keep_region = (known, known_mask): every state
+    handed to f is blended at its own time, the end of the last interval exactly; None issues the unmasked loop's launches and nothing else."""
+    blender = None
+    if keep_region is not None:
+        blender = inpaint.Blender(*keep_region, x, fresh=False)
+        levels = flow_levels(times, x.shape[0], x.device)
+        x = blender.level(x, levels[0], 0, 1)
+    last = len(times) - 2
+    for j, (t0, t1) in enumerate(zip(times[:-1], times[1:])):
+        dt = t1 - t0
+        k1 = f(t0, x)
+        mid = ops.axpby_rows(x, k1, ones, ones * (0.5 * dt))
+        if blender is not None:
+            mid = blender.level(mid, levels[1 + 2 * j], 0, 1)
+        k2 = f(t0 + 0.5 * dt, mid)
+        x = ops.axpby_rows(x, k2, ones, ones * dt)
+        if blender is not None:
+            x = blender.exact(x) if j == last else blender.level(x, levels[2 + 2 * j], 0, 1)
+    return x
 
 
 def fixed_grid_loop(f: Callable, x: torch.Tensor, times: Sequence[float], tab: Tableau, keep_region=None) -> torch.Tensor:
     """One step of `tab` per interval of `times`.  keep_region = (known, known_mask): every state handed to f is blended at its own time
-    t0 + c_i dt, the end of an interval at t1 and the end of the last interval exactly, as models/rectified_flow.midpoint_loop does."""
+    t0 + c_i dt, the end of an interval at t1 and the end of the last interval exactly, as midpoint_loop does."""
     co = tab.floats()
     blender = None
     if keep_region is not None:
@@ -230,12 +263,11 @@ def adaptive_loop(f: Callable, x: torch.Tensor, t0: float, t_end: float, tab: Ta
 def ode_loop(f: Callable, x: torch.Tensor, times: Sequence[float], ones: torch.Tensor, method: str = "midpoint", rtol: float = 1e-5,
              atol: float = 1e-5, first_step: Optional[float] = None, max_steps: int = 1000, keep_region=None) -> Tuple[torch.Tensor, dict]:
     """The flow f(t, y) integrated over `times` (the sampler's linspace(0, 1, S)) -> (the state at times[-1], stats).  stats: evals (calls
-    of f), accepted, rejected, times (the ends of the accepted steps).  "midpoint" is models/rectified_flow.midpoint_loop itself, launches and
+    of f), accepted, rejected, times (the ends of the accepted steps).  "midpoint" is midpoint_loop itself, launches and
     bits unchanged; "euler" and "rk4" step once per interval of the grid and ignore the tolerances, as torchdiffeq's fixed-grid solvers do;
     "bosh3" and "dopri5" choose their own steps from rtol / atol, starting at first_step (None: the grid's first interval) and ending
     exactly at times[-1].  keep_region with an adaptive method: ValueError (see the module docstring).  RuntimeError after max_steps
     attempted steps."""
-    from .models.rectified_flow import midpoint_loop
     tab = check_options(method, rtol, atol, first_step, max_steps)
     if tab.adaptive and keep_region is not None:
         raise ValueError(f"method={method!r} does not take known / known_mask: a blend between steps invalidates the reused stage and the "

@@ -3,7 +3,8 @@ iterate is cut into overlapping windows of the trained length (osuf_window_gathe
 the window predictions are fused back into one full-length prediction by a tapered, normalised overlap-add (osuf_window_fuse, both in
 csrc/sampling.hip; reached as ops.window_gather / ops.window_fuse).  The step kernels then work on the full-length tensors as they do
 without windows.  The window layout, the taper, the allocating wrappers and the argument rules of every sample() live here, as
-inpaint.py's do; the closure the sampling loops call is _TransformerOsuFusion._windowed_denoiser (models/transformer_diffusion.py).  The
+inpaint.py's do; the closure the sampling loops (models/base._OsuFusion._run, ode.ode_loop) call is
+_TransformerOsuFusion._windowed_denoiser (models/transformer_diffusion.py); the UNet family has no windowed closure yet.  The
 guarded-memory cases are in tests/test_windowed_gpu.py."""
 from __future__ import annotations
 

@@ -2,7 +2,8 @@
 guidance on (cond_scale 2.0), full UNet dim_h=256, bf16; eager vs hipGraph-captured step.
     python tools/bench_sampler.py [--batch 16 --length 8192 --steps 50]"""
 import argparse, json, sys, time
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch
 from osufusion_amd.models.diffusion import OsuFusion
 
