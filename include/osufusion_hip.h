@@ -570,6 +570,30 @@ int osuf_frame_rows(const float* in, long n_in, int hop, int K, float* out, long
 int osuf_resample(const float* x_pad, long n_pad, const float* table, int L, int M, int T, long base0, float* y, long n_out,
                   hipStream_t stream);
 
+/* ---- .osu hit objects -> training signals (encode.hip)    replaces: the per-frame Python loops of osu_fusion/library/osu/data/hit.py
+ *      (flips, extents), cursor.py (cursor_signal) and encode.py (encode_beatmap), library/augment.py's two cursor flips and the x padding
+ *      of trainer.py's collate_fn.  One thread per (sample, frame), one launch per batch, no atomics, no LDS.
+ *      out: fp32 contiguous (B, 6, L): HIT, SUSTAIN, SLIDER, COMBO, CURSOR_X, CURSOR_Y in [-1, 1].  Row b, frame l < len[b], is global frame
+ *      g = start[b] + l of map map_idx[b], at (double)g * 176 / 22050 * 1000 ms (evaluated in that order); frames l >= len[b], and every
+ *      frame of a row whose map_idx is outside [0, n_maps), hold -1.0f in all six channels.  flip (NULL: none): bit 0 changes the sign of
+ *      the stored CURSOR_X, bit 1 of CURSOR_Y.  round_pos: 1 = slider positions rounded half-to-even to whole pixels as the reference does,
+ *      0 = left unrounded (measurement only).  pos_px (NULL: not wanted): fp64 (B, 2, L), the cursor in osu!pixels before the division and
+ *      the rounding to fp32 (0 in padding) -- what tests/test_encode_gpu.py measures the kernel's geometry with.  All selects and geometry in fp64, contraction off, one rounding to fp32 after * 2 - 1.
+ *      Tables (osufusion_amd/encode.py BeatmapTable builds them; every offset is global over the N maps; none may be empty: pad with one
+ *      unused entry):
+ *        map_hdr int [n_maps][8]    {n_obj, obj_off, n_sus, sus_off, n_sld, sld_off, 0, 0}
+ *        obj_f   double [objs][16]  {t, end_time, rounded start_x, start_y, end_x, end_y, unrounded start_x, start_y, end_x, end_y,
+ *                                    slide_duration, g0 .. g4}; Line g = {ax, ay, bx, by}, Perfect g = {cx, cy, r, theta0, theta1}
+ *        obj_i   int [objs][4]      {kind: 0 circle 1 spinner 2 line 3 perfect 4 bezier, new-combo objects of the map up to and including
+ *                                    this one, seg_off, n_seg}; objects sorted by t within a map
+ *        ivl     double [..][2]     disjoint sorted [s, e) intervals: a map's SUSTAIN list at sus_off, its SLIDER list at sld_off
+ *        seg_cum double [segs]      cum_t of the segments of a Bezier slider (ascending, last 1.0); seg_i int [segs][2] {node_off, degree};
+ *        nodes   double [..][2]     control points.
+ *      OSUF_EINVAL: a null pointer other than flip and pos_px, n_maps, B or L <= 0, B > 65535. ---- */
+int osuf_encode_signals(const int* map_hdr, int n_maps, const double* obj_f, const int* obj_i, const double* ivl, const double* seg_cum,
+                        const int* seg_i, const double* nodes, const int* map_idx, const long* start, const int* len, const int* flip,
+                        int round_pos, float* out, double* pos_px, int B, int L, hipStream_t stream);
+
 /* ---- DiT row kernels (dit.hip)    replaces: osu_fusion/modules/dit.py:14-15 modulate(LayerNorm(x)), 275-277 the audio statistics
  *      pooling (63-70 MultiHeadRMSNorm: osuf_joint_qknorm_fwd / _bwd below, one stream and G = H).  Rows [M][C], M = B * L, sample of row m = m / L; C % 8 == 0, C <= 2048; row strides multiples of 8
  *      elements, 16-B aligned pointers.  No atomics: every cross-row sum goes through per-workgroup partials added in a fixed order.
