@@ -7,11 +7,11 @@
  *
  * Conventions
  *   - plain device pointers + sizes + hipStream_t; no allocation, no host sync, graph-capturable.  Nothing is kept between
- *     calls except the one-time hipFuncSetAttribute registration of kernels that need > 64 KiB of LDS.  Kernel variants are
- *     chosen per call (`variant` arguments).  A few environment switches force one path so that tests can compare it bit for
- *     bit with another and A/B runs can time it: OSUF_GEMM_BIG_MIN_TILES, OSUF_GEMM_NO8P, OSUF_GEMM_NOHALO and
- *     OSUF_WGRAD_F32_PARTIALS in the GEMM launchers, OSUF_ATTN_FWD_NOWHOLE and OSUF_ATTN_FWD_NOQSK in the attention forward.
- *     They are test and A/B aids, not configuration, and are read on every call (never cached);
+ *     calls except two things: the one-time hipFuncSetAttribute registration of kernels that need > 64 KiB of LDS, and the
+ *     per-process override table below (osuf_override_set).  Kernel variants are chosen per call (`variant` arguments); the
+ *     table forces the few launcher branches that have no such argument, so that tests can compare one path bit for bit with
+ *     another and A/B runs can time it.  It is a test and A/B aid, not configuration: every slot starts at its default, the
+ *     launchers read it on every call, and nothing is read from the environment;
  *   - return 0 on success, <0 for an argument error (-1 invalid, -2 unsupported), >0 = hipError_t of the launch;
  *   - activations are channels-last rows [B*L][C] ("rows"), C contiguous, row stride `ld*` in ELEMENTS;
  *   - dtype: 0 = fp32 storage (exact-f32 MFMA), 1 = bf16 storage (bf16 MFMA, fp32 accumulate);
@@ -46,6 +46,23 @@ extern "C" {
                                   /* (4 was a timing-only build of the 512-key sweep, since removed: refused with OSUF_EINVAL) */
 
 int osuf_version(void);
+
+/* ---- the override table (test and A/B aid) ---------------------------------------------------------------
+ * One int per launcher branch that can be forced; OSUF_KNOB_DEFAULT in every slot at load.  The boolean slots are on for a value > 0. */
+enum {
+  OSUF_KNOB_GEMM_BIG_MIN_TILES,   /* osuf_gemm_nt / osuf_gemm_tn / osuf_gemm_tn_workspace_bytes: when the 256 x 256 kernels are picked.  Default: from
+                                     192 tiles and N >= 192 on; 0: never; n > 0: from n tiles on, whatever N (1 forces them, the wgrad plan included) */
+  OSUF_KNOB_GEMM_NO8P,            /* osuf_gemm_nt: the one-barrier-per-K-step 256 x 256 loops instead of the 8-phase ones */
+  OSUF_KNOB_GEMM_NOHALO,          /* osuf_gemm_nt / osuf_gemm_tn: k = 3 convolutions on the plain kernels, not the shared-panel / merged-taps ones */
+  OSUF_KNOB_WGRAD_F32_PARTIALS,   /* osuf_gemm_tn: fp32 partial tiles in the workspace instead of bf16 pairs */
+  OSUF_KNOB_ATTN_FWD_NOWHOLE,     /* attention forward: the bounds-checked kernel also where N % 64 == 0 */
+  OSUF_KNOB_ATTN_FWD_NOQSK,       /* attention forward on pre-scaled queries: osuf_mqa_fwd's kernel at a unit exponent scale, not their own */
+  OSUF_KNOB_COUNT
+};
+#define OSUF_KNOB_DEFAULT (-1)
+/* value: OSUF_KNOB_DEFAULT or >= 0.  An unknown knob or a value below OSUF_KNOB_DEFAULT is OSUF_EINVAL (-1) and changes nothing. */
+int osuf_override_set(int knob, int value);
+int osuf_override_get(int knob, int* value);
 
 /* ---- conv1d / linear as tap-GEMMs (gemm.hip) -------------------------------------------------------------
  * C[m][n] = act( sum_t sum_k A[rowmap(m,t)][k] * W[t][n][k] + bias[n] ) * silu'(U[m][n]) + R[m][n] * rscale[b][n]

@@ -19,6 +19,8 @@ P, L, I, F = c_void_p, c_long, c_int, c_float
 # name -> argtypes (all return int).  Must list every symbol of include/osufusion_hip.h (tests/test_host_logic.py::test_capi_* check).
 SIGNATURES = {
     "osuf_version": [],
+    "osuf_override_set": [I, I],
+    "osuf_override_get": [I, P],
     "osuf_gemm_nt": [I, P, L, P, L, L, P, L, P, L, P, L, P, L, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "osuf_gemm_nt_rowdot": [I, P, L, P, L, P, L, P, L, P, I, I, I, I, I, P],
     "osuf_gemm_tn": [I, P, L, P, L, P, L, L, I, I, I, I, I, I, I, I, I, I, I, I, P, L, P],

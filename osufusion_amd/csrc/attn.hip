@@ -11,7 +11,6 @@
 // (key-stationary: a wave owns 32 keys, dK^T/dV^T stay in registers while it sweeps heads x query blocks).
 #include "common.hpp"
 #include <type_traits>
-#include <stdlib.h>
 
 static constexpr int D = 64;                      // head dim (bytes per tile row = 128)
 static constexpr float kLog2e = 1.4426950408889634f;
@@ -1943,13 +1942,13 @@ static int mqa_fwd_impl(const void* q, long ldq, const void* k, long ldk, const 
     launch_gen_fwd<false, false>(a, head_dim, 1, stream);
     return osuf_launch_status();
   }
-  const bool whole = (N & 63) == 0 && getenv("OSUF_ATTN_FWD_NOWHOLE") == nullptr;
+  const bool whole = (N & 63) == 0 && !osuf_knob_on(OSUF_KNOB_ATTN_FWD_NOWHOLE);
   const dim3 grid((nvb + 7) / 8, B);
   const int lds = 32768 + 8 * 4096;
   if (rope) {
     if (whole) hipLaunchKernelGGL((mqa_fwd_kernel<8, true, true, true>), grid, dim3(512), lds, stream, a);
     else hipLaunchKernelGGL((mqa_fwd_kernel<8, true, false, true>), grid, dim3(512), lds, stream, a);
-  } else if (qs && getenv("OSUF_ATTN_FWD_NOQSK") == nullptr) {
+  } else if (qs && !osuf_knob_on(OSUF_KNOB_ATTN_FWD_NOQSK)) {
     if (whole) hipLaunchKernelGGL((mqa_fwd_kernel<8, true, true>), grid, dim3(512), lds, stream, a);
     else hipLaunchKernelGGL((mqa_fwd_kernel<8, true>), grid, dim3(512), lds, stream, a);
   } else if (whole) hipLaunchKernelGGL((mqa_fwd_kernel<8, false, true>), grid, dim3(512), lds, stream, a);

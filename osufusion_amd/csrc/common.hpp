@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 // descriptor of osuf_pack_weight_group (include/osufusion_hip.h holds the same definition for callers)
 #ifndef OSUF_PACK_DESC_DEFINED
@@ -174,6 +175,16 @@ static inline int osuf_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? OSUF_OK : (int)e;
 }
+
+// The override table (include/osufusion_hip.h: osuf_override_set / osuf_override_get): one slot per launcher branch a test or an A/B
+// run can force.  One definition for every translation unit; the launchers read it on every call.
+enum { OSUF_KNOB_GEMM_BIG_MIN_TILES, OSUF_KNOB_GEMM_NO8P, OSUF_KNOB_GEMM_NOHALO, OSUF_KNOB_WGRAD_F32_PARTIALS, OSUF_KNOB_ATTN_FWD_NOWHOLE,
+       OSUF_KNOB_ATTN_FWD_NOQSK, OSUF_KNOB_COUNT };
+#define OSUF_KNOB_DEFAULT (-1)
+inline std::atomic<int> osuf_knobs[OSUF_KNOB_COUNT] = {{OSUF_KNOB_DEFAULT}, {OSUF_KNOB_DEFAULT}, {OSUF_KNOB_DEFAULT},
+                                                       {OSUF_KNOB_DEFAULT}, {OSUF_KNOB_DEFAULT}, {OSUF_KNOB_DEFAULT}};
+static inline int osuf_knob(int k) { return osuf_knobs[k].load(std::memory_order_relaxed); }
+static inline bool osuf_knob_on(int k) { return osuf_knob(k) > 0; }                     // the five boolean slots
 
 // host side of the entry points: `using T` by dtype code around a launch (unknown code: OSUF_EUNSUPPORTED), the grid of a grid-stride
 // elementwise kernel, 16-byte pointer alignment, and the channel widths the 8-channel-chunk kernels serve

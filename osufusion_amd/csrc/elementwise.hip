@@ -864,3 +864,15 @@ extern "C" int osuf_clock_probe(int blocks, int iters, int mode, long* out, hipS
 }
 
 extern "C" int osuf_version(void) { return 1; }
+
+// the override table of common.hpp: OSUF_KNOB_DEFAULT (-1) or a value >= 0; anything else, and an unknown slot, is refused
+extern "C" int osuf_override_set(int knob, int value) {
+  if (knob < 0 || knob >= OSUF_KNOB_COUNT || value < OSUF_KNOB_DEFAULT) return OSUF_EINVAL;
+  osuf_knobs[knob].store(value, std::memory_order_relaxed);
+  return OSUF_OK;
+}
+extern "C" int osuf_override_get(int knob, int* value) {
+  if (knob < 0 || knob >= OSUF_KNOB_COUNT || !value) return OSUF_EINVAL;
+  *value = osuf_knob(knob);
+  return OSUF_OK;
+}

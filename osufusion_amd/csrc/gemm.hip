@@ -10,8 +10,6 @@
 // Global -> LDS double buffering (one barrier per K-step), XOR-swizzled 16-B chunks so the
 // ds_read_b128 fragment reads are conflict-free; epilogue goes through LDS so HBM stores are full rows.
 #include "common.hpp"
-#include <optional>
-#include <stdlib.h>
 
 struct RowMap {
   int Lin, Lout, stride, pad, mode;
@@ -2416,14 +2414,6 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* Y, long ldy, int M
 // ---------------------------------------------------------------------------------------------------------
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// OSUF_GEMM_BIG_MIN_TILES overrides when the 256^2 kernels are picked (tests: 1 forces them, 0 / "off" rules them out).  Read on
-// every call: tests flip it between calls.
-static std::optional<long> big_min_tiles_override() {
-  const char* s = getenv("OSUF_GEMM_BIG_MIN_TILES");
-  if (!s) return std::nullopt;
-  return atol(s);
-}
-
 static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, long ldw, long tapstride,
                           void* C, long ldc, void* C2, long ldc2, const void* R, long ldr, const void* U, long ldu,
                           const float* bias, const float* rscale, double* stats,
@@ -2457,10 +2447,11 @@ static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, lon
     return osuf_launch_status();
   }
   // 256^2 tiles once they fill most of the 256 CUs
-  const std::optional<long> bigenv = big_min_tiles_override();
-  const long min_tiles = bigenv.value_or(192);
+  // (OSUF_KNOB_GEMM_BIG_MIN_TILES overrides when they are picked: n > 0 is the threshold and waives N >= 192, 0 rules them out)
+  const int bigknob = osuf_knob(OSUF_KNOB_GEMM_BIG_MIN_TILES);
+  const long min_tiles = bigknob == OSUF_KNOB_DEFAULT ? 192 : bigknob;
   const long big_tiles = (long)((M + kBig - 1) / kBig) * ((N + kBig - 1) / kBig);
-  const bool use_big = (dtype == OSUF_DT_BF16 || dtype == OSUF_DT_F32X3) && min_tiles > 0 && big_tiles >= min_tiles && (N >= 192 || bigenv) && N % 8 == 0 &&
+  const bool use_big = (dtype == OSUF_DT_BF16 || dtype == OSUF_DT_F32X3) && min_tiles > 0 && big_tiles >= min_tiles && (N >= 192 || bigknob != OSUF_KNOB_DEFAULT) && N % 8 == 0 &&
                        ldc % 8 == 0 && (!C2 || ldc2 % 8 == 0) && (!R || ldr % 8 == 0) && (!U || ldu % 8 == 0) &&
                        (!bias || (reinterpret_cast<uintptr_t>(bias) & 31) == 0) && (!rscale || (reinterpret_cast<uintptr_t>(rscale) & 31) == 0);
   if (use_big) {
@@ -2471,18 +2462,18 @@ static int gemm_nt_launch(int dtype, const void* A, long lda, const void* W, lon
     const long tm = (M + kBig - 1) / kBig, tn = (N + kBig - 1) / kBig;
     const dim3 grid_big((int)(((tm + 7) / 8) * 8 * tn));
     const bool halo3 = taps == 3 && mode == 0 && stride == 1 && pad == 1 && Lin == Lout && Lout % kBig == 0 && K % (dtype == OSUF_DT_BF16 ? 64 : 32) == 0 &&
-                       getenv("OSUF_GEMM_NOHALO") == nullptr;
+                       !osuf_knob_on(OSUF_KNOB_GEMM_NOHALO);
     if (halo3) {
       allow_lds<gemm_nt_big_halo3_kernel<bf16_t>>(lds_big);
       allow_lds<gemm_nt_big_halo3_kernel<float>>(lds_big);
-      if (dtype == OSUF_DT_BF16 && getenv("OSUF_GEMM_NO8P") == nullptr && K <= 8192) {
+      if (dtype == OSUF_DT_BF16 && !osuf_knob_on(OSUF_KNOB_GEMM_NO8P) && K <= 8192) {
         const int lds_h8 = kH8B + 65536 + 2112;
         allow_lds<gemm_nt_big8_halo3_kernel>(lds_h8);
         hipLaunchKernelGGL(gemm_nt_big8_halo3_kernel, grid_big, dim3(512), lds_h8, stream, g);
       } else if (dtype == OSUF_DT_BF16) hipLaunchKernelGGL(gemm_nt_big_halo3_kernel<bf16_t>, grid_big, dim3(512), lds_big, stream, g);
       else hipLaunchKernelGGL(gemm_nt_big_halo3_kernel<float>, grid_big, dim3(512), lds_big, stream, g);
-    } else if (dtype == OSUF_DT_BF16 && getenv("OSUF_GEMM_NO8P") == nullptr && taps <= kP8MaxTaps && K <= 8192 && K % 64 == 0) {
-      // (the 8-phase loop; OSUF_GEMM_NO8P=1 = the one-barrier-per-K-step loop above, for A/B runs and for K % 64 != 0 / more than 16 taps)
+    } else if (dtype == OSUF_DT_BF16 && !osuf_knob_on(OSUF_KNOB_GEMM_NO8P) && taps <= kP8MaxTaps && K <= 8192 && K % 64 == 0) {
+      // (the 8-phase loop; OSUF_KNOB_GEMM_NO8P = the one-barrier-per-K-step loop above, for A/B runs and for K % 64 != 0 / more than 16 taps)
       allow_lds<gemm_nt_big8_kernel>(kP8Tbl + kP8MaxTaps * kBig * 4);       // once, so for the most taps a launch can have
       hipLaunchKernelGGL(gemm_nt_big8_kernel, grid_big, dim3(512), lds_p8, stream, g);
     } else if (dtype == OSUF_DT_F32X3) hipLaunchKernelGGL((gemm_nt_big_kernel<float, true>), grid_big, dim3(512), lds_big, stream, g);
@@ -2516,8 +2507,8 @@ extern "C" int osuf_gemm_nt_rowdot(int dtype, const void* A, long lda, const voi
 
 // split plan of the 256x256 wgrad kernel: rows of m per split and number of splits (one workgroup per CU, ~1.25 rounds)
 static bool tn_big_plan(int dtype, int M, int N1, int N2, int taps, int* rows_out, int* splits_out) {
-  const std::optional<long> bigenv = big_min_tiles_override();
-  const bool forced = bigenv == 1, off = bigenv && *bigenv <= 0;
+  const int bigknob = osuf_knob(OSUF_KNOB_GEMM_BIG_MIN_TILES);
+  const bool forced = bigknob == 1, off = bigknob == 0;
   if ((dtype != OSUF_DT_BF16 && dtype != OSUF_DT_F32X3) || off || !(forced || (N1 >= 64 && N2 >= 64 && (N1 >= 192 || N2 >= 192)))) return false;
   const int btiles = ((N1 + kBig - 1) / kBig) * ((N2 + kBig - 1) / kBig);
   int sp = (256 + btiles * taps / 2) / (btiles * taps);        // one workgroup per CU: about one round of the 256 CUs
@@ -2540,9 +2531,9 @@ extern "C" long osuf_gemm_tn_workspace_bytes(int dtype, int M, int N1, int N2, i
   return (long)sp * taps * N1 * N2 * (long)sizeof(float);            // (bf16-pair partial tiles need half of it; one size keeps callers simple)
 }
 // bf16 kernels write their partial tiles as bf16 pairs of rows (half the bytes of the write-out and of the reduce's reads); the fp32
-// modes keep fp32 tiles.  OSUF_WGRAD_F32_PARTIALS=1 restores fp32 tiles for A/B.
+// modes keep fp32 tiles.  OSUF_KNOB_WGRAD_F32_PARTIALS restores fp32 tiles for A/B.
 static bool wgrad_pk(int dtype, int N1, int N2) {
-  return dtype == OSUF_DT_BF16 && (N1 % 2) == 0 && (N2 % 4) == 0 && getenv("OSUF_WGRAD_F32_PARTIALS") == nullptr;
+  return dtype == OSUF_DT_BF16 && (N1 % 2) == 0 && (N2 % 4) == 0 && !osuf_knob_on(OSUF_KNOB_WGRAD_F32_PARTIALS);
 }
 
 extern "C" int osuf_colsum(int dtype, const void* Y, long ldy, int M, int N, float* out, hipStream_t stream) {
@@ -2618,7 +2609,7 @@ static int gemm_tn_launch(int dtype, const void* dY, long ldy, const void* X, lo
     return osuf_launch_status();
   }
   if (splits <= 0 && (dtype == OSUF_DT_BF16 || dtype == OSUF_DT_F32X3) && taps == 3 && mode == 0 && stride == 1 && pad == 1 && Lin == Lout && Lout % 128 == 0 && N1 >= 64 &&
-      N2 >= 64 && tn_big_plan(dtype, M, N1, N2, taps, nullptr, nullptr) && getenv("OSUF_GEMM_NOHALO") == nullptr) {
+      N2 >= 64 && tn_big_plan(dtype, M, N1, N2, taps, nullptr, nullptr) && !osuf_knob_on(OSUF_KNOB_GEMM_NOHALO)) {
     // the three taps in one workgroup (gemm_tn_taps3_kernel): 128 x 128 tiles, about one round of the 256 CUs
     const int btiles = ((N1 + 127) / 128) * ((N2 + 127) / 128);
     int sp = 256 / btiles;

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
-import os
+import ctypes
 
 import numpy as np
 import torch
@@ -133,6 +133,55 @@ class one_launch_attention:
     def __exit__(self, *exc):
         global _ONE_LAUNCH_ATTENTION
         _ONE_LAUNCH_ATTENTION = self.prev
+        return False
+
+
+# Forced paths (tests and A/B runs; not configuration).  The six launcher branches of the library are slots of its override table, in the order
+# of the OSUF_KNOB_* enumeration of include/osufusion_hip.h; the two choices made on this side of the C ABI are module state.
+_KNOBS = {"gemm_big": 0, "no8p": 1, "nohalo": 2, "wgrad_f32_partials": 3, "attn_fwd_nowhole": 4, "attn_fwd_noqsk": 5}
+_SWITCHES = {"zdq": True, "fwd_rope": True}
+
+
+def _forced(name: str):
+    if name in _SWITCHES:
+        return _SWITCHES[name]
+    v = ctypes.c_int()
+    _lib.check(_lib.load().osuf_override_get(_KNOBS[name], ctypes.byref(v)), "osuf_override_get")
+    return v.value
+
+
+def _set_forced(name: str, value) -> None:
+    if name in _SWITCHES:
+        _SWITCHES[name] = True if value is None else bool(value)
+    else:
+        _lib.check(_lib.load().osuf_override_set(_KNOBS[name], -1 if value is None else int(value)), "osuf_override_set")
+
+
+class force:
+    """Force kernel paths for the body of a `with`; the previous values come back on exit, also when the body raises.  None = the default.
+    gemm_big=n: the 256 x 256 GEMM kernels from n tiles on whatever the width (1 forces them, the wgrad split plan included), 0 rules them out;
+    no8p / nohalo / wgrad_f32_partials / attn_fwd_nowhole / attn_fwd_noqsk=True: see OSUF_KNOB_* in the header;
+    zdq=False: no dQ accumulator zero-filled by the forward (fused_bwd_workspace); fwd_rope=False: no forward that rotates its queries (fwd_rope_ok)."""
+
+    def __init__(self, **values) -> None:
+        for name in values:
+            if name not in _KNOBS and name not in _SWITCHES:
+                raise TypeError(f"force() got an unexpected keyword argument {name!r}")
+        self.values = values
+
+    def __enter__(self):
+        self.prev = {name: _forced(name) for name in self.values}
+        try:
+            for name, value in self.values.items():
+                _set_forced(name, value)
+        except BaseException:
+            self.__exit__()
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        for name, value in self.prev.items():
+            _set_forced(name, value)
         return False
 
 
@@ -503,9 +552,9 @@ DQ_PREZEROED = 0x100                                             # OSUF_DQ_PREZE
 def fused_bwd_workspace(B: int, N: int, H: int, D: int, out_dtype: torch.dtype, device, variant: Optional[int] = None, qsplit: int = 0):
     """A PRIVATE workspace for one layer's fused attention backward, to be zero-filled by that layer's forward (mqa_fwd(zero_dq=...)) and handed to
     mqa_bwd(workspace=...): the dQ accumulator's memset (66 us per N = 4096 layer in front of the backward sweep) then rides the forward
-    kernel, which is bound by the vector pipe and leaves HBM idle.  None where the path does not apply (head dim != 64, non-atomic dQ, OSUF_ATTN_NO_ZDQ=1)."""
+    kernel, which is bound by the vector pipe and leaves HBM idle.  None where the path does not apply (head dim != 64, non-atomic dQ, force(zdq=False))."""
     variant = ATTN_BWD_DEFAULT if variant is None else variant
-    if D != 64 or variant not in _FUSED_DQ_MODE or variant == ATTN_FUSED_SLABS or os.environ.get("OSUF_ATTN_NO_ZDQ") == "1":
+    if D != 64 or variant not in _FUSED_DQ_MODE or variant == ATTN_FUSED_SLABS or not _SWITCHES["zdq"]:
         return None
     need = _lib.load().osuf_mqa_bwd_fused_workspace_bytes(B, H, N, _DT[out_dtype], qsplit, _FUSED_DQ_MODE[variant])
     if need <= 0:
@@ -549,8 +598,9 @@ def gqa_fwd(qkv: torch.Tensor, B: int, N: int, H: int, D: int, out_dtype: torch.
 
 
 def fwd_rope_ok(qkv: torch.Tensor, head_dim: int, kv_heads: int, qs: bool) -> bool:
-    """The forward that rotates its own queries (mqa_fwd_rope) applies: bf16 projections, 64-wide heads, one K/V head, pre-scaled-query kernels."""
-    return qs and head_dim == 64 and kv_heads == 1 and qkv.dtype == torch.bfloat16 and os.environ.get("OSUF_ATTN_NO_FWD_ROPE") != "1"
+    """The forward that rotates its own queries (mqa_fwd_rope) applies: bf16 projections, 64-wide heads, one K/V head, pre-scaled-query kernels
+    (and not ruled out by force(fwd_rope=False))."""
+    return qs and head_dim == 64 and kv_heads == 1 and qkv.dtype == torch.bfloat16 and _SWITCHES["fwd_rope"]
 
 
 def mqa_fwd_rope(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, N: int, H: int, D: int, out_dtype: torch.dtype, scale: float,

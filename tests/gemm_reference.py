@@ -157,7 +157,7 @@ def geom(kind, k, L):
 # which kernel the launchers pick (gemm_nt_launch / gemm_tn_launch restated; the kernel trace of the GPU file is the proof)
 # ---------------------------------------------------------------------------------------------------------------------------------
 def nt_kernel(mode, M, N, K, g, big, no8p=False, nohalo=False, plain=True):
-    """mode "bf16" | "f32" | "x3"; g: geometry dict; big: OSUF_GEMM_BIG_MIN_TILES=1; plain: no epilogue operand at all."""
+    """mode "bf16" | "f32" | "x3"; g: geometry dict; big: ops.force(gemm_big=1); plain: no epilogue operand at all."""
     if mode == "bf16" and N <= 32 and M >= 4096 and plain:
         return "gemm_nt_skinny_kernel"
     if not big or mode == "f32":
@@ -196,7 +196,7 @@ GEOMETRIES = [
 ]
 # (mode, forced 256^2) crossed with every geometry; exact f32 has no 256^2 kernel
 GEO_MODES = [("bf16", False), ("bf16", True), ("f32", False), ("x3", False), ("x3", True)]
-# shared-panel k = 3 kernels (forced 256^2, L % 256 == 0): (mode, L, K, OSUF_GEMM_NO8P)
+# shared-panel k = 3 kernels (forced 256^2, L % 256 == 0): (mode, L, K, ops.force(no8p=True))
 HALO = ([("bf16", L, K, no8p) for L in (256, 512) for K in (64, 128, 192) for no8p in (False, True)] +
         [("x3", L, K, False) for L in (256, 512) for K in (32, 96)])
 # K > 8192: both 8-phase kernels fall back to the one-barrier loops -- (k, B, L): M = 264 for k = 1; the k = 3 panel needs L = 256
@@ -237,10 +237,10 @@ FAST = 2.0 ** -21
 
 COLSUM_M, COLSUM_N = [1, 256, 257, 700], [8, 264, 520]
 
-# Weight gradients, exact: (id, mode, B, L, N1, N2, kind, k, conv_layout, accumulate, env, kernel, reduce kernel or None)
-_F32P = {"OSUF_WGRAD_F32_PARTIALS": "1"}
-_OFF = {"OSUF_GEMM_BIG_MIN_TILES": "0"}
-_BIG = {"OSUF_GEMM_BIG_MIN_TILES": "1"}
+# Weight gradients, exact: (id, mode, B, L, N1, N2, kind, k, conv_layout, accumulate, ops.force keywords, kernel, reduce kernel or None)
+_F32P = {"wgrad_f32_partials": True}
+_OFF = {"gemm_big": 0}
+_BIG = {"gemm_big": 1}
 WGRAD_EXACT = [
     ("tn128_bf16_t3", "bf16", 3, 200, 328, 128, "same", 3, True, False, _OFF, "gemm_tn_kernel<bf16>", None),
     ("tn128_f32_t3", "f32", 3, 200, 328, 128, "same", 3, True, True, {}, "gemm_tn_kernel<float>", None),

@@ -87,7 +87,7 @@ def ref_rows(ref, G=1):
 
 # ---- forward, head dim 64 -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("N", R.LENGTHS)
-def test_mqa_fwd_64(N, monkeypatch):
+def test_mqa_fwd_64(N):
     """mqa_fwd_kernel: plain / WHOLE (N % 64 == 0), pre-scaled queries, rope in the kernel with and without write_q, zero_dq; osuf_rope_cast / _qs."""
     D = 64
     B, H = shape_for(N)
@@ -131,12 +131,11 @@ def test_mqa_fwd_64(N, monkeypatch):
             o, lse = ops.mqa_fwd(strided(qr), B, N, H, D, dt, c.scale, qs=True)
             ck = Exact("mqa_fwd_qs", dt, **where)
             ck.finite(o=o, lse=lse); ck.value("o", o, refq["o"]); ck.lse(lse, refq["lse2"]); ck.done()
-        if N == 64 and kind == "tie":                                   # the getenv-gated fall-backs of the launcher: one case each
-            for env, qs_ in (("OSUF_ATTN_FWD_NOWHOLE", False), ("OSUF_ATTN_FWD_NOQSK", True)):
-                monkeypatch.setenv(env, "1")
-                o, lse = ops.mqa_fwd(strided(qr) if qs_ else qkv, B, N, H, D, BF16, c.scale, qs=qs_)
-                monkeypatch.delenv(env)
-                ck = Exact("mqa_fwd_" + env.rsplit("_", 1)[1].lower(), BF16, **where)
+        if N == 64 and kind == "tie":                                   # the override-gated fall-backs of the launcher: one case each
+            for knob, qs_ in (("attn_fwd_nowhole", False), ("attn_fwd_noqsk", True)):
+                with ops.force(**{knob: True}):
+                    o, lse = ops.mqa_fwd(strided(qr) if qs_ else qkv, B, N, H, D, BF16, c.scale, qs=qs_)
+                ck = Exact("mqa_fwd_" + knob.rsplit("_", 1)[1], BF16, **where)
                 ck.value("o", o, (refq if qs_ else ref)["o"]); ck.lse(lse, (refq if qs_ else ref)["lse2"]); ck.done()
         # osuf_mqa_fwd_rope: un-rotated bf16 projections in, the kernel rotates / scales / rounds its queries
         for write_q in (True, False):

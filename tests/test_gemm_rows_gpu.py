@@ -3,7 +3,7 @@ launch_wgrad_reduce and osuf_colsum pick from.  Every launch is checked on input
 
 References and case tables: tests/gemm_reference.py (checked on the CPU by tests/test_gemm_reference_cpu.py, which also holds every cap
 used here above 16 x the fp32 evaluation's own noise).  Kernels are forced with the switches the suite already uses
-(OSUF_GEMM_BIG_MIN_TILES, OSUF_GEMM_NO8P, OSUF_WGRAD_F32_PARTIALS, ops.set_f32_matmul); the kernel each case reaches is named in its
+(ops.force(gemm_big=, no8p=, wgrad_f32_partials=), ops.set_f32_matmul); the kernel each case reaches is named in its
 table entry (gemm_reference.nt_kernel / the WGRAD tables) and listed from a kernel trace in profiles/gemm_sweep.md.
 
 A. Geometry, exact: operands are small integers (|A| <= 3, |W| <= 2), so every partial sum is an integer below 2^24, exact in fp32 in any
@@ -14,6 +14,8 @@ B. Epilogue, real-valued, bounded (tests/bound_check.py): an fp32 result within 
    FAST * (1 + max|U|).  x3 is held to the fp64 sum of the three products mfma_x3 issues, and that to 3e-5 rel-L2 of the unsplit product.
    GroupNorm sums are referenced from the kernel's own stored output (1e-5), delta from bf16(C as stored) . O.
 """
+import contextlib
+
 import pytest
 import torch
 
@@ -26,7 +28,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 F32, F64, BF16 = torch.float32, torch.float64, torch.bfloat16
 SENT = 777.0
-SWITCHES = ("OSUF_GEMM_BIG_MIN_TILES", "OSUF_GEMM_NO8P", "OSUF_GEMM_NOHALO", "OSUF_WGRAD_F32_PARTIALS")
 
 
 EPI_IDS = lambda v: v if isinstance(v, str) else ("big" if v else "128")
@@ -45,24 +46,15 @@ def dev(t, mode):
 
 
 @pytest.fixture()
-def force(monkeypatch):
-    """force(mode, big=None|bool, **env): sets the compute mode and the dispatch switches for the test, all others cleared."""
-    prev = []
+def force():
+    """force(mode, big=None|bool, no8p, env=ops.force keywords): sets the compute mode and the dispatch overrides for the test, all others at their default."""
+    with contextlib.ExitStack() as stack:
+        def set_(mode, big=None, no8p=False, env=None):
+            stack.enter_context(ops.force(gemm_big=None if big is None else int(big), no8p=no8p, nohalo=None, wgrad_f32_partials=None))
+            stack.enter_context(ops.force(**(env or {})))
+            stack.callback(ops.set_f32_matmul, ops.set_f32_matmul("x3" if mode == "x3" else "exact"))
 
-    def set_(mode, big=None, no8p=False, env=None):
-        for s in SWITCHES:
-            monkeypatch.delenv(s, raising=False)
-        if big is not None:
-            monkeypatch.setenv("OSUF_GEMM_BIG_MIN_TILES", "1" if big else "0")
-        if no8p:
-            monkeypatch.setenv("OSUF_GEMM_NO8P", "1")
-        for k, v in (env or {}).items():
-            monkeypatch.setenv(k, v)
-        prev.append(ops.set_f32_matmul("x3" if mode == "x3" else "exact"))
-
-    yield set_
-    if prev:
-        ops.set_f32_matmul(prev[0])
+        yield set_
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -95,7 +87,7 @@ def test_shared_panel_k3_exact(force, mode, L, K, no8p):
 
 @pytest.mark.parametrize("k,B,L", G.K8256)
 def test_k_above_8192_falls_back_exact(force, k, B, L):
-    """K = 8256 > 8192 without OSUF_GEMM_NO8P: gemm_nt_big8_kernel / gemm_nt_big8_halo3_kernel hand over to the one-barrier loops."""
+    """K = 8256 > 8192 without ops.force(no8p=True): gemm_nt_big8_kernel / gemm_nt_big8_halo3_kernel hand over to the one-barrier loops."""
     force("bf16", True)
     exact_nt("bf16", B, 256, 8256, G.geom("same", k, L)[0])
 

@@ -5,6 +5,7 @@ Tolerances (relative to the reference tensor's max-abs unless stated):
                        attention is bf16 inside the reference itself (attention.py:87-101), noise floor ~5e-4.
   bf16 mode : 3e-2 element-wise on single blocks vs the oracle's bf16 emulation, 2e-2 rel-L2 on whole-UNet outputs.
 """
+import contextlib
 import json
 
 import numpy as np
@@ -53,6 +54,13 @@ def report(name, **vals):
     os.makedirs("gpurun_out", exist_ok=True)
     with open("gpurun_out/parity_metrics.jsonl", "a") as f:
         f.write(json.dumps({"test": name, **{k: (v if isinstance(v, (list, str)) else float(v)) for k, v in vals.items()}}) + "\n")
+
+
+@pytest.fixture()
+def forcing():
+    """forcing(**overrides): ops.force for the rest of the test."""
+    with contextlib.ExitStack() as stack:
+        yield lambda **kw: stack.enter_context(ops.force(**kw))
 
 
 def load_pattern(module):
@@ -177,7 +185,7 @@ def test_conv_fn_forward_backward(dtype, tol, kind, k, L):
 
 
 @pytest.mark.parametrize("kind,k,L", [("same", 3, 200), ("same", 1, 520), ("down", 3, 96), ("up", 3, 56), ("same", 15, 64)])
-def test_big_tile_gemm_kernel(monkeypatch, kind, k, L):
+def test_big_tile_gemm_kernel(kind, k, L):
     """The 256x256 8-wave LDS-DMA kernel is normally selected only for chip-filling shapes; force it on small ragged ones
     (M, N, K tails, every row-map mode, every epilogue option) and compare with the 128x128 kernel bit for bit."""
     Cin, Cout = 72, 328
@@ -188,16 +196,13 @@ def test_big_tile_gemm_kernel(monkeypatch, kind, k, L):
     res = torch.randn(B, Lout, Cout, device=DEV).to(torch.bfloat16)
     rscale = torch.rand(B, Cout, device=DEV)
     outs = []
-    monkeypatch.setenv("OSUF_WGRAD_F32_PARTIALS", "1")           # pin the kernel's products: fp32 partial tiles (the bf16-pair tiles of round 4 have
-    for force in ("0", "1"):                                     # their own test, tests/test_round4_gpu.py)
-        monkeypatch.setenv("OSUF_GEMM_BIG_MIN_TILES", force)
-        stats = torch.zeros(B, 2, dtype=torch.float64, device=DEV)
-        y, pre = Fn.conv_forward(x, w, bias, Fn.PackCache(), kind, None, act=1, residual=res, rscale=rscale, stats=stats, want_pre=True)
-        dx = Fn.conv_dgrad(y, w, Fn.PackCache(), kind, L, residual=x)
-        dw = Fn.conv_wgrad(res, x, w, kind)                      # 256x256 LDS-DMA wgrad kernel when forced
+    for big in (0, 1):                                           # fp32 partial tiles pin the kernel's products (the bf16-pair tiles of round 4 have
+        with ops.force(gemm_big=big, wgrad_f32_partials=True):   # their own test, tests/test_round4_gpu.py)
+            stats = torch.zeros(B, 2, dtype=torch.float64, device=DEV)
+            y, pre = Fn.conv_forward(x, w, bias, Fn.PackCache(), kind, None, act=1, residual=res, rscale=rscale, stats=stats, want_pre=True)
+            dx = Fn.conv_dgrad(y, w, Fn.PackCache(), kind, L, residual=x)
+            dw = Fn.conv_wgrad(res, x, w, kind)                  # 256x256 LDS-DMA wgrad kernel when forced
         outs.append((y.float(), pre.float(), stats.clone(), dx.float(), dw.float()))
-    monkeypatch.delenv("OSUF_GEMM_BIG_MIN_TILES")
-    monkeypatch.delenv("OSUF_WGRAD_F32_PARTIALS")
     (y0, p0, s0, d0, w0), (y1, p1, s1, d1, w1) = outs
     assert torch.equal(p0, p1)
     # y = silu(.)+res*rscale: the two kernels' epilogues are separate instantiations and may contract mul+add differently -- at most a

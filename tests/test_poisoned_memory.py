@@ -11,7 +11,6 @@ Shapes are those of the parity tests (tests/test_hip_parity.py, test_round5_gpu.
 tails, N in {200, 512, 1024, 2048}.  The CPU test at the end requires a case (or a written exemption) for every allocating function of
 osufusion_amd/ops.py and functional.py."""
 import ast
-import os
 from pathlib import Path
 
 import pytest
@@ -104,9 +103,9 @@ def run_case(fn):
 # ----------------------------------------------------------------------------------------------------------------------------------------
 def conv_epilogue(kind, k, L, Cin, dtype, big=None):
     """conv_forward with every epilogue option (bias, SiLU, pre-activation copy, residual x per-sample scale, GroupNorm sums) and its input
-    gradient with a residual -- the 128 x 128 kernel, or (big="1") the 256 x 256 ones forced onto the small shape."""
+    gradient with a residual -- the 128 x 128 kernel, or (big=1) the 256 x 256 ones forced onto the small shape."""
     def run(c):
-        from osufusion_amd import functional as Fn
+        from osufusion_amd import functional as Fn, ops
         Cout, B = 328, 2
         Lout = {"same": L, "down": L // 2, "up": 2 * L}[kind]
         x = c.inp(rnd("x", (B, L, Cin)), dtype)
@@ -114,20 +113,11 @@ def conv_epilogue(kind, k, L, Cin, dtype, big=None):
         bias = c.inp(rnd("b", (Cout,)))
         res = c.inp(rnd("r", (B, Lout, Cout)), dtype)
         rscale = c.inp(rnd("s", (B, Cout)).abs())
-        prev = os.environ.get("OSUF_GEMM_BIG_MIN_TILES")
-        if big is not None:
-            os.environ["OSUF_GEMM_BIG_MIN_TILES"] = big
-        try:
+        with ops.force(**({} if big is None else {"gemm_big": big})):
             stats = torch.zeros(B, 2, dtype=torch.float64, device=DEV)
             y, pre = Fn.conv_forward(x, w, bias, Fn.PackCache(), kind, None, act=1, residual=res, rscale=rscale, stats=stats, want_pre=True)
             dx = Fn.conv_dgrad(y, w, Fn.PackCache(), kind, L, residual=x)
             y2 = Fn.conv_forward(x, w, None, Fn.PackCache(), kind, None)
-        finally:
-            if big is not None:
-                if prev is None:
-                    os.environ.pop("OSUF_GEMM_BIG_MIN_TILES")
-                else:
-                    os.environ["OSUF_GEMM_BIG_MIN_TILES"] = prev
         c.eq("y", y), c.eq("pre", pre), c.eq("dx", dx), c.eq("y_plain", y2)
         yd = y.double()                                                   # the sums are of the stored (rounded) outputs
         c.close("stats", stats, torch.stack([yd.sum((1, 2)), (yd * yd).sum((1, 2))], 1), 1e-5)
@@ -615,8 +605,8 @@ CASES = {
     "gemm_nt": [("conv_same_k3_bf16", conv_epilogue("same", 3, 200, 72, BF)), ("conv_same_k3_f32", conv_epilogue("same", 3, 200, 72, F32)),
                 ("conv_down_bf16", conv_epilogue("down", 3, 96, 72, BF)), ("conv_up_f32", conv_epilogue("up", 3, 56, 72, F32)),
                 ("conv_k15_bf16", conv_epilogue("same", 15, 64, 72, BF)),
-                ("big256_same_k3", conv_epilogue("same", 3, 200, 64, BF, big="1")), ("big256_8phase_k1", conv_epilogue("same", 1, 264, 192, BF, big="1")),
-                ("big256_down", conv_epilogue("down", 3, 96, 128, BF, big="1")), ("big256_up", conv_epilogue("up", 3, 56, 64, BF, big="1")),
+                ("big256_same_k3", conv_epilogue("same", 3, 200, 64, BF, big=1)), ("big256_8phase_k1", conv_epilogue("same", 1, 264, 192, BF, big=1)),
+                ("big256_down", conv_epilogue("down", 3, 96, 128, BF, big=1)), ("big256_up", conv_epilogue("up", 3, 56, 64, BF, big=1)),
                 ("plain_ragged_bf16", plain_gemm(133, 200, 136, BF)), ("plain_ragged_f32", plain_gemm(133, 200, 136, F32)),
                 ("skinny_n_taps", plain_gemm(4100, 16, 328, BF, taps=3, slice_out=False)), ("plain_k_tail", plain_gemm(70, 24, 48, F32))],
     "gemm_nt_rowdot": [("heads4_L200", gemm_rowdot)],

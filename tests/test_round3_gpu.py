@@ -13,7 +13,7 @@ if torch.cuda.is_available():
     from osufusion_amd import functional as Fn
     from osufusion_amd import ops
 
-from tests.test_hip_parity import DEV, T, load_pattern, rell2, report
+from tests.test_hip_parity import DEV, T, forcing, load_pattern, rell2, report  # noqa: F401  (forcing: a fixture)
 
 _TINY = dict(dim_h_mult=(1, 2), num_layer_blocks=(2, 2), num_middle_transformers=1, cross_embed_kernel_sizes=(3,), attn_dim_head=64,
              attn_context_len=512)
@@ -278,12 +278,12 @@ def test_attention_module_head_dims_vs_oracle(D, heads, kv_heads):
 
 @pytest.mark.parametrize("big", [False, True])
 @pytest.mark.parametrize("M,N,K,taps", [(1024, 256, 256, 3), (520, 96, 40, 1), (2048, 768, 512, 1)])
-def test_f32x3_gemms_keep_seventeen_bits(monkeypatch, M, N, K, taps, big):
+def test_f32x3_gemms_keep_seventeen_bits(forcing, M, N, K, taps, big):
     """OSUF_DT_F32X3 (fp32 storage, three bf16 MFMAs on split operands) for the conv / linear GEMMs and their weight gradients against an
     fp64 product: an order of magnitude and a half inside north_star's 1e-3, two orders better than bf16 operands (residual.py:70,115,
     unet.py:118-123,149-156 in an fp32 run).  big: the 256x256 LDS-DMA kernels' x3 paths forced onto these small ragged shapes."""
     if big:
-        monkeypatch.setenv("OSUF_GEMM_BIG_MIN_TILES", "1")
+        forcing(gemm_big=1)
     torch.manual_seed(1)
     L = M // 2
     a = torch.randn(M, K, device=DEV)
@@ -429,7 +429,7 @@ def test_masked_forward_op_random_bias(D, N):
 
 
 @pytest.mark.parametrize("Cin,Cout,L,Bq", [(128, 328, 512, 3), (64, 256, 256, 4), (192, 72, 768, 2)])
-def test_halo_shared_k3_conv_kernel(monkeypatch, Cin, Cout, L, Bq):
+def test_halo_shared_k3_conv_kernel(forcing, Cin, Cout, L, Bq):
     """gemm_nt_big_halo3_kernel (k = 3 'same' convs and their input gradients with L % 256 == 0: one activation panel per K-step shared by
     the three taps) forced onto small shapes: against the plain 256x256 kernel (same products, K-step-major instead of tap-major fp32
     sums) and against conv1d on the bf16-rounded operands -- sample edges (halo rows from the zero page), N tail, every epilogue
@@ -437,8 +437,7 @@ def test_halo_shared_k3_conv_kernel(monkeypatch, Cin, Cout, L, Bq):
     import torch.nn.functional as F
     from tests.test_hip_parity import relmax
     torch.manual_seed(Cin + L)
-    monkeypatch.setenv("OSUF_GEMM_BIG_MIN_TILES", "1")
-    monkeypatch.setenv("OSUF_WGRAD_F32_PARTIALS", "1")         # pins the kernels' products (round 4's bf16-pair partial tiles: tests/test_round4_gpu.py)
+    forcing(gemm_big=1, wgrad_f32_partials=True)               # pins the kernels' products (round 4's bf16-pair partial tiles: tests/test_round4_gpu.py)
     x = torch.randn(Bq, L, Cin, device=DEV).to(torch.bfloat16)
     w = torch.randn(Cout, Cin, 3, device=DEV) / (Cin * 3) ** 0.5
     bias = torch.randn(Cout, device=DEV)
@@ -446,14 +445,11 @@ def test_halo_shared_k3_conv_kernel(monkeypatch, Cin, Cout, L, Bq):
     rscale = torch.rand(Bq, Cout, device=DEV)
     outs = []
     for nohalo in (True, False):
-        if nohalo:
-            monkeypatch.setenv("OSUF_GEMM_NOHALO", "1")
-        else:
-            monkeypatch.delenv("OSUF_GEMM_NOHALO")
-        stats = torch.zeros(Bq, 2, dtype=torch.float64, device=DEV)
-        y, pre = Fn.conv_forward(x, w, bias, Fn.PackCache(), "same", None, act=1, residual=res, rscale=rscale, stats=stats, want_pre=True)
-        dx = Fn.conv_dgrad(y, w, Fn.PackCache(), "same", L, residual=x)
-        dw = Fn.conv_wgrad(res, x, w, "same")                  # gemm_tn_taps3_kernel (three taps per workgroup, one X panel) when not "nohalo"
+        with ops.force(nohalo=nohalo):
+            stats = torch.zeros(Bq, 2, dtype=torch.float64, device=DEV)
+            y, pre = Fn.conv_forward(x, w, bias, Fn.PackCache(), "same", None, act=1, residual=res, rscale=rscale, stats=stats, want_pre=True)
+            dx = Fn.conv_dgrad(y, w, Fn.PackCache(), "same", L, residual=x)
+            dw = Fn.conv_wgrad(res, x, w, "same")              # gemm_tn_taps3_kernel (three taps per workgroup, one X panel) when not "nohalo"
         outs.append((y.float(), pre.float(), stats.clone(), dx.float(), dw.float()))
     (y0, p0, s0, d0, w0), (y1, p1, s1, d1, w1) = outs
     assert relmax(w1, w0) < 1e-5                               # same bf16 products, different fp32 summation order
@@ -472,12 +468,12 @@ def test_halo_shared_k3_conv_kernel(monkeypatch, Cin, Cout, L, Bq):
 @pytest.mark.parametrize("M,N1,N2,taps,force_big", [(1024, 328, 128, 3, True), (2048, 256, 64, 1, True), (4096, 1152, 256, 1, True),
                                                      (520, 96, 40, 1, False), (1024, 328, 128, 3, False)])
 @pytest.mark.parametrize("dtype", ["bf16", "x3"])
-def test_bias_gradient_rides_the_weight_gradient(monkeypatch, M, N1, N2, taps, force_big, dtype):
+def test_bias_gradient_rides_the_weight_gradient(forcing, M, N1, N2, taps, force_big, dtype):
     """osuf_gemm_tn_bias: the layer's bias gradient (column sums of dy) from the weight gradient's own pass over dy -- the merged-taps and
     256x256 bf16 kernels sum the dY fragments they hold, every other path (small shapes, the fp32 modes) runs osuf_colsum inside the entry
     point.  Against dy.sum(0) in fp64 and against osuf_gemm_tn + osuf_colsum (residual.py:70,115, unet.py:118-123,149-156)."""
     if force_big:
-        monkeypatch.setenv("OSUF_GEMM_BIG_MIN_TILES", "1")
+        forcing(gemm_big=1)
     torch.manual_seed(M + N1)
     L = M // 2
     dt = torch.bfloat16 if dtype == "bf16" else torch.float32

@@ -12,9 +12,9 @@ from tests.test_hip_parity import DEV, rell2, report
                                                          (16384, 4096, 1152, 256, 1, False),    # 256^2 kernel, kernel's own layout
                                                          (8192, 512, 1024, 1024, 3, True),      # deep level: few splits, large tiles
                                                          (16384, 4096, 256, 512, 1, True)])
-def test_bf16_pair_partial_tiles_of_the_split_weight_gradient(monkeypatch, M, L, N1, N2, taps, conv_layout):
+def test_bf16_pair_partial_tiles_of_the_split_weight_gradient(M, L, N1, N2, taps, conv_layout):
     """The bf16 weight-gradient kernels leave their per-split partial tiles as bf16 pairs of rows (half the write-out and half the reduce's
-    reads) and wgrad_reduce_pk_kernel sums them in fp32 in a fixed order: against the fp32 partial tiles (OSUF_WGRAD_F32_PARTIALS=1) the result
+    reads) and wgrad_reduce_pk_kernel sums them in fp32 in a fixed order: against the fp32 partial tiles (ops.force(wgrad_f32_partials=True)) the result
     moves by the rounding of one bf16 per split partial -- on these random operands, where the partials of different splits are uncorrelated and
     the total is no larger than its parts, that is the full 2^-9 / sqrt(3) ~ 1.7e-3 of the result (the worst case; real gradients sum correlated
     partials) -- against 1.1e-2 for the bf16 train step's gradients as a whole (tests/test_full_size.py holds those to the oracle's own
@@ -27,9 +27,8 @@ def test_bf16_pair_partial_tiles_of_the_split_weight_gradient(monkeypatch, M, L,
     got = ops.gemm_tn(dy, x, **kw)
     again = ops.gemm_tn(dy, x, **kw)
     assert torch.equal(got, again)
-    monkeypatch.setenv("OSUF_WGRAD_F32_PARTIALS", "1")
-    ref = ops.gemm_tn(dy, x, **kw)
-    monkeypatch.delenv("OSUF_WGRAD_F32_PARTIALS")
+    with ops.force(wgrad_f32_partials=True):
+        ref = ops.gemm_tn(dy, x, **kw)
     e = rell2(got, ref)
     base = torch.full_like(got, 0.25)
     acc = ops.gemm_tn(dy, x, out=base.clone(), accumulate=True, **kw)

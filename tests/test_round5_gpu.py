@@ -18,11 +18,11 @@ from tests.test_hip_parity import B, DEV, relmax, report
                                           ("down", 3, 96, 128),      # stride 2 + right reflect (row-map mode 1); its input gradient: mode 3, four taps
                                           ("up", 3, 56, 64),         # nearest x2 (mode 2); its input gradient: stride 2
                                           ("same", 15, 64, 64)])     # 15 taps (the table's upper range is 16)
-def test_gemm_8phase_kernel_bit_exact(monkeypatch, kind, k, L, Cin):
+def test_gemm_8phase_kernel_bit_exact(kind, k, L, Cin):
     """gemm_nt_big8_kernel (8-phase schedule: counted vmcnt, raw barriers, staggered wave halves; the default 256 x 256 forward / input-gradient
     kernel of residual.py:70,115, unet.py:118-123,149-156 for K % 64 == 0) forced onto small ragged shapes -- M, N tails, every row-map mode,
     every epilogue option (bias, SiLU, pre-activation copy, residual x per-sample scale, GroupNorm sums; the dgrad's residual) -- against
-    (a) the one-barrier-per-K-step 256 x 256 kernel (OSUF_GEMM_NO8P): same accumulation order, same epilogue code: bit-identical outputs;
+    (a) the one-barrier-per-K-step 256 x 256 kernel (ops.force(no8p=True)): same accumulation order, same epilogue code: bit-identical outputs;
     (b) the 128 x 128 kernel: bit-identical pre-activations (the epilogues differ in mul+add contraction by at most a bf16 ulp)."""
     Cout = 328
     x = torch.randn(B, L, Cin, device=DEV).to(torch.bfloat16)
@@ -32,23 +32,17 @@ def test_gemm_8phase_kernel_bit_exact(monkeypatch, kind, k, L, Cin):
     res = torch.randn(B, Lout, Cout, device=DEV).to(torch.bfloat16)
     rscale = torch.rand(B, Cout, device=DEV)
     outs = {}
-    for name, big, no8p in (("small", "0", None), ("plain", "1", "1"), ("p8", "1", None)):
-        monkeypatch.setenv("OSUF_GEMM_BIG_MIN_TILES", big)
-        if no8p:
-            monkeypatch.setenv("OSUF_GEMM_NO8P", no8p)
-        else:
-            monkeypatch.delenv("OSUF_GEMM_NO8P", raising=False)
-        stats = torch.zeros(B, 2, dtype=torch.float64, device=DEV)
-        y, pre = Fn.conv_forward(x, w, bias, Fn.PackCache(), kind, None, act=1, residual=res, rscale=rscale, stats=stats, want_pre=True)
-        dx = Fn.conv_dgrad(y, w, Fn.PackCache(), kind, L, residual=x)
-        # the launches without residual / pre-activation copy: transposed accumulators + gemm_big_epilogue_tr (bias, SiLU, GroupNorm sums)
-        stats2 = torch.zeros(B, 2, dtype=torch.float64, device=DEV)
-        y2 = Fn.conv_forward(x, w, bias, Fn.PackCache(), kind, None, act=1, stats=stats2)
-        y3 = Fn.conv_forward(x, w, None, Fn.PackCache(), kind, None)
-        dx2 = Fn.conv_dgrad(y, w, Fn.PackCache(), kind, L)
+    for name, big, no8p in (("small", 0, False), ("plain", 1, True), ("p8", 1, False)):
+        with ops.force(gemm_big=big, no8p=no8p):
+            stats = torch.zeros(B, 2, dtype=torch.float64, device=DEV)
+            y, pre = Fn.conv_forward(x, w, bias, Fn.PackCache(), kind, None, act=1, residual=res, rscale=rscale, stats=stats, want_pre=True)
+            dx = Fn.conv_dgrad(y, w, Fn.PackCache(), kind, L, residual=x)
+            # the launches without residual / pre-activation copy: transposed accumulators + gemm_big_epilogue_tr (bias, SiLU, GroupNorm sums)
+            stats2 = torch.zeros(B, 2, dtype=torch.float64, device=DEV)
+            y2 = Fn.conv_forward(x, w, bias, Fn.PackCache(), kind, None, act=1, stats=stats2)
+            y3 = Fn.conv_forward(x, w, None, Fn.PackCache(), kind, None)
+            dx2 = Fn.conv_dgrad(y, w, Fn.PackCache(), kind, L)
         outs[name] = (y.float(), pre.float(), stats.clone(), dx.float(), y2.float(), y3.float(), dx2.float(), stats2.clone())
-    monkeypatch.delenv("OSUF_GEMM_BIG_MIN_TILES")
-    monkeypatch.delenv("OSUF_GEMM_NO8P", raising=False)
     for a, b_ in zip(outs["p8"][:2] + outs["p8"][3:7], outs["plain"][:2] + outs["plain"][3:7]):
         assert torch.equal(a, b_)
     assert torch.allclose(outs["p8"][2], outs["plain"][2], rtol=1e-6)          # LDS float atomics inside a tile: order only
@@ -70,7 +64,6 @@ def test_gemm_8phase_kernel_bit_exact(monkeypatch, kind, k, L, Cin):
 def test_gemm_8phase_chip_filling_shapes_repeatable():
     """The same comparison on chip-filling shapes (every CU busy, DMA queues loaded -- where a fragment read overtaking its LDS-DMA would
     show), ten launches each: bit-identical to the one-barrier loop every time."""
-    import os
     for M, N, K, taps, halo in ((131072, 256, 256, 1, False), (65536, 1152, 256, 1, False), (32768, 512, 1024, 1, False), (32768, 768, 768, 3, False),
                                 (16384, 1024, 2048, 1, False),
                                 # the shared-panel k = 3 kernel (gemm_nt_big8_halo3_kernel) against gemm_nt_big_halo3_kernel: odd / even K-step counts, one K-step
@@ -79,18 +72,12 @@ def test_gemm_8phase_chip_filling_shapes_repeatable():
         x = torch.randn(M, K, device=DEV).bfloat16()
         w = (torch.randn(taps, N, K, device=DEV) * 0.05).bfloat16()
         kw = dict(taps=taps, lin=L, lout=L, stride=1, pad=taps // 2) if taps > 1 else {}
-        os.environ["OSUF_GEMM_NO8P"] = "1"
-        if not halo:
-            os.environ["OSUF_GEMM_NOHALO"] = "1"
-        try:
-            ref = ops.gemm_nt(x, w, None, **kw)
-            del os.environ["OSUF_GEMM_NO8P"]
+        with ops.force(nohalo=not halo):
+            with ops.force(no8p=True):
+                ref = ops.gemm_nt(x, w, None, **kw)
             for _ in range(10):
                 got = ops.gemm_nt(x, w, None, **kw)
                 assert torch.equal(got, ref), (M, N, K, taps)
-        finally:
-            os.environ.pop("OSUF_GEMM_NO8P", None)
-            os.environ.pop("OSUF_GEMM_NOHALO", None)
 
 
 @pytest.mark.parametrize("Bn,N,H,G,qsplit", [(2, 1024, 1, 1, 0), (2, 1024, 1, 1, 2), (1, 2048, 1, 1, 0), (1, 2048, 1, 1, 2),      # one query head per call
@@ -218,27 +205,22 @@ def test_forward_zero_fills_the_backward_dq_accumulator(Bn, N, H, qs):
 
 def test_attention_module_gradients_with_and_without_the_forward_zero_fill(monkeypatch):
     """AttentionFn end to end (LayerNorm -> q|kv -> RoPE -> attention -> to_out): every gradient with the dQ accumulator cleared by the forward kernel
-    against OSUF_ATTN_NO_ZDQ=1 (the memset in the backward entry point), and a no-grad forward allocates no workspace."""
+    against ops.force(zdq=False) (the memset in the backward entry point), and a no-grad forward allocates no workspace."""
     from osufusion_amd.modules.unet import Attention
     torch.manual_seed(3)
     att = Attention(256, heads=4, dim_head=64, kv_heads=1, context_len=1024).to(DEV)
     x = torch.randn(2, 1024, 256, device=DEV)
     res = {}
     for off in (False, True):
-        if off:
-            monkeypatch.setenv("OSUF_ATTN_NO_ZDQ", "1")
-        else:
-            monkeypatch.delenv("OSUF_ATTN_NO_ZDQ", raising=False)
         for p in att.parameters():
             p.grad = None
         xi = x.clone().requires_grad_()
-        with forced_compute_dtype(torch.bfloat16):
+        with ops.force(zdq=not off), forced_compute_dtype(torch.bfloat16):
             y = att(xi)
             y.float().square().mean().backward()
         res[off] = [xi.grad.clone()] + [p.grad.clone() for p in att.parameters()]
     for a, b in zip(res[False], res[True]):
         assert torch.isfinite(a).all() and ((a.float() - b.float()).norm() / b.float().norm().clamp_min(1e-20)).item() < 1e-5
-    monkeypatch.delenv("OSUF_ATTN_NO_ZDQ", raising=False)
     calls = []
     real = ops.fused_bwd_workspace
     monkeypatch.setattr(ops, "fused_bwd_workspace", lambda *a, **k: calls.append(1) or real(*a, **k))
@@ -282,8 +264,8 @@ def test_forward_rotates_its_own_queries(Bn, N, H):
     assert torch.equal(o1, o3) and int((ws[: Bn * N * H * D] != 0).sum().item()) == 0
 
 
-def test_attention_module_with_and_without_the_rotating_forward(monkeypatch):
-    """AttentionFn end to end, default path (the forward rotates its queries) against OSUF_ATTN_NO_FWD_ROPE=1 (rope_cast over all heads): output and every
+def test_attention_module_with_and_without_the_rotating_forward():
+    """AttentionFn end to end, default path (the forward rotates its queries) against ops.force(fwd_rope=False) (rope_cast over all heads): output and every
     gradient to bf16 rounding noise; and the inference forward (no_grad: no stored queries) equals the training forward."""
     from osufusion_amd.modules.unet import Attention
     torch.manual_seed(5)
@@ -291,20 +273,15 @@ def test_attention_module_with_and_without_the_rotating_forward(monkeypatch):
     x = torch.randn(1, 2048, 256, device=DEV)                  # (N >= 2048: where the training forward takes the rotating kernel)
     res = {}
     for off in (False, True):
-        if off:
-            monkeypatch.setenv("OSUF_ATTN_NO_FWD_ROPE", "1")
-        else:
-            monkeypatch.delenv("OSUF_ATTN_NO_FWD_ROPE", raising=False)
         for p in att.parameters():
             p.grad = None
         xi = x.clone().requires_grad_()
-        with forced_compute_dtype(torch.bfloat16):
+        with ops.force(fwd_rope=not off), forced_compute_dtype(torch.bfloat16):
             y = att(xi)
             y.float().square().mean().backward()
         res[off] = [y.detach().float(), xi.grad.clone()] + [p.grad.clone() for p in att.parameters()]
     for a, b in zip(res[False], res[True]):
         assert torch.isfinite(a).all() and ((a.float() - b.float()).norm() / b.float().norm().clamp_min(1e-20)).item() < 2e-3
-    monkeypatch.delenv("OSUF_ATTN_NO_FWD_ROPE", raising=False)
     with torch.no_grad(), forced_compute_dtype(torch.bfloat16):
         y_inf = att(x)
     assert torch.equal(y_inf.float(), res[False][0])
