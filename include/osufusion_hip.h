@@ -611,6 +611,37 @@ int osuf_encode_signals(const int* map_hdr, int n_maps, const double* obj_f, con
                         const int* seg_i, const double* nodes, const int* map_idx, const long* start, const int* len, const int* flip,
                         int round_pos, float* out, double* pos_px, int B, int L, hipStream_t stream);
 
+/* ---- sampled signals -> hit objects (decode.hip)    replaces: the first forty lines of decode_beatmap in
+ *      osu_fusion/library/osu/data/decode.py (decode_flips / decode_extents of data/hit.py, one sample at a time on the host) and the
+ *      1,000 np.histogram calls of its calculate_timing_point.  Host yardstick: osufusion_amd/decode.py (object_table, np.histogram).
+ * osuf_decode_objects: x fp32 contiguous (B, 6, L), rows HIT, SUSTAIN, SLIDER, COMBO, CURSOR_X, CURSOR_Y; lengths (NULL: every sample
+ *      has L frames): int32 [B], only the first lengths[b] frames of sample b exist and frame lengths[b] - 1 is the end of its signal
+ *      (np.gradient's one-sided end); a lengths[b] outside [2, L] gives count[b] = 0.  Outputs, all [B][cap] but count [B]: for object
+ *      i < min(count[b], cap) of sample b, in ascending frame order,
+ *        frame        the onset: a frame where decode_flips of the HIT row (a hit channel is +1 where x > 0, else -1: 0.0, -0.0 and
+ *                     NaN give -1) has a peak, the middle of a two-frame plateau rounded down, the two end frames never;
+ *        sustain_end / slider_end  the last positive frame of the SUSTAIN / SLIDER run whose last non-positive frame is the onset
+ *                     (decode_extents), -1 where no run starts there or the run is still open at the end of the signal;
+ *        new_combo    1 where decode_flips of the COMBO row has this frame; a combo flip at a frame that is no onset sets it on the
+ *                     LAST object (the host's index -1);
+ *        px, py       fp64: rint((double(x) + 1) / 2 * 512) and (... * 384), ties to even, contraction off (np.round of the host).
+ *      count[b] is the true number of onsets even when it exceeds cap; no row at or past cap is written (the caller raises).  Rows
+ *      from count[b] on keep what they held.  One workgroup of 1024 lanes per sample; the four sign rows as bit masks in LDS (32 KiB),
+ *      the order from a popcount prefix sum.  No atomics, no allocation, no host sync, graph-capturable; the bits do not depend on
+ *      the rest of the batch.
+ *      OSUF_EINVAL, nothing launched: a NULL pointer other than lengths; B < 1; L < 2 or > 65536; cap < 1.
+ * osuf_tempo_scan: frame / count / cap as written above (count[b] is clamped to [0, cap]; a frame outside [0, L) is skipped);
+ *      frame_times fp64 [L] in ms; beat_len fp64 [B][C].  For every (b, c): the phases np.remainder(frame_times[frame], beat_len) (fmod,
+ *      plus beat_len once where the remainder's sign differs) go into numpy's 100 uniform bins over [0, beat_len] -- idx = (int)(phase /
+ *      beat_len * 100); 100 -> 99; one step down where phase < idx * (beat_len / 100); one step up where phase >= the next edge and
+ *      idx != 99 -- and best_count[b][c] = the largest bin count, best_bin[b][c] = the index of the first bin that holds it.  One wave
+ *      per candidate, integer LDS atomics only: order-independent.  No allocation, no host sync, graph-capturable.
+ *      OSUF_EINVAL, nothing launched: a NULL pointer; B < 1 or > 65535; C, L or cap < 1. ---- */
+int osuf_decode_objects(const float* x, const int* lengths, int B, int L, int cap, int* count, int* frame, int* sustain_end,
+                        int* slider_end, int* new_combo, double* px, double* py, hipStream_t stream);
+int osuf_tempo_scan(const int* frame, const int* count, int cap, const double* frame_times, int L, const double* beat_len, int B, int C,
+                    int* best_count, int* best_bin, hipStream_t stream);
+
 /* ---- DiT row kernels (dit.hip)    replaces: osu_fusion/modules/dit.py:14-15 modulate(LayerNorm(x)), 275-277 the audio statistics
  *      pooling (63-70 MultiHeadRMSNorm: osuf_joint_qknorm_fwd / _bwd below, one stream and G = H).  Rows [M][C], M = B * L, sample of row m = m / L; C % 8 == 0, C <= 2048; row strides multiples of 8
  *      elements, 16-B aligned pointers.  No atomics: every cross-row sum goes through per-workgroup partials added in a fixed order.

@@ -108,6 +108,8 @@ SIGNATURES = {
     "osuf_frame_rows": [P, L, I, I, P, L, P],
     "osuf_resample": [P, L, P, I, I, I, L, P, L, P],
     "osuf_encode_signals": [P, I, P, P, P, P, P, P, P, P, P, P, I, P, P, I, I, P],
+    "osuf_decode_objects": [P, P, I, I, I, P, P, P, P, P, P, P, P],
+    "osuf_tempo_scan": [P, P, I, P, I, P, I, I, P, P, P],
     "osuf_skinny_fwd": [I, P, L, P, P, P, L, I, I, I, I, I, P],
     "osuf_skinny_bwd": [I, P, L, P, L, P, L, P, P, L, P, P, I, I, I, I, I, I, P],
     "osuf_skinny_fwd_group": [I, P, L, P, I, I, I, I, I, P],

@@ -3,8 +3,12 @@ and of the two helpers it pulls in, ``data/hit.py:24-28,57-74`` (``decode_flips`
 ``data/fit_bezier.py`` (Schneider's curve fit as the reference adapts it from volkerp/fitCurves).
 
 This is the CPU post-processing that ``inference_gradio.py:149-163`` runs on every sample AFTER the GPU sampler returned
-(SURVEY section 8f row 4): a few thousand frames of 6 channels per song -- numpy on the host, as in the reference; nothing here is
-on the timed path and nothing here needs the GPU.  The reference evaluates Bezier points and arc lengths through the ``bezier``
+(SURVEY section 8f row 4), numpy on the host as in the reference, one sample per call.  It is the yardstick of the batched path,
+``decode_gpu.decode_beatmaps``, which builds the object tables and scans the tempo candidates on the GPU and calls ``table_to_text``
+below for the rest.  Measured on an MI355X host (profiles/decode.md): a loop of 16 calls at L = 8192 takes 251 ms at the object density
+of the golden maps (76 ms of it in ``object_table``'s frame loops, 171 ms in the slider fits) and 539 ms on dense onset trains (441 ms in
+the 1,001 ``np.histogram`` calls per sample) -- as long as 2M at 16 steps takes to draw those samples; the batched path takes 177 ms and
+23 ms.  The reference evaluates Bezier points and arc lengths through the ``bezier``
 package (absent from this image, so the reference module cannot even be imported here: **parity unpinned**, the reference holds no
 decoded fixtures either); the same quantities are computed below from their definitions -- de Casteljau / Bernstein evaluation,
 and the arc length by composite 16-point Gauss-Legendre quadrature of |B'(t)| (agrees with adaptive quadrature to ~1e-12 on
@@ -219,12 +223,10 @@ def get_timings(hit_times: np.ndarray, beat_length: float) -> Tuple[bool, Timing
     return True, TimingPoint(float(edges[int(np.argmax(hist))]), beat_length, 4)
 
 
-def calculate_timing_point(hit_times: np.ndarray, allow_beat_snap: bool, verbose: bool = True) -> Tuple[bool, TimingPoint]:
-    """Tempo from the autocorrelation of the inter-onset intervals, refined by a 1,000-point scan of +-5 % for the tempo whose
-    phase histogram is the most peaked (decode.py:89-121); (False, 200 BPM at 0 ms) when snapping is off or no lag qualifies."""
-    fallback = (False, TimingPoint(0, 60000 / 200, 4))
-    if not allow_beat_snap:
-        return fallback
+def tempo_candidates(hit_times: np.ndarray, verbose: bool = True) -> Optional[np.ndarray]:
+    """The first half of calculate_timing_point: the lag of the highest qualifying autocorrelation peak of the inter-onset intervals ->
+    the 1,000 tempi (BPM, fp64) within +-5 % of it, or None when no lag qualifies.  Stays on the host in both decode paths: it is a few
+    thousand fp64 products whose summation order decides which peak wins."""
     gaps = np.diff(np.asarray(hit_times, dtype=np.float64))
     corr = np.correlate(gaps, gaps, mode="full")[len(gaps) - 1:] if len(gaps) else np.zeros(0)
     periods = 60000.0 / np.arange(MIN_BPM, MAX_BPM + 1)
@@ -233,10 +235,23 @@ def calculate_timing_point(hit_times: np.ndarray, allow_beat_snap: bool, verbose
     if len(cand) == 0:
         if verbose:
             print("Warning: no valid BPM found within the range, disabling beat snap")
-        return fallback
+        return None
     lag = cand[int(np.argmax(corr[cand]))]
     bpm0 = 60000.0 / lag
-    scan = np.linspace(bpm0 * 0.95, bpm0 * 1.05, 1000)
+    return np.linspace(bpm0 * 0.95, bpm0 * 1.05, 1000)
+
+
+TIMING_FALLBACK = (False, TimingPoint(0, 60000 / 200, 4))         # snapping off, or no tempo found: 200 BPM at 0 ms, nothing snapped
+
+
+def calculate_timing_point(hit_times: np.ndarray, allow_beat_snap: bool, verbose: bool = True) -> Tuple[bool, TimingPoint]:
+    """Tempo from the autocorrelation of the inter-onset intervals, refined by a 1,000-point scan of +-5 % for the tempo whose
+    phase histogram is the most peaked (decode.py:89-121); (False, 200 BPM at 0 ms) when snapping is off or no lag qualifies."""
+    if not allow_beat_snap:
+        return TIMING_FALLBACK
+    scan = tempo_candidates(hit_times, verbose)
+    if scan is None:
+        return TIMING_FALLBACK
     score = [np.histogram(np.asarray(hit_times) % (60000.0 / b), bins=100, range=(0, 60000.0 / b))[0].max() for b in scan]
     return get_timings(hit_times, 60000.0 / scan[int(np.argmax(score))])
 
@@ -288,17 +303,24 @@ def _osu_text(meta: Metadata, timing_points: Sequence[str], hit_objects: Sequenc
     return "\n".join(out)
 
 
-def decode_beatmap(metadata: Metadata, encoded_beatmap: np.ndarray, frame_times: np.ndarray, bpm: Optional[float],
-                   allow_beat_snap: bool = True, verbose: bool = True) -> str:
-    """decode.py:133-237.  encoded_beatmap: (6, L) sample of the diffusion model (any real values: the four hit channels are
-    discretised by sign), frame_times: (L,) milliseconds.  Returns the text of an ``.osu`` file (format v14)."""
-    enc = np.asarray(encoded_beatmap, dtype=np.float64)
-    frame_times = np.asarray(frame_times)
+class HostTable(NamedTuple):
+    """One sample's hit objects in ascending frame order, before any timing: what decode_beatmap reads off the signal, and one row of
+    decode_gpu.ObjectTable copied back."""
+    frame: List[int]                                                 # onset frames
+    sustain_end: List[int]                                           # last positive SUSTAIN frame of a run starting at the onset, else -1
+    slider_end: List[int]                                            # the same for SLIDER
+    new_combo: List[bool]
+    px: np.ndarray                                                   # cursor at the onset in whole osu!pixels, (count,) int
+    py: np.ndarray
+
+
+def object_table(enc: np.ndarray) -> HostTable:
+    """decode.py:135-172 on the host: enc (6, L) fp64 -> the objects.  (The yardstick of osuf_decode_objects.)"""
     hit_sig = np.where(enc[[HIT, SUSTAIN, SLIDER, COMBO]] > 0, 1.0, -1.0)
     cursor = (enc[[CURSOR_X, CURSOR_Y]] + 1.0) / 2.0 * np.array([[PLAYFIELD[0]], [PLAYFIELD[1]]])
 
     onsets = decode_flips(hit_sig[0])
-    onset_of_frame = np.full(len(frame_times), -1, dtype=int)
+    onset_of_frame = np.full(enc.shape[1], -1, dtype=int)
     for i, frame in enumerate(onsets):
         onset_of_frame[frame] = i
     new_combo = [False] * len(onsets)
@@ -312,14 +334,20 @@ def decode_beatmap(metadata: Metadata, encoded_beatmap: np.ndarray, frame_times:
                 ends[onset_of_frame[start]] = end
         return ends
 
-    sustain_end, slider_end = run_ends(1), run_ends(2)
-    hit_times = frame_times[onsets]
-    snap, tp = get_timings(hit_times, 60000 / bpm) if bpm is not None else calculate_timing_point(hit_times, allow_beat_snap, verbose)
+    px, py = np.round(cursor[:, onsets]).astype(int)
+    return HostTable(onsets, run_ends(1), run_ends(2), new_combo, px, py)
+
+
+def table_to_text(metadata: Metadata, table: HostTable, cursor: np.ndarray, frame_times: np.ndarray, snap: bool, tp: TimingPoint,
+                  verbose: bool = True, slider_fit=None) -> str:
+    """decode.py:174-237: the objects, the cursor in (unrounded) osu!pixels (2, L) for the slider fits and the timing -> ``.osu`` text.
+    The tail of decode_beatmap, shared with decode_gpu.decode_beatmaps.  slider_fit (default slider_decoder): a stand-in with the same
+    signature, for timing the fits apart from the rest."""
+    slider_fit = slider_decoder if slider_fit is None else slider_fit
     slider_vel_base = SLIDER_MULT * 100 / tp.beat_length
     timing_lines = [f"{tp.t},{tp.beat_length},{tp.meter},0,0,50,1,0"]
     objects: List[str] = []
-    for frame, combo, s_end, l_end in zip(onsets, new_combo, sustain_end, slider_end):
-        x, y = np.round(cursor[:, frame]).astype(int)
+    for frame, combo, s_end, l_end, x, y in zip(table.frame, table.new_combo, table.sustain_end, table.slider_end, table.px, table.py):
         t, u = frame_times[frame], frame_times[s_end]
         combo_bit = 4 if combo else 0
         if snap:
@@ -335,7 +363,7 @@ def decode_beatmap(metadata: Metadata, encoded_beatmap: np.ndarray, frame_times:
             objects.append(circle)
             continue
         slides = max(1, round((s_end - frame) / (l_end - frame)))
-        length, ctrl = slider_decoder(cursor, frame, s_end, slides)
+        length, ctrl = slider_fit(cursor, frame, s_end, slides)
         if length == 0:
             objects.append(circle)                                  # (the reference then still emits the slider line below)
         x1, y1 = ctrl[0]
@@ -347,3 +375,16 @@ def decode_beatmap(metadata: Metadata, encoded_beatmap: np.ndarray, frame_times:
             print(f"Warning: slider velocity {ratio} is out of bounds, slider will not be good")
         timing_lines.append(f"{t},{-100 / ratio},4,0,0,50,0,0")
     return _osu_text(metadata, timing_lines, objects)
+
+
+def decode_beatmap(metadata: Metadata, encoded_beatmap: np.ndarray, frame_times: np.ndarray, bpm: Optional[float],
+                   allow_beat_snap: bool = True, verbose: bool = True) -> str:
+    """decode.py:133-237.  encoded_beatmap: (6, L) sample of the diffusion model (any real values: the four hit channels are
+    discretised by sign), frame_times: (L,) milliseconds.  Returns the text of an ``.osu`` file (format v14)."""
+    enc = np.asarray(encoded_beatmap, dtype=np.float64)
+    frame_times = np.asarray(frame_times)
+    table = object_table(enc)
+    cursor = (enc[[CURSOR_X, CURSOR_Y]] + 1.0) / 2.0 * np.array([[PLAYFIELD[0]], [PLAYFIELD[1]]])
+    hit_times = frame_times[table.frame]
+    snap, tp = get_timings(hit_times, 60000 / bpm) if bpm is not None else calculate_timing_point(hit_times, allow_beat_snap, verbose)
+    return table_to_text(metadata, table, cursor, frame_times, snap, tp, verbose)

@@ -1145,3 +1145,18 @@ def log_vqt(wave_pad: torch.Tensor, bank: torch.Tensor, scale: torch.Tensor, hop
     assert out.dtype == torch.float32 and out.shape == (bins, frames) and out.stride(1) == 1
     call("osuf_log_vqt", _p(wave_pad), wave_pad.numel(), _p(bank), K, bins, hop, _p(scale), eps, _p(ws), _p(out), out.stride(0), frames, _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# sampled signals -> hit objects (decode.hip); the allocating wrappers live in decode_gpu.py, as encode.py's do
+# ---------------------------------------------------------------------------------------------------------
+def decode_objects(x: torch.Tensor, lengths: Optional[torch.Tensor] = None, cap: Optional[int] = None):
+    """-> decode_gpu.ObjectTable: onsets, run ends, new combos and cursor pixels of every sample of x (B, 6, L), one launch."""
+    from . import decode_gpu
+    return decode_gpu.decode_objects(x, lengths, cap)
+
+
+def tempo_scan(table, frame_times: torch.Tensor, beat_len: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (best_count, best_bin) int32 (B, C): the fullest of the 100 phase bins per candidate beat length, one launch."""
+    from . import decode_gpu
+    return decode_gpu.tempo_scan(table, frame_times, beat_len)

@@ -71,3 +71,24 @@ def synth_inputs(tag: str, batch: int, length: int, dim_x: int = 6, dim_a: int =
     u = sum(hash_uniform(f"{tag}/n{i}", batch * dim_x * length) for i in range(4))
     noise = ((u - 2.0) * np.sqrt(3.0)).astype(np.float32).reshape(batch, dim_x, length)
     return x, a, c, t, noise
+
+
+def onset_train(length: int, seed: int, keep: float = 0.6, bpm: float = 180.0) -> np.ndarray:
+    """A synthetic sample (6, length) fp32 with circles only: onsets on a random `keep` share of the quarter-beat grid of `bpm`, a new
+    combo at every fifth or so, a smooth cursor.  Dense enough (about 240 onsets per 4096 frames at the defaults) for
+    decode.tempo_candidates to find a lag, which the golden .osu fixtures, tiled or not, are not."""
+    rng = np.random.default_rng(seed)
+    ft = np.arange(length) * 176 / 22050 * 1000.0
+    ticks = np.arange(200.0, ft[-2], 60000 / bpm / 4)
+    ticks = ticks[rng.random(len(ticks)) < keep]
+    frames = np.unique(np.searchsorted(ft, ticks))
+    frames = frames[(frames > 2) & (frames < length - 2)]
+    frames = frames[np.concatenate([[True], np.diff(frames) > 2])]
+    flips = np.zeros(length, int)
+    flips[frames] = 1
+    x = -np.ones((6, length), dtype=np.float32)
+    x[0] = np.where(np.cumsum(flips) % 2 == 1, 0.8, -0.8)
+    x[3] = np.where(np.cumsum(flips * (rng.random(length) < 0.2)) % 2 == 1, 0.8, -0.8)
+    x[4] = np.sin(np.arange(length) / 50.0) * 0.8
+    x[5] = np.cos(np.arange(length) / 70.0) * 0.8
+    return x
