@@ -650,7 +650,13 @@ int osuf_tempo_scan(const int* frame, const int* count, int cap, const double* f
  * osuf_adaln_bwd: dx = dres + LN-backward(dy * (1 + scale[b])) (dres may be NULL); stores dshift[b][c] = sum_n dy at dmod[b * ldd + c]
  *      and dscale[b][c] = sum_n dy * xhat at dmod[b * ldd + off2 + c] (e.g. column blocks of the (B, 6C) modulation gradient, ldd = 6C);
  *      B = M / L <= 65535; workspace: osuf_adaln_bwd_workspace_bytes(M, C, L) bytes.
- * osuf_stat_pool: a fp32 (B, C, L) contiguous -> out (B, 2C) = [mean_l | unbiased std_l]. ---- */
+ * osuf_stat_pool: a fp32 (B, C, L) contiguous -> out (B, 2C) = [mean_l | unbiased std_l].
+ * OSUF_EINVAL, nothing launched (as the elementwise contract above): C outside 8 .. 2048 or no multiple of 8; M, L < 1 or M % L; a row
+ *      stride that is no multiple of 8 (ldm: of 4) or below C -- ldx, ldo, lddy, lddx, ldm, ldd, and ldr when dres is given; a NULL
+ *      x / out / shift / scale (forward; mr may be NULL: mean and rstd are then not kept), a NULL dy / x / dx / scale / mr / dmod /
+ *      workspace (backward); x, out, dy, dx, dres, shift or scale off a 16-byte boundary; B > 65535 (backward, osuf_stat_pool); a
+ *      workspace smaller than osuf_adaln_bwd_workspace_bytes; osuf_stat_pool's NULL a / out or a size < 1.  OSUF_EUNSUPPORTED: an
+ *      unknown dtype code.  Checked case by case, with the joint entry points below, in tests/test_dit_rows_gpu.py. ---- */
 int osuf_adaln_fwd(int dtype, const void* x, long ldx, void* out, long ldo, float* mr, const float* shift, const float* scale, long ldm,
                    int M, int C, int L, float eps, hipStream_t stream);
 long osuf_adaln_bwd_workspace_bytes(int M, int C, int L);

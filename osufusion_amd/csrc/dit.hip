@@ -168,6 +168,7 @@ extern "C" int osuf_adaln_fwd(int dtype, const void* x, long ldx, void* out, lon
                               int M, int C, int L, float eps, hipStream_t stream) {
   if (bad_c(C) || M <= 0 || L <= 0 || M % L || ldx % 8 || ldo % 8 || ldm % 4 || !al16(x) || !al16(out) || !al16(shift) || !al16(scale))
     return OSUF_EINVAL;
+  if (!x || !out || !shift || !scale || ldx < C || ldo < C || ldm < C) return OSUF_EINVAL;       // mr may be NULL: mean and rstd are then not kept
   const int J = chunk_iters(C / 8);
   long blocks = ((long)M + 3) / 4;
   if (blocks > 4096) blocks = 4096;
@@ -191,6 +192,7 @@ extern "C" int osuf_adaln_bwd(int dtype, const void* dy, long lddy, const void* 
   if (bad_c(C) || M <= 0 || L <= 0 || M % L || M / L > 65535 || lddy % 8 || ldx % 8 || lddx % 8 || (dres && ldr % 8) || ldm % 4 || !mr || !dmod || !workspace)
     return OSUF_EINVAL;
   if (!al16(dy) || !al16(x) || !al16(dx) || (dres && !al16(dres)) || !al16(scale)) return OSUF_EINVAL;
+  if (!dy || !x || !dx || !scale || lddy < C || ldx < C || lddx < C || (dres && ldr < C) || ldm < C || ldd < C) return OSUF_EINVAL;
   if (workspace_bytes < osuf_adaln_bwd_workspace_bytes(M, C, L)) return OSUF_EINVAL;
   const int B = M / L, J = chunk_iters(C / 8), nblk = adaln_bwd_blocks(B, L);
   const size_t lds = (size_t)8 * C * sizeof(float);
