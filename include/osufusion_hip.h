@@ -12,7 +12,7 @@
  *     table forces the few launcher branches that have no such argument, so that tests can compare one path bit for bit with
  *     another and A/B runs can time it.  It is a test and A/B aid, not configuration: every slot starts at its default, the
  *     launchers read it on every call, and nothing is read from the environment;
- *   - return 0 on success, <0 for an argument error (-1 invalid, -2 unsupported), >0 = hipError_t of the launch;
+ *   - return 0 on success, <0 for an argument error (OSUF_EINVAL -1 invalid, OSUF_EUNSUPPORTED -2 unsupported), >0 = hipError_t of the launch;
  *   - activations are channels-last rows [B*L][C] ("rows"), C contiguous, row stride `ld*` in ELEMENTS;
  *   - dtype: 0 = fp32 storage (exact-f32 MFMA), 1 = bf16 storage (bf16 MFMA, fp32 accumulate);
  *   - all row strides / channel counts must be multiples of 8 elements, pointers 16-byte aligned.
@@ -25,6 +25,11 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+/* status of every `int` entry point: OSUF_OK, one of the two argument errors, or the (positive) hipError_t of the launch */
+#define OSUF_OK 0
+#define OSUF_EINVAL (-1)
+#define OSUF_EUNSUPPORTED (-2)
 
 #define OSUF_DT_F32 0
 #define OSUF_DT_BF16 1
@@ -487,8 +492,6 @@ int osuf_pack_weight(const float* w, int O, int I, int k, int out_dtype, void* F
  * descs: DEVICE array of n descriptors, one per weight, fields as osuf_pack_weight's arguments; block0 = running sum of
  * ceil(O/32) * ceil(I/32) over the preceding descriptors (descs[0].block0 == 0), total_blocks = that sum over all n.
  * All destinations share out_dtype.  The table is only read: it can be built once and reused while the pointers stay put. */
-#ifndef OSUF_PACK_DESC_DEFINED
-#define OSUF_PACK_DESC_DEFINED
 typedef struct osuf_pack_desc {
   const float* w;
   void* F;
@@ -497,7 +500,6 @@ typedef struct osuf_pack_desc {
   int O, I, k, dkind;
   int block0, reserved;
 } osuf_pack_desc;                                   /* 80 bytes */
-#endif
 int osuf_pack_weight_group(const osuf_pack_desc* descs, int n, int total_blocks, int out_dtype, hipStream_t stream);
 
 /* LoRA / DoRA adapters folded into an effective weight (reference: osu_fusion/modules/lora_layers.py:16-26 get_weight_norm,
@@ -542,8 +544,6 @@ int osuf_skinny_bwd(int mode, const float* dy, long lddy, const float* y, long l
  *   osuf_skinny_dx_group : dx = in_act'(x) * sum_i dy_i W_i (dx overwritten);      block0 = running sum of ceil(N_i / 512).
  * K and every N_i multiples of 8, rows 16-byte aligned (OSUF_EINVAL otherwise: use the per-linear entry points).  The weight
  * gradients stay per linear (osuf_skinny_bwd with dx == NULL), so each is complete as soon as its block's backward has run. */
-#ifndef OSUF_LINEAR_DESC_DEFINED
-#define OSUF_LINEAR_DESC_DEFINED
 typedef struct osuf_linear_desc {
   const float* W;          /* (N, K) fp32 master weight */
   const float* bias;       /* (N) or NULL */
@@ -552,7 +552,6 @@ typedef struct osuf_linear_desc {
   long ldy, lddy;
   int N, block0;
 } osuf_linear_desc;                                 /* 56 bytes */
-#endif
 int osuf_skinny_fwd_group(int mode, const float* x, long ldx, const osuf_linear_desc* descs, int n, int total_blocks, int M, int K,
                           int in_act, hipStream_t stream);
 int osuf_skinny_dx_group(int mode, const osuf_linear_desc* descs, int n, int total_slices, const float* x, long ldx, float* dx, long lddx,

@@ -11,7 +11,8 @@ from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
 SOURCES = ["gemm.hip", "norm.hip", "attn.hip", "elementwise.hip", "sampling.hip", "skinny.hip", "audio.hip", "dit.hip", "encode.hip", "decode.hip"]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
+HEADER = HERE.parent.parent / "include" / "osufusion_hip.h"      # the C ABI: common.hpp includes it, so every definition meets its declaration
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", f"-I{HEADER.parent}"]
 LIB = HERE / "libosuf_hip.so"
 
 
@@ -32,7 +33,8 @@ def _stale() -> bool:
     if not LIB.exists():
         return True
     t = LIB.stat().st_mtime
-    deps = [HERE / s for s in SOURCES] + [HERE / "common.hpp", HERE / "attn_generic.hpp", HERE / "attn_bwd512_asm.inc", HERE / "attn_bwd512qs_asm.inc", Path(__file__)]
+    deps = [HERE / s for s in SOURCES] + [HERE / "common.hpp", HERE / "attn_generic.hpp", HERE / "attn_bwd512_asm.inc", HERE / "attn_bwd512qs_asm.inc",
+                                          HEADER, Path(__file__)]
     return any(d.stat().st_mtime > t for d in deps)
 
 

@@ -4,48 +4,11 @@
 #include <stdint.h>
 #include <atomic>
 
-// descriptor of osuf_pack_weight_group (include/osufusion_hip.h holds the same definition for callers)
-#ifndef OSUF_PACK_DESC_DEFINED
-#define OSUF_PACK_DESC_DEFINED
-typedef struct osuf_pack_desc {
-  const float* w;
-  void* F;
-  void* D;
-  long f_ld, f_tapstride, d_ld, d_tapstride;
-  int O, I, k, dkind;
-  int block0, reserved;
-} osuf_pack_desc;
-#endif
+// The C ABI: every extern "C" definition in csrc/ is compiled against its declaration, and the OSUF_* codes, the descriptor structs and the
+// knob enumeration are defined there alone.
+#include "osufusion_hip.h"                                 // include/ of the repository: -I in build.py
 static_assert(sizeof(osuf_pack_desc) == 80, "osuf_pack_desc is part of the C ABI");
-// descriptor of the osuf_skinny_*_group entry points (same definition in include/osufusion_hip.h)
-#ifndef OSUF_LINEAR_DESC_DEFINED
-#define OSUF_LINEAR_DESC_DEFINED
-typedef struct osuf_linear_desc {
-  const float* W;          /* (N, K) fp32 master weight */
-  const float* bias;       /* (N) or NULL */
-  float* y;                /* forward output rows, row stride ldy */
-  const float* dy;         /* backward: gradient of y, row stride lddy */
-  long ldy, lddy;
-  int N, block0;
-} osuf_linear_desc;                                 /* 56 bytes */
-#endif
 static_assert(sizeof(osuf_linear_desc) == 56, "osuf_linear_desc is part of the C ABI");
-
-#define OSUF_DT_F32 0
-#define OSUF_DT_BF16 1
-#define OSUF_DT_F32X3 2   /* GEMM entry points only: fp32 storage, products as three bf16 MFMAs on split (hi + lo) operands */
-// kernel choice of the attention-backward entry points (per call; nothing is read from the environment)
-#define OSUF_ATTN_AUTO 0
-#define OSUF_ATTN_PLAIN 1
-#define OSUF_ATTN_PIPE 2
-// how the fused attention backward sums dQ over its 256-key workgroups
-#define OSUF_DQ_ATOMIC 0          /* fp32 atomics; the sweep (256 or 512 keys per workgroup) is picked by shape */
-#define OSUF_DQ_SLABS 1
-#define OSUF_DQ_ATOMIC_256 2      /* force the 8-wave, 256-key sweep */
-#define OSUF_DQ_ATOMIC_512 3      /* force the 4-wave, 512-key sweep (N % 32 == 0) */
-                                  /* (4: a timing-only build of the 512-key sweep, since removed; refused) */
-#define OSUF_DQ_ATOMIC_512A 5     /* the 512-key sweep with the generated, hand-placed loop (attn_bwd512_asm.inc) */
-#define OSUF_DQ_PREZEROED 0x100   /* flag: the dQ accumulator was zero-filled by osuf_mqa_fwd_zdq (no memset in the backward entry point) */
 
 typedef uint16_t bf16_t;                                   // raw bf16 bits in HBM
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -166,11 +129,7 @@ __device__ __forceinline__ float group_max_dyn(float v, int width) {
 __device__ __forceinline__ void atomic_add_f64(double* p, double v) { unsafeAtomicAdd(p, v); }
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
 
-// C-ABI status: 0 ok, negative = argument error, positive = hipError_t
-#define OSUF_OK 0
-#define OSUF_EINVAL (-1)
-#define OSUF_EUNSUPPORTED (-2)
-
+// C-ABI status: OSUF_OK, negative = argument error, positive = hipError_t
 static inline int osuf_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? OSUF_OK : (int)e;
@@ -178,9 +137,6 @@ static inline int osuf_launch_status() {
 
 // The override table (include/osufusion_hip.h: osuf_override_set / osuf_override_get): one slot per launcher branch a test or an A/B
 // run can force.  One definition for every translation unit; the launchers read it on every call.
-enum { OSUF_KNOB_GEMM_BIG_MIN_TILES, OSUF_KNOB_GEMM_NO8P, OSUF_KNOB_GEMM_NOHALO, OSUF_KNOB_WGRAD_F32_PARTIALS, OSUF_KNOB_ATTN_FWD_NOWHOLE,
-       OSUF_KNOB_ATTN_FWD_NOQSK, OSUF_KNOB_COUNT };
-#define OSUF_KNOB_DEFAULT (-1)
 inline std::atomic<int> osuf_knobs[OSUF_KNOB_COUNT] = {{OSUF_KNOB_DEFAULT}, {OSUF_KNOB_DEFAULT}, {OSUF_KNOB_DEFAULT},
                                                        {OSUF_KNOB_DEFAULT}, {OSUF_KNOB_DEFAULT}, {OSUF_KNOB_DEFAULT}};
 static inline int osuf_knob(int k) { return osuf_knobs[k].load(std::memory_order_relaxed); }

@@ -85,9 +85,6 @@ __global__ __launch_bounds__(256) void ct_schedule_kernel(const float* t, const 
 // noise buffer: the mean, whatever noise holds.  The kernel is ct_step_kernel below, which the solvers share.
 // OBJ = what the network predicts (OSUF_CT_OBJ_*): the start prediction is (x - sigma p) / max(alpha, 1e-8) for noise, p itself for x_start and
 // alpha x - sigma p for v.  THR: the sample's dynamic threshold s (>= 1, osuf_ct_x0_quantile) replaces the static clamp: clamp(x0, -s, s) / s.
-#define OSUF_CT_OBJ_NOISE 0                                  // as in include/osufusion_hip.h
-#define OSUF_CT_OBJ_X_START 1
-#define OSUF_CT_OBJ_V 2
 template <int OBJ>
 __device__ inline float ct_start(float x, float p, const float* k) {
   if (OBJ == 1) return p;
@@ -121,8 +118,6 @@ __device__ inline float ct_start_clamped(float x, float p, const float* k, const
 // (rows[i][b][13], so that osuf_ct_x0_quantile and the step kernels index a step's rows by sample as they do osuf_ct_schedule's), and
 // fac[i][4] = k_x, k_0, k_p, gain, one per step.  Row columns 0-11 by ct_schedule_kernel's expressions on (ls[i], ls[i + 1]); column 12, the
 // ancestral gain, is zero on the last step (where ct_schedule_kernel has t_next = 0): a row is a valid osuf_ct_step_ex row too.
-#define OSUF_CT_SAMPLER_DDIM 0                               // as in include/osufusion_hip.h
-#define OSUF_CT_SAMPLER_DPMPP_2M 1
 __global__ __launch_bounds__(256) void ct_solver_schedule_kernel(const float* ls_grid, int S, int sampler, float eta, float* rows, float* fac,
                                                                  int B) {
 #pragma clang fp contract(off)

@@ -52,7 +52,7 @@ def ct_step(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Tensor], c
 
 
 # what the network predicts (include/osufusion_hip.h: OSUF_CT_OBJ_*)
-OBJECTIVES = {"noise": 0, "x_start": 1, "v": 2}
+OBJECTIVES = {name: _lib.CONSTS["OSUF_CT_OBJ_" + name.upper()] for name in ("noise", "x_start", "v")}
 
 
 def objective_code(objective) -> int:
@@ -103,7 +103,7 @@ def ct_x0_quantile(x: torch.Tensor, cond: torch.Tensor, null: Optional[torch.Ten
 
 
 # solvers on a log-SNR grid (include/osufusion_hip.h: OSUF_CT_SAMPLER_*); "ddpm" is the ancestral path and has no code here
-SAMPLERS = {"ddim": 0, "dpmpp_2m": 1}
+SAMPLERS = {name: _lib.CONSTS["OSUF_CT_SAMPLER_" + name.upper()] for name in ("ddim", "dpmpp_2m")}
 FAC_K_X, FAC_K_0, FAC_K_P, FAC_GAIN = range(4)
 
 

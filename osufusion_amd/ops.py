@@ -14,7 +14,8 @@ import torch
 
 from . import _lib
 
-F32, BF16 = 0, 1
+_C = _lib.CONSTS           # the OSUF_* codes, from include/osufusion_hip.h
+F32, BF16 = _C["OSUF_DT_F32"], _C["OSUF_DT_BF16"]
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 
 
@@ -44,7 +45,7 @@ def dt_of(t: torch.Tensor) -> int:
     return _DT[t.dtype]
 
 
-F32X3 = 2                  # OSUF_DT_F32X3: fp32 storage, GEMM products as three bf16 MFMAs on split operands
+F32X3 = _C["OSUF_DT_F32X3"]  # fp32 storage, GEMM products as three bf16 MFMAs on split operands
 F32_MATMUL = "exact"       # how the fp32 compute mode multiplies: "exact" (v_mfma_f32_32x32x2_f32, a bitwise fmaf chain, 1/16 of the bf16
 #                            MFMA rate) or "x3" (a = a_hi + a_lo in bf16, three bf16 MFMAs: inputs kept to ~17 bits, 3/16 of the cost)
 
@@ -136,9 +137,11 @@ class one_launch_attention:
         return False
 
 
-# Forced paths (tests and A/B runs; not configuration).  The six launcher branches of the library are slots of its override table, in the order
-# of the OSUF_KNOB_* enumeration of include/osufusion_hip.h; the two choices made on this side of the C ABI are module state.
-_KNOBS = {"gemm_big": 0, "no8p": 1, "nohalo": 2, "wgrad_f32_partials": 3, "attn_fwd_nowhole": 4, "attn_fwd_noqsk": 5}
+# Forced paths (tests and A/B runs; not configuration).  The six launcher branches of the library are slots of its override table, named by
+# the OSUF_KNOB_* enumeration of include/osufusion_hip.h; the two choices made on this side of the C ABI are module state.
+_KNOBS = {name: _C["OSUF_KNOB_" + enumerator] for name, enumerator in (
+    ("gemm_big", "GEMM_BIG_MIN_TILES"), ("no8p", "GEMM_NO8P"), ("nohalo", "GEMM_NOHALO"), ("wgrad_f32_partials", "WGRAD_F32_PARTIALS"),
+    ("attn_fwd_nowhole", "ATTN_FWD_NOWHOLE"), ("attn_fwd_noqsk", "ATTN_FWD_NOQSK"))}
 _SWITCHES = {"zdq": True, "fwd_rope": True}
 
 
@@ -154,7 +157,7 @@ def _set_forced(name: str, value) -> None:
     if name in _SWITCHES:
         _SWITCHES[name] = True if value is None else bool(value)
     else:
-        _lib.check(_lib.load().osuf_override_set(_KNOBS[name], -1 if value is None else int(value)), "osuf_override_set")
+        _lib.check(_lib.load().osuf_override_set(_KNOBS[name], _C["OSUF_KNOB_DEFAULT"] if value is None else int(value)), "osuf_override_set")
 
 
 class force:
@@ -546,7 +549,7 @@ def rope_bwd(dqkv32: torch.Tensor, out_dtype: torch.dtype, cos, sin, N: int, n_r
     return out
 
 
-DQ_PREZEROED = 0x100                                             # OSUF_DQ_PREZEROED
+DQ_PREZEROED = _C["OSUF_DQ_PREZEROED"]
 
 
 def fused_bwd_workspace(B: int, N: int, H: int, D: int, out_dtype: torch.dtype, device, variant: Optional[int] = None, qsplit: int = 0):
@@ -621,10 +624,12 @@ def mqa_fwd_rope(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int
     return qkv_r, o, lse
 
 
-ATTN_AUTO, ATTN_PLAIN, ATTN_PIPE, ATTN_FUSED, ATTN_FUSED_SLABS = 0, 1, 2, 3, 4
+ATTN_AUTO, ATTN_PLAIN, ATTN_PIPE = _C["OSUF_ATTN_AUTO"], _C["OSUF_ATTN_PLAIN"], _C["OSUF_ATTN_PIPE"]
+ATTN_FUSED, ATTN_FUSED_SLABS = 3, 4     # from here on variants of this side of the C ABI: the fused sweep, by its dq_mode
 ATTN_FUSED256, ATTN_FUSED512 = 5, 6     # force the 256- / 512-key sweep of ATTN_FUSED (7 was a timing-only build, since removed)
 ATTN_FUSED512A = 8                                               # the 512-key sweep with the generated, hand-placed loop
-_FUSED_DQ_MODE = {ATTN_FUSED: 0, ATTN_FUSED_SLABS: 1, ATTN_FUSED256: 2, ATTN_FUSED512: 3, ATTN_FUSED512A: 5}      # OSUF_DQ_*
+_FUSED_DQ_MODE = {ATTN_FUSED: _C["OSUF_DQ_ATOMIC"], ATTN_FUSED_SLABS: _C["OSUF_DQ_SLABS"], ATTN_FUSED256: _C["OSUF_DQ_ATOMIC_256"],
+                  ATTN_FUSED512: _C["OSUF_DQ_ATOMIC_512"], ATTN_FUSED512A: _C["OSUF_DQ_ATOMIC_512A"]}
 # What AttentionFn.backward asks for: ATTN_FUSED = one key-stationary sweep, dQ by fp32 atomics (fastest at every UNet shape, measured
 # round 2); ATTN_FUSED_SLABS = the same sweep with a fixed-order dQ sum (bit-reproducible); ATTN_AUTO = the dQ + dK/dV kernel pair.
 ATTN_BWD_DEFAULT = ATTN_FUSED

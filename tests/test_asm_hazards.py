@@ -20,6 +20,7 @@ def test_asm_mfma_kernels_have_no_unpadded_hazards(tmp_path):
     src = ROOT / "osufusion_amd" / "csrc"
     for f in ("attn.hip", "attn_generic.hpp", "common.hpp", "attn_bwd512_asm.inc", "attn_bwd512qs_asm.inc"):
         shutil.copy(src / f, tmp_path / f)
+    shutil.copy(ROOT / "include" / "osufusion_hip.h", tmp_path / "osufusion_hip.h")      # common.hpp compiles against the C ABI header
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-save-temps", "-c", "attn.hip",
                         "-o", "attn.o"], cwd=tmp_path, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]

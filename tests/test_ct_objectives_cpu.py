@@ -2,8 +2,6 @@
 (tests/ct_objectives_oracle.py; the two fp64 algebra tests check the yardstick against itself), GaussianDiffusionContinuousTimes.loss_weight / .dynamic_threshold (plain torch, any device), the host
 side of the quantile (ct.quantile_rank), the constructor's validation and the C ABI of the new entry points."""
 import inspect
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -15,7 +13,6 @@ from osufusion_amd.modules import GaussianDiffusionContinuousTimes
 from tests import ct_objectives_oracle as CO
 from tests import scheduler_oracle as SO
 
-ROOT = Path(__file__).resolve().parent.parent
 SMALL = {"mmdit": dict(dim_h=32, depth=2, attn_heads=2, attn_kv_heads=1, attn_dim_head=16), "dit": dict(dim_h=96, depth=2, attn_heads=6, attn_dim_head=16)}
 TIMES = torch.tensor([1e-3, 0.25, 0.5, 0.75, 0.999], dtype=torch.float64)
 
@@ -162,7 +159,7 @@ def test_new_methods_refuse_cpu_tensors():
 
 
 def test_capi_new_entry_points_are_declared_and_bound():
-    src = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "osufusion_hip.h").read_text(), flags=re.S)
+    decls, consts = _lib.read_header()
     want = {
         "osuf_ct_step_ex": ["x", "cond", "nullp", "cond_scale", "coef", "noise", "objective", "s", "s_ld", "out", "B", "per_sample", "stream"],
         "osuf_ct_x0_quantile": ["x", "cond", "nullp", "cond_scale", "coef", "objective", "k_lo", "frac", "out", "workspace", "B", "per_sample", "stream"],
@@ -170,13 +167,12 @@ def test_capi_new_entry_points_are_declared_and_bound():
         "osuf_mse_w": ["pred", "target", "orig_len", "w", "grad", "loss_sum", "B", "Dch", "L", "stream"],
     }
     for name, names in want.items():
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-        assert decl, f"{name} is not declared in include/osufusion_hip.h"
-        assert [p.strip().split()[-1].lstrip("*") for p in decl.group(1).split(",")] == names
+        assert name in decls, f"{name} is not declared in include/osufusion_hip.h"
+        assert decls[name][0] == "int" and [p.split()[-1].lstrip("*") for p in decls[name][1]] == names
         assert len(_lib.SIGNATURES[name]) == len(names)
         assert hasattr(_lib.load(), name)
     for j, obj in enumerate(("NOISE", "X_START", "V")):
-        assert re.search(rf"#define OSUF_CT_OBJ_{obj} {j}\b", src)
+        assert consts[f"OSUF_CT_OBJ_{obj}"] == j
     lib = _lib.load()
     assert lib.osuf_ct_x0_quantile_workspace_bytes(3) == 3 * (5 * 2048 + 8) * 4 and lib.osuf_ct_x0_quantile_workspace_bytes(0) == 0
     from osufusion_amd import ops

@@ -1,7 +1,6 @@
 """The host side of the batched decode (osufusion_amd/decode_gpu.py, csrc/decode.hip): the ABI surface, numpy's uniform-bin rule as the
 tempo-scan kernel restates it, and the table -> text helper that both decode paths share.  The kernels themselves are compared with the
 host functions in tests/test_decode_gpu.py."""
-import re
 from pathlib import Path
 
 import numpy as np
@@ -22,11 +21,10 @@ META = D.Metadata("audio.mp3", "Song", "Artist", "Version", cs=4.0, ar=9.0, od=8
 
 def test_abi_surface():
     P, I = _lib.P, _lib.I
-    header = (ROOT / "include" / "osufusion_hip.h").read_text()
+    decls = _lib.read_header()[0]
     for name, n_args in (("osuf_decode_objects", 13), ("osuf_tempo_scan", 11)):
-        m = re.search(r"\bint " + name + r"\(([^;]*)\);", header)
-        assert m, f"{name} is not declared in include/osufusion_hip.h"
-        assert len(m.group(1).split(",")) == n_args == len(_lib.SIGNATURES[name])
+        assert name in decls and decls[name][0] == "int", f"{name} is not declared in include/osufusion_hip.h"
+        assert len(decls[name][1]) == n_args == len(_lib.SIGNATURES[name])
     assert _lib.SIGNATURES["osuf_decode_objects"] == [P, P, I, I, I, P, P, P, P, P, P, P, P]
     assert _lib.SIGNATURES["osuf_tempo_scan"] == [P, P, I, P, I, P, I, I, P, P, P]
     assert "decode.hip" in build.SOURCES

@@ -2,7 +2,6 @@
 the fp64 oracle (tests/encode_oracle.py) against the reference's recorded output (tests/golden/encode_cases.npz), the device tables of
 osufusion_amd/encode.py walked on the host, the C ABI of osuf_encode_signals, and the round trip through decode.decode_beatmap."""
 import math
-import re
 from ctypes import c_int, c_void_p
 from pathlib import Path
 
@@ -301,11 +300,10 @@ def test_merge_intervals():
 
 # ---- C ABI --------------------------------------------------------------------------------------------------------------------------------
 def test_capi_encode_signals_is_declared_bound_and_exported():
-    src = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "osufusion_hip.h").read_text(), flags=re.S)
-    decl = re.search(r"\bint\s+osuf_encode_signals\s*\(([^)]*)\)\s*;", src)
-    assert decl, "osuf_encode_signals is not declared in include/osufusion_hip.h"
-    names = [p.strip().split()[-1].lstrip("*") for p in decl.group(1).split(",")]
-    assert names == ["map_hdr", "n_maps", "obj_f", "obj_i", "ivl", "seg_cum", "seg_i", "nodes", "map_idx", "start", "len", "flip", "round_pos", "out",
+    decls = _lib.read_header()[0]
+    assert "osuf_encode_signals" in decls, "osuf_encode_signals is not declared in include/osufusion_hip.h"
+    ret, params = decls["osuf_encode_signals"]
+    assert ret == "int" and [p.split()[-1].lstrip("*") for p in params] == ["map_hdr", "n_maps", "obj_f", "obj_i", "ivl", "seg_cum", "seg_i", "nodes", "map_idx", "start", "len", "flip", "round_pos", "out",
                      "pos_px", "B", "L", "stream"]
     P, I = c_void_p, c_int
     assert _lib.SIGNATURES["osuf_encode_signals"] == [P, I, P, P, P, P, P, P, P, P, P, P, I, P, P, I, I, P]

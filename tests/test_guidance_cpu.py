@@ -2,9 +2,7 @@
 five sampling loops against hand-written expectations (the package's osufusion_amd/guidance.py and the restatement tests/guidance_oracle.py
 side by side), and the C surface of osuf_cfg_rescale: declared, bound, exported, and refusing bad arguments before any launch."""
 import math
-import re
 from ctypes import c_float, c_int, c_long, c_void_p
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -15,7 +13,6 @@ from osufusion_amd.models import ContinuousDiffusionOsuFusionDiT, DiffusionOsuFu
 from osufusion_amd.models.diffusion import DDIMSchedule
 from tests import guidance_oracle as GO
 
-ROOT = Path(__file__).resolve().parent.parent
 INF = math.inf
 
 
@@ -131,15 +128,15 @@ def test_oracle_rescale_by_hand():
 
 # ---- the C surface -----------------------------------------------------------------------------------------------------------------------------
 def test_capi_cfg_rescale_is_declared_bound_and_exported():
-    src = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "osufusion_hip.h").read_text(), flags=re.S)
+    decls = _lib.read_header()[0]
     P, L, I, F = c_void_p, c_long, c_int, c_float
-    decl = re.search(r"\bint\s+osuf_cfg_rescale\s*\(([^)]*)\)\s*;", src)
-    assert decl, "osuf_cfg_rescale is not declared in include/osufusion_hip.h"
-    names = [p.strip().split()[-1].lstrip("*") for p in decl.group(1).split(",")]
-    assert names == ["cond", "nullp", "cond_scale", "phi", "ws", "factor", "out", "B", "per_sample", "stream"]
+    assert "osuf_cfg_rescale" in decls, "osuf_cfg_rescale is not declared in include/osufusion_hip.h"
+    ret, params = decls["osuf_cfg_rescale"]
+    assert ret == "int"
+    assert [p.split()[-1].lstrip("*") for p in params] == ["cond", "nullp", "cond_scale", "phi", "ws", "factor", "out", "B", "per_sample", "stream"]
     assert _lib.SIGNATURES["osuf_cfg_rescale"] == [P, P, F, F, P, P, P, I, L, P]
-    ws = re.search(r"\blong\s+osuf_cfg_rescale_workspace_bytes\s*\(([^)]*)\)\s*;", src)
-    assert ws and [p.strip().split()[-1] for p in ws.group(1).split(",")] == ["B", "per_sample"]
+    ws = decls.get("osuf_cfg_rescale_workspace_bytes")
+    assert ws and ws[0] == "long" and [p.split()[-1] for p in ws[1]] == ["B", "per_sample"]
     assert _lib.SIGNATURES["osuf_cfg_rescale_workspace_bytes"] == [I, L]
     lib = _lib.load()
     assert hasattr(lib, "osuf_cfg_rescale") and lib.osuf_cfg_rescale_workspace_bytes.restype is c_long

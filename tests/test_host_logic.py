@@ -2,7 +2,9 @@
 autograd through a numpy emulation of the tap-GEMM contract in include/osufusion_hip.h), state-dict parity, C-ABI
 surface, DDIM schedule, loud failure without a GPU."""
 import json
+import os
 import re
+import shutil
 import subprocess
 from pathlib import Path
 
@@ -281,29 +283,28 @@ def test_ddim_schedule_known_answers():
 
 
 # ---- C ABI ------------------------------------------------------------------------------------------------------
-def _header_decls():
-    src = (ROOT / "include" / "osufusion_hip.h").read_text()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return re.findall(r"\b(?:int|long)\s+(osuf_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)
-
-
 def test_capi_exports_every_declared_symbol():
     lib_path = _lib.LIB_PATH
     if not lib_path.exists():
         from osufusion_amd.csrc import build
         build.build()
-    decls = _header_decls()
+    decls = _lib.read_header()[0]
     assert len(decls) >= 29
     syms = subprocess.run(["nm", "-D", "--defined-only", str(lib_path)], capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r" T (osuf_\w+)", syms))
-    for name, _ in decls:
+    for name in decls:
         assert name in exported, f"{name} declared in include/osufusion_hip.h but not exported by libosuf_hip.so"
-    assert set(_lib.SIGNATURES) == {n for n, _ in decls}
+    assert set(_lib.SIGNATURES) == set(decls)
 
 
 def test_capi_ctypes_signatures_match_header():
+    """A second reading of the header's text, independent of _lib.read_header, against what _lib.load() installed on the library."""
     from ctypes import c_float, c_int, c_long, c_void_p
-    for name, params in _header_decls():
+    src = re.sub(r"/\*.*?\*/", "", _lib.HEADER.read_text(), flags=re.S)
+    decls = re.findall(r"\b(int|long)\s+(osuf_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)
+    lib = _lib.load()
+    assert len(decls) == len(_lib.SIGNATURES) >= 105
+    for ret, name, params in decls:
         ps = [p.strip() for p in params.split(",")] if params.strip() != "void" else []
         want = []
         for p in ps:
@@ -317,7 +318,41 @@ def test_capi_ctypes_signatures_match_header():
                 want.append(c_float)
             else:
                 raise AssertionError(f"unparsed parameter {p!r} of {name}")
-        assert _lib.SIGNATURES[name] == want, name
+        assert list(getattr(lib, name).argtypes) == want == _lib.SIGNATURES[name], name
+        assert getattr(lib, name).restype is {"int": c_int, "long": c_long}[ret], name
+
+
+def test_capi_header_is_valid_c99(tmp_path):
+    """The header alone, as a C caller includes it: the host C compiler in syntax-only mode, with ROCm's include directory for hip_runtime_api.h."""
+    cc = next((c for c in ("cc", "gcc", "clang") if shutil.which(c)), None)
+    if cc is None:
+        pytest.skip("no host C compiler (cc, gcc or clang) on PATH")
+    src = tmp_path / "caller.c"
+    src.write_text('#include "osufusion_hip.h"\nint main(void) { return OSUF_OK; }\n')
+    run = subprocess.run([cc, "-std=c99", "-fsyntax-only", "-D__HIP_PLATFORM_AMD__", "-I", str(_lib.HEADER.parent),
+                          "-I", str(Path(os.environ.get("ROCM_PATH", "/opt/rocm")) / "include"), str(src)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr
+
+
+def test_capi_csrc_defines_nothing_the_header_defines():
+    """The header's macros, enumerators and structs exist once: an identical macro redefinition under csrc/ would compile silently, and
+    a second copy is where the two comments start to disagree."""
+    src = re.sub(r"/\*.*?\*/", "", _lib.HEADER.read_text(), flags=re.S)
+    consts = _lib.read_header()[1]
+    structs = set(re.findall(r"\bstruct\s+(osuf_\w+)", src))
+    assert {"OSUF_OK", "OSUF_EINVAL", "OSUF_DT_BF16", "OSUF_DQ_PREZEROED", "OSUF_CT_OBJ_V", "OSUF_KNOB_COUNT", "OSUF_KNOB_DEFAULT"} <= set(consts)
+    assert structs == {"osuf_pack_desc", "osuf_linear_desc"}
+    csrc = ROOT / "osufusion_amd" / "csrc"
+    files = [p for p in sorted(csrc.iterdir()) if p.suffix in (".hip", ".hpp", ".h", ".inc")]
+    assert len(files) >= 14, [p.name for p in files]
+    assert re.search(r'^#include "osufusion_hip\.h"', (csrc / "common.hpp").read_text(), flags=re.M), "common.hpp does not include the header"
+    for path in files:
+        text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", path.read_text(), flags=re.S))
+        defined = set(re.findall(r"^\s*#\s*define\s+(\w+)", text, flags=re.M)) | set(re.findall(r"\bstruct\s+(\w+)\s*\{", text))
+        defined |= set(re.findall(r"\}\s*(\w+)\s*;", text))                                  # typedef struct { ... } name;
+        for body in re.findall(r"\benum\b[^{;]*\{(.*?)\}", text, flags=re.S):
+            defined |= set(re.findall(r"(\w+)\s*(?:=[^,]*)?(?:,|$)", body.strip()))
+        assert not defined & (set(consts) | structs), (path.name, sorted(defined & (set(consts) | structs)))
 
 
 def test_capi_descriptor_structs_match_their_numpy_layouts():

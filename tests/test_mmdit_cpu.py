@@ -1,7 +1,6 @@
 """CPU checks of the MMDiT backbone (osufusion_amd/modules/mmdit.py): module layout against the reference, the constructor guards, the
 torch restatement (tests/mmdit_oracle.py) against the reference's recorded fixtures, and the C ABI of the joint-attention row kernels."""
 import json
-import re
 from ctypes import c_float, c_int, c_long, c_void_p
 from pathlib import Path
 
@@ -144,20 +143,14 @@ def test_joint_attention_restatement_matches_reference_fixture():
 
 
 # ---- C ABI of the joint-attention row kernels (what tests/test_host_logic.py::test_capi_* check for every symbol) -----------------
-def _header_decls():
-    src = (ROOT / "include" / "osufusion_hip.h").read_text()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return dict(re.findall(r"\b(?:int|long)\s+(osuf_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S))
-
-
 def test_capi_declares_and_binds_the_joint_entry_points():
-    decls = _header_decls()
+    decls = _lib.read_header()[0]
     kinds = {"*": c_void_p, "hipStream_t": c_void_p, "long": c_long, "int": c_int, "float": c_float}
     for name in JOINT_ENTRY_POINTS:
         assert name in decls, f"{name} is not declared in include/osufusion_hip.h"
         assert name in _lib.SIGNATURES, f"{name} is not bound in osufusion_amd/_lib.py"
         want = []
-        for prm in (s.strip() for s in decls[name].split(",")):
+        for prm in decls[name][1]:
             key = "*" if "*" in prm else prm.split()[0]
             want.append(kinds[key])
         assert _lib.SIGNATURES[name] == want, name

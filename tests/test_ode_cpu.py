@@ -6,10 +6,8 @@ conditions are the proof."""
 import ctypes
 import inspect
 import math
-import re
 from ctypes import c_int, c_long, c_void_p
 from fractions import Fraction as Fr
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -19,8 +17,6 @@ from osufusion_amd import _lib, ode
 from osufusion_amd.models import RectifiedFlowOsuFusionDiT
 from osufusion_amd.models.rectified_flow import OsuFusion as FlowOsuFusion
 from tests import ode_oracle as OO
-
-ROOT = Path(__file__).resolve().parent.parent
 
 
 # ---- order conditions ----------------------------------------------------------------------------------------------------------------------------
@@ -255,12 +251,11 @@ def test_the_samplers_take_the_solver_keywords():
 
 # ---- the C surface -------------------------------------------------------------------------------------------------------------------------------
 def test_capi_rk_error_is_declared_bound_and_exported():
-    src = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "osufusion_hip.h").read_text(), flags=re.S)
+    decls = _lib.read_header()[0]
     P, L, I = c_void_p, c_long, c_int
-    decl = re.search(r"\bint\s+osuf_rk_error\s*\(([^)]*)\)\s*;", src)
-    assert decl, "osuf_rk_error is not declared in include/osufusion_hip.h"
-    names = [p.strip().split()[-1].lstrip("*") for p in decl.group(1).split(",")]
-    assert names == ["y0", "y1", "k", "e", "S", "step", "ws", "ratio", "B", "per_sample", "stream"]
+    assert "osuf_rk_error" in decls, "osuf_rk_error is not declared in include/osufusion_hip.h"
+    ret, params = decls["osuf_rk_error"]
+    assert ret == "int" and [p.split()[-1].lstrip("*") for p in params] == ["y0", "y1", "k", "e", "S", "step", "ws", "ratio", "B", "per_sample", "stream"]
     assert _lib.SIGNATURES["osuf_rk_error"] == [P, P, P, P, I, P, P, P, I, L, P]
     assert _lib.SIGNATURES["osuf_rk_error_workspace_bytes"] == [I, L]
     lib = _lib.load()

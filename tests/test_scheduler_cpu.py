@@ -2,7 +2,6 @@
 (tests/golden/scheduler_cases.npz), the time grids, the error text, the exports, the model's constructor and the C ABI of the two entry
 points.  The bounds are written down in profiles/ct_scheduler_parity.md."""
 import inspect
-import re
 from ctypes import c_float, c_int, c_long, c_void_p
 from pathlib import Path
 
@@ -142,7 +141,7 @@ def test_model_constructor(backbone):
 
 
 def test_capi_ct_entry_points_are_declared_and_bound():
-    src = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "osufusion_hip.h").read_text(), flags=re.S)
+    decls = _lib.read_header()[0]
     P, L, I, F = c_void_p, c_long, c_int, c_float
     kinds = {"*": P, "hipStream_t": P, "long": L, "int": I, "float": F}
     want_names = {
@@ -150,10 +149,9 @@ def test_capi_ct_entry_points_are_declared_and_bound():
         "osuf_ct_step": ["x", "cond", "nullp", "cond_scale", "coef", "noise", "out", "B", "per_sample", "stream"],
     }
     for name, names in want_names.items():
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-        assert decl, f"{name} is not declared in include/osufusion_hip.h"
-        params = [p.strip() for p in decl.group(1).split(",")]
-        assert [p.split()[-1].lstrip("*") for p in params] == names
+        assert name in decls, f"{name} is not declared in include/osufusion_hip.h"
+        ret, params = decls[name]
+        assert ret == "int" and [p.split()[-1].lstrip("*") for p in params] == names
         assert _lib.SIGNATURES[name] == [kinds["*" if "*" in p else p.split()[0]] for p in params], name
         assert hasattr(_lib.load(), name)
     from osufusion_amd import ct, ops

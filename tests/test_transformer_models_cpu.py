@@ -1,7 +1,6 @@
 """CPU checks of the DiT / MMDiT model wrappers (osufusion_amd/models/transformer_diffusion.py): state-dict layout, constructor, the DDIM
 schedule against the oracle, gradient checkpointing, the GPU-only guard, and the C ABI of the one-launch grouped attention forward."""
 import json
-import re
 from ctypes import c_float, c_int, c_long, c_void_p
 from pathlib import Path
 
@@ -107,11 +106,10 @@ def test_one_launch_switch_is_off_by_default_and_restored():
 
 
 def test_capi_gqa_fwd_is_declared_bound_and_exported():
-    src = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "osufusion_hip.h").read_text(), flags=re.S)
-    decl = re.search(r"\bint\s+osuf_gqa_fwd\s*\(([^)]*)\)\s*;", src)
-    assert decl, "osuf_gqa_fwd is not declared in include/osufusion_hip.h"
-    names = [p.strip().split()[-1].lstrip("*") for p in decl.group(1).split(",")]
-    assert names == ["q", "ldq", "k", "ldk", "v", "ldv", "o", "ldo", "o_dtype", "lse2", "B", "H", "G", "N", "head_dim", "scale", "stream"]
+    decls = _lib.read_header()[0]
+    assert "osuf_gqa_fwd" in decls, "osuf_gqa_fwd is not declared in include/osufusion_hip.h"
+    ret, params = decls["osuf_gqa_fwd"]
+    assert ret == "int" and [p.split()[-1].lstrip("*") for p in params] == ["q", "ldq", "k", "ldk", "v", "ldv", "o", "ldo", "o_dtype", "lse2", "B", "H", "G", "N", "head_dim", "scale", "stream"]
     P, L, I, F = c_void_p, c_long, c_int, c_float
     assert _lib.SIGNATURES["osuf_gqa_fwd"] == [P, L, P, L, P, L, P, L, I, P, I, I, I, I, I, F, P]
     mqa = _lib.SIGNATURES["osuf_mqa_fwd"]
