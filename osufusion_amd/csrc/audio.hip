@@ -177,6 +177,9 @@ extern "C" int osuf_log_vqt(const float* wave_pad, long n_pad, const float* bank
                             float eps, float* spec_ws, float* out, long ldo, long frames, hipStream_t stream) {
   if (!wave_pad || !bank || !spec_ws || frames <= 0 || frames >= (1L << 31) || hop <= 0 || K <= 0) return OSUF_EINVAL;
   if ((frames - 1) * (long)hop + K > n_pad) return OSUF_EINVAL;       // the last frame would read past the buffer
+  // what osuf_vqt_logmag would refuse is refused before the GEMM writes the workspace
+  if (!out || !scale || bins <= 0 || ldo < frames) return OSUF_EINVAL;
+  if ((size_t)kFrames * (2 * bins + 1) * sizeof(float) > 160 * 1024) return OSUF_EUNSUPPORTED;
   const int M = (int)frames, N = 2 * bins;
   int rc = osuf_gemm_nt(OSUF_DT_F32, wave_pad, hop, bank, K, 0, spec_ws, N, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr,
                         nullptr, M, N, K, 1, M, M, 1, 0, 0, 0, stream);

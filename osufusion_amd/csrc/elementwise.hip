@@ -802,9 +802,8 @@ extern "C" int osuf_adapter_finish(const float* tb, const float* sg, float* dB, 
                                    const float* bias, const float* m, float* dm, int O, int I, int k, int r, int accumulate,
                                    hipStream_t stream) {
   if (!tb || !sg || !dB || !gt || !dA || O <= 0 || I <= 0 || k <= 0 || r <= 0 || (dm && (!s0 || !m || (bias && !s1)))) return OSUF_EINVAL;
-  long n = (long)O * r;
+  long n = (long)O * r;                                     // >= O, the third index range
   if ((long)r * I * k > n) n = (long)r * I * k;
-  if (O > n) n = O;
   hipLaunchKernelGGL(adapter_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tb, sg, dB, gt, dA, s0, s1, bias, m, dm, O, I,
                      k, r, accumulate);
   return osuf_launch_status();
